@@ -19,9 +19,11 @@ One process per GPU.  Rank 0 generates the genome and builds the index on its GP
 pos_index / mers / genome / contig table through an RCCL broadcast at start-up (nothing is exchanged while mapping);
 every rank maps its own reads (weak scaling) into its own pileup counters, which are summed once at the end
 (`timings.pileup_reduce_s`, outside the timed region as the reference's final genome walk is).
-The same JSON line carries two more measurements: `secondary` = BASELINE config 3's shape (pemapper_tsw reads: 2 x 250
-bases trimmed 3 / 2, 5 % of the read-ends with one 1..10-base indel), and `pecaller` = BASELINE config 4 (the per-site
-caller on 64-sample 30x pileup columns).  The last line printed by rank 0 is the JSON record.
+A plain run measures the headline alone.  With --full the same JSON line also carries `resident_value`, the CPU baselines
+(the oracle, its results compared with the GPU's), `secondary` = BASELINE config 3's shape (pemapper_tsw reads: 2 x 250
+bases trimmed 3 / 2, 5 % of the read-ends with one 1..10-base indel), `realistic` (the same reads on a genome with few repeat
+tiles) and `pecaller` = BASELINE config 4 (the per-site caller on 64-sample 30x pileup columns).  --dump-outputs DIR writes
+what the last timed step returned (dump_outputs).  The last line printed by rank 0 is the JSON record.
 """
 import argparse
 import json
@@ -61,9 +63,10 @@ def lookup_kernel_name(n_rep):
     return "pm_seed4_kernel" if n_rep else "pm_lookup_wave_kernel"
 
 
-def mapper_leg(dev, a, L, B, steps, warmup, rank, world, barrier, allmax, indel_read_frac=0.0, seed_off=7, seam=True):
-    """K steps of the mapping path on batches of B pairs of L-base reads: at the seam (host buffers in, results out) and on
-    resident reads.  -> dict of rates, per-step kernel times and counters of the seam run (or of the resident run if seam=False)"""
+def mapper_leg(dev, a, L, B, steps, warmup, rank, world, barrier, allmax, indel_read_frac=0.0, seed_off=7, seam=True, resident=True):
+    """K steps of the mapping path on batches of B pairs of L-base reads: at the seam (host buffers in, results out) and, unless
+    resident=False, on resident reads.  -> dict of rates, per-step kernel times and counters of the seam run (or of the resident run
+    if seam=False)"""
     n_batches = steps + warmup
     # at most --host-batches distinct batches exist (generated on the device, staged on the host, pinned); step k maps batch k modulo
     # that number.  (Every batch of a run was distinct until round 3: (steps + warm-up) x 1 M x 2 x 160 B = 8 GB of pinned host memory
@@ -124,6 +127,9 @@ def mapper_leg(dev, a, L, B, steps, warmup, rank, world, barrier, allmax, indel_
         out["mapped_frac"] = mapped / float(2 * B * steps)
         dev.unpin_host(r1)
         dev.unpin_host(r2)
+        if not resident:
+            out.update(host=host, host_batches=NB)
+            return out
         synth()                     # back to one resident read set (same reads)
     # ---- resident: reads already in HBM, results left there; the K steps queued back to back and synchronised once (the library
     #      pipelines the look-ups of a step's first chunk under the previous step's last chunk)
@@ -222,6 +228,23 @@ def roofline_of(leg, dt, steps, L, n_rep, gs, B, config="hg38_150"):
     return roof
 
 
+DUMP_MAX_PAIRS = 1500000        # 4 arrays of float64 at most: 48 MB
+
+
+def dump_outputs(d, res, seed):
+    """what pemap_dev_wait_batch handed back for the last timed step -- m1, m2, mapping_type, one entry per pair -- as DIR/<name>.npy in
+    float64 (coordinates reach 3.1e9: exact in float64, not in float32).  A batch of more than DUMP_MAX_PAIRS pairs is written as a
+    fixed sample of its pairs (drawn from the run's --seed), their indices in pair_index.npy"""
+    os.makedirs(d, exist_ok=True)
+    m1, m2, mt = res
+    idx = None
+    if len(m1) > DUMP_MAX_PAIRS:
+        idx = np.sort(np.random.default_rng(seed).choice(len(m1), DUMP_MAX_PAIRS, replace=False))
+        np.save(os.path.join(d, "pair_index.npy"), idx.astype(np.float64))
+    for name, arr in (("m1", m1), ("m2", m2), ("mapping_type", mt)):
+        np.save(os.path.join(d, name + ".npy"), (arr if idx is None else arr[idx]).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -238,6 +261,11 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the CPU baseline's primary sample; 0 = the physical cores of the host this process may run on "
                          "(SURVEY.md 8(d)); samples with 24 (the authors' default) and 16 threads are reported beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline too: the resident rate, the CPU baselines (the oracle, compared "
+                         "with the GPU's results), the 2x250 `secondary` leg, the `realistic` genome and the PECaller leg; the --no-* "
+                         "options below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write m1 / m2 / mapping_type of the last timed step (rank 0) to DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the pemapper_tsw 2x250 leg")
@@ -364,20 +392,24 @@ def main():
     TSW_L = 245                     # 250-base reads after pemapper_tsw's trims of 3 / 2 (pemapper_tsw.c:693-704; the golden's values)
     main_leg = None
     if not tsw_only:
-        main_leg = mapper_leg(dev, a, a.read_len, B, a.steps, a.warmup, rank, world, barrier, allmax)
+        main_leg = mapper_leg(dev, a, a.read_len, B, a.steps, a.warmup, rank, world, barrier, allmax, resident=a.full)
     sec_leg = None
-    if tsw_only or not a.no_secondary:
+    if tsw_only or (a.full and not a.no_secondary):
         k, w = (a.steps, a.warmup) if tsw_only else (a.secondary_steps, 1)
-        sec_leg = mapper_leg(dev, a, TSW_L, B, k, w, rank, world, barrier, allmax, indel_read_frac=0.05, seed_off=11, seam=True)
+        sec_leg = mapper_leg(dev, a, TSW_L, B, k, w, rank, world, barrier, allmax, indel_read_frac=0.05, seed_off=11, seam=True,
+                             resident=a.full)
         sec_leg["steps"] = k
 
     leg0 = sec_leg if tsw_only else main_leg
-    step_rows = gather_ranks([leg0["seam_dt_local"] / a.steps * 1e3, leg0["resident_dt_local"] / a.steps * 1e3, leg0["mapped_frac"],
+    step_rows = gather_ranks([leg0["seam_dt_local"] / a.steps * 1e3, leg0.get("resident_dt_local", 0.0) / a.steps * 1e3, leg0["mapped_frac"],
                               leg0["stats"]["big_ends"] / a.steps])
     ranks = [{"rank": r, "lookup_replicas": int(setup_rows[r][0]), "hbm_free_after_setup_GiB": round(setup_rows[r][1], 1),
               "hbm_total_GiB": round(setup_rows[r][2], 1), "setup_s": round(setup_rows[r][3], 2), "ms_per_step": round(step_rows[r][0], 3),
               "resident_ms_per_step": round(step_rows[r][1], 3), "mapped_frac": round(step_rows[r][2], 4), "big_ends_per_step": int(step_rows[r][3])}
              for r in range(world)]
+    if not a.full:
+        for row in ranks:
+            del row["resident_ms_per_step"]
     # ---- end of the run: the per-GPU pileup partials are summed (the reference's one shared all_base_list, pemapper.c:156)
     if world > 1:
         cnt = pd.device_tensor(torch, dev, 4)
@@ -407,10 +439,11 @@ def main():
         reads_per_step = 2 * B
         dt = leg["seam_dt"]
         value = world * steps * reads_per_step / dt / 1e6
-        resident = world * steps * reads_per_step / leg["resident_dt"] / 1e6
         roof = roofline_of(leg, dt, steps, L, n_rep, gs, B)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, leg["results"][a.warmup + steps - 1], a.seed)
         cpu = None
-        if world == 1 and not a.no_cpu:
+        if world == 1 and a.full and not a.no_cpu:
             cpu = cpu_baseline(dev, a, B, leg, a.warmup)
         rec = {
             "metric": "M reads mapped/sec (whole node), 2x150bp PE synthetic hg38",
@@ -419,7 +452,6 @@ def main():
             "dtype": "f64", "data": "synthetic",
             "timed_region": "host buffers of reads in -> m1/m2/mapping_type in host memory (pemap_dev_submit_batch / pemap_dev_wait_batch, "
                             "2 batches in flight, PCIe both ways included)",
-            "resident_value": round(resident, 4), "resident_ms_per_step": round(leg["resident_dt"] / steps * 1e3, 3),
             "mapped_frac": round(leg["mapped_frac"], 4), "mapped_reads_per_s_M": round(value * leg["mapped_frac"], 4),
             "config": {"workload": "hg38-sized synthetic index resident in HBM (%.2f Gbp, %d contigs, %d%% repeat tiles), "
                                    "2x%dbp paired-end reads, %d pairs per step per GPU" % (gs / 1e9, n_contigs, int(a.repeat_frac * 100), L, B),
@@ -431,6 +463,9 @@ def main():
             "roofline": roof, "cpu_baseline": cpu, "timings": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in timings.items()},
             "counters_per_step": {k: int(v / steps) for k, v in leg["stats"].items()},
         }
+        if "resident_dt" in leg:
+            rec["resident_value"] = round(world * steps * reads_per_step / leg["resident_dt"] / 1e6, 4)
+            rec["resident_ms_per_step"] = round(leg["resident_dt"] / steps * 1e3, 3)
         if tsw_only:
             rec["metric"] = "M reads mapped/sec, pemapper_tsw path, 2x250bp (trimmed 3/2) 5% indel-enriched reads"
         elif sec_leg is not None:
@@ -446,7 +481,7 @@ def main():
                 "mapped_frac": round(sec_leg["mapped_frac"], 4),
                 "roofline": roofline_of(sec_leg, sdt, ks, TSW_L, n_rep, gs, B, config="tsw250"),
                 "counters_per_step": {k: int(v / ks) for k, v in sec_leg["stats"].items()}}
-        if world == 1 and not tsw_only and a.realistic_steps > 0:
+        if world == 1 and a.full and not tsw_only and a.realistic_steps > 0:
             # ---- the workload's own weakness: a third of its reads never seed (high-copy repeat tiles, N blocks), so H = 0.66
             #      alignments per end where real hg38 reads map at > 95 % with H >= 1.  The same path on a genome of the same size
             #      with 2 % repeat tiles: every number of the headline again, with its own check against the CPU oracle
@@ -480,7 +515,7 @@ def main():
             # (beside `value`: what a genome with hg38's share of mappable sequence gives)
             rec["realistic_value"] = rec["realistic"]["value"]
             rec["realistic_ms_per_step"] = rec["realistic"]["ms_per_step"]
-        if world == 1 and not a.no_pecaller and not tsw_only:
+        if world == 1 and a.full and not a.no_pecaller and not tsw_only:
             dev.close()
             dev = None
             rec["pecaller"] = pecaller_leg(a)

@@ -49,7 +49,7 @@ def test_bench_two_ranks_runs_the_broadcast_and_the_reduction(tmp_path):
     """bench.py --gpus 2 as the driver launches it, on a small genome: the N > 1 branch (broadcast into the device buffers,
     sharded reads, max-over-ranks timing, end-of-run pileup sum with its check) runs and prints one JSON line"""
     r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--genome-size", "2.5e8", "--batch-pairs", "100000",
-                 "--steps", "2", "--warmup", "1", "--no-cpu", "--no-secondary", "--no-pecaller"], tmp_path, 29500 + os.getpid() % 200)
+                 "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-secondary", "--no-pecaller"], tmp_path, 29500 + os.getpid() % 200)
     assert r.returncode == 0, r.stdout[-3000:].decode(errors="replace")
     rec = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 2 and rec["value"] > 0 and rec["resident_value"] > 0

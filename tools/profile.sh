@@ -1,16 +1,16 @@
 #!/bin/bash
 # rocprofv3 passes behind profiles/: kernel-trace stats, then FETCH_SIZE and WRITE_SIZE in separate --pmc runs.
 # Run on the GPU box from the repo root:  tools/profile.sh <tag> [config]   (config: hg38_150 (default) or tsw250)
-#   -> gpurun_out/prof_<tag>/{stats.csv, pmc.json, ...}; copy pmc.json to profiles/r04_bench_pmc_<config>.json
+#   -> $TOOL_OUT/prof_<tag>/{stats.csv, pmc.json, ...} (TOOL_OUT: tool_out/ unless set); copy pmc.json to profiles/r04_bench_pmc_<config>.json
 # (the program itself follows `--`: no env / bash -c hop between the profiler and python3)
 set -e
 TAG=${1:-r03}
 CFG=${2:-hg38_150}
 ROOT=$(pwd)
-OUT=$ROOT/gpurun_out/prof_$TAG
+OUT=${TOOL_OUT:-$ROOT/tool_out}/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--config $CFG --no-cpu --no-secondary --no-pecaller --realistic-steps 0"
+ARGS="--full --config $CFG --no-cpu --no-secondary --no-pecaller --realistic-steps 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --steps 4 --warmup 1 $ARGS > $OUT/stats.log 2>&1
 echo "stats pass done"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 $ROOT/bench.py --steps 2 --warmup 1 $ARGS > $OUT/fetch.log 2>&1

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include "../../include/pemap_hip.h"
 #include "pemap_kernels.hip.h"
@@ -56,11 +57,10 @@ static std::vector < PmPinned > g_pinned;
 
 // Tuning knobs.  The environment is read ONCE, by pemap_dev_create, into the object: nothing below
 // calls getenv again, so two objects of one process may run with different settings and a setting cannot change under a
-// run.  None is needed in normal use.  The two timing probes that cut kernels short (and so return wrong results) exist
-// only in a library built with -DPEMAP_TIMING_PROBES, which the product build does not define.
+// run.  None is needed in normal use.
 struct PmKnobs
 {
-  int seed_blocks_per_cu, big_blocks_per_cu, sw_waves_per_cu;
+  int big_blocks_per_cu, sw_waves_per_cu;
   int replicas;                 // -1 unset, 0 never, 1 as the default
   int gapless;                  // 0 off, 1 first case only, 2 both
   double dir_budget_gb;
@@ -68,11 +68,10 @@ struct PmKnobs
   int lookup_prio, vote_prio, sw_prio;
   int vote_waves;
   int walk_blocks_per_cu, pile_blocks_per_cu;
-  int pipeline;
+  int pipeline;                 // 1 the seed stage on a stream of its own, two chunks ahead; 2 everything on the ALU stream
   int chunk_pairs;
   int gapless_blocks_per_cu;
   int band, band_waves_per_cu;  // the banded DP (pm_band_kernel) for the problems it is exact for; its waves per CU
-  int seed_phase;               // always 0 without PEMAP_TIMING_PROBES
   int tier2_waves;              // persistent waves per CU of the fused seed kernel's second tier (the first tier's big-end list)
 };
 
@@ -84,11 +83,9 @@ static int env_int (const char *name, int dflt)
 
 static void read_knobs (PmKnobs & k)
 {
-  k.seed_blocks_per_cu = env_int ("PEMAP_SEED_BLOCKS_PER_CU", 8);
   k.big_blocks_per_cu = env_int ("PEMAP_BIG_BLOCKS_PER_CU", 8);
   k.sw_waves_per_cu = env_int ("PEMAP_SW_WAVES_PER_CU", 16);
   // a grid of zero or fewer blocks is not a setting
-  if (k.seed_blocks_per_cu < 1) k.seed_blocks_per_cu = 1;
   if (k.big_blocks_per_cu < 1) k.big_blocks_per_cu = 1;
   if (k.sw_waves_per_cu < 1) k.sw_waves_per_cu = 1;
   k.replicas = getenv ("PEMAP_REPLICAS") ? (env_int ("PEMAP_REPLICAS", 1) ? 1 : 0) : -1;
@@ -97,6 +94,7 @@ static void read_knobs (PmKnobs & k)
   k.lookup_waves = env_int ("PEMAP_LOOKUP_WAVES", -1);
   k.lookup_prio = env_int ("PEMAP_LOOKUP_PRIO", 0);
   k.tier2_waves = env_int ("PEMAP_TIER2_WAVES", 3);
+  if (k.tier2_waves < 1) k.tier2_waves = 1;
   k.vote_prio = env_int ("PEMAP_VOTE_PRIO", 0);
   k.sw_prio = env_int ("PEMAP_SW_PRIO", 0);
   k.vote_waves = env_int ("PEMAP_VOTE_WAVES", 1024);
@@ -112,10 +110,6 @@ static void read_knobs (PmKnobs & k)
   if (k.gapless_blocks_per_cu == 0) k.gapless_blocks_per_cu = 1;
   k.band_waves_per_cu = env_int ("PEMAP_BAND_WAVES_PER_CU", 16);
   if (k.band_waves_per_cu < 1) k.band_waves_per_cu = 1;
-  k.seed_phase = 0;
-#ifdef PEMAP_TIMING_PROBES
-  k.seed_phase = env_int ("PEMAP_SEED_PHASE", 0);
-#endif
 }
 
 struct pemap_dev
@@ -137,8 +131,7 @@ struct pemap_dev
   bool index_ready;
   uint32_t *d_counts;           // the pileup counter planes (PmPile): 6 planes of pile_plane_words words
   size_t pile_plane_words;
-  bool rest_on_alu;
-  // each chunk's seed-stage remainder (big read-ends + emit) is enqueued exactly once: checked in launch_vote (the round-3 fault)
+  // each chunk's big-end remainder is enqueued exactly once: checked in launch_rest (the round-3 fault)
   uint64_t run_serial, rest_id[2];
   bool rest_twice;
   // params
@@ -154,7 +147,6 @@ struct pemap_dev
   PmHits hits;
   uint32_t *d_tasks_s, *d_tasks_m, *d_redo, *d_wins;
   uint32_t *d_tasks_s2, *d_tasks_m2;      // second set: the vote of the next chunk runs beside the SW of this one
-  bool vote_on_mem;
   // second set of the arrays the walk kernel reads, so that walk(chunk k) can run beside vote/SW(chunk k+1)
   PmHits hits2;
   uint32_t *d_wins2, *d_dirbuf2;
@@ -173,19 +165,15 @@ struct pemap_dev
   size_t dir_slabs;             // slabs d_dirbuf holds for the staged read length; the last one is the dump slab of task-less lane groups
   uint8_t *d_ins_log;
   unsigned ins_cap;
-  int seed_grid, sw_grid;
+  int sw_grid;
   // run bookkeeping
   int run_first, run_n;
   bool run_pending;             // kernels of the last run still in flight / not yet accounted
-  bool run_split, serial_split;
   int run_chunks, run_chunk_pairs, run_L;
   uint64_t run_ends;
   hipEvent_t ev[7];
   // two-stream pipeline: the look-up kernel of chunk k+1 (memory stream) runs beside vote/SW/walk of chunk k
   hipStream_t stream2;
-  hipStream_t stream3;          // the vote's own stream (PEMAP_VOTE_ON_MEM=2)
-  hipEvent_t ev_lookup_done[2];
-  int vote_stream;
   int n_cus;
   hipEvent_t ev_lists_ready[2], ev_lists_free[2];
   PmLists lists[2];
@@ -193,8 +181,8 @@ struct pemap_dev
   bool lists_arrays;            // the (key, segment) lists exist (not needed, and not allocated, while the fused seed kernel serves)
   PmChunkCtr *d_chunk_ctr;
   std::vector < hipEvent_t > evs;
-  int big_grid, scratch_blocks;
-  uint64_t last_big, last_big2;  // read-ends the fused seed kernel's first tier passed over; of them, left to the monolithic kernel
+  int big_grid;
+  uint64_t last_big, last_big2;  // read-ends the fused seed kernel's first tier passed over; of them, left to pm_seed_kernel
   PmCounters last_ctr;          // summed over the chunks of the last run
   PmInsCursor last_cur;
   // batches in flight
@@ -291,9 +279,6 @@ extern "C" int pemap_dev_create (pemap_dev ** out, int device_id)
   d->path_words = d->path_cap_ends = 0;
   d->d_tasks_s = d->d_tasks_m = d->d_redo = d->d_wins = d->d_m1 = d->d_m2 = nullptr;
   d->d_tasks_s2 = d->d_tasks_m2 = nullptr;
-  d->vote_on_mem = false;
-  d->stream3 = nullptr;
-  d->vote_stream = 0;
   d->d_cur = nullptr;
   d->dirbuf_dwords = 0;
   memset (&d->last_cur, 0, sizeof (d->last_cur));
@@ -306,7 +291,6 @@ extern "C" int pemap_dev_create (pemap_dev ** out, int device_id)
   d->ins_cap = 0;
   d->run_first = d->run_n = 0;
   d->run_pending = false;
-  d->run_split = false;
   d->run_chunks = 0;
   d->stream2 = nullptr;
   memset (d->lists, 0, sizeof (d->lists));
@@ -349,15 +333,18 @@ extern "C" int pemap_dev_create (pemap_dev ** out, int device_id)
     }
   int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   read_knobs (d->kn);
-  // pm_seed_kernel is launched with seed_grid blocks (monolithic form) or big_grid blocks (list mode, the big read-ends of the
-  // split pipeline); every block owns one spill area of d_seed_scratch, which is sized for the LARGER of the two grids
-  // (scratch_blocks) and passed to the kernel as its capacity.  (Round 1: the area was sized by seed_grid alone, an A/B run
+  if (d->kn.pipeline != 1 && d->kn.pipeline != 2)
+    {
+      fail (nullptr, "PEMAP_PIPELINE=%d: the settings are 1 (the default) and 2", d->kn.pipeline);
+      delete d;
+      return 1;
+    }
+  // pm_seed_kernel is launched with big_grid blocks; every block owns one spill area of d_seed_scratch, which is sized for
+  // big_grid blocks and passed to the kernel as its capacity.  (Round 1: the area was sized by another grid, an A/B run
   // raised big_grid above it through an environment knob, and the blocks beyond it wrote past the allocation: the memory
-  // access fault of gpurun_out/ab_rep15.log.  DESIGN.md section 8.)
-  d->seed_grid = cus * d->kn.seed_blocks_per_cu;
+  // access fault of DESIGN.md section 8.)
   d->sw_grid = cus * d->kn.sw_waves_per_cu;
   d->big_grid = cus * d->kn.big_blocks_per_cu;
-  d->scratch_blocks = d->seed_grid > d->big_grid ? d->seed_grid : d->big_grid;
   d->n_cus = cus;
   if (hipStreamCreateWithFlags (&d->stream, hipStreamNonBlocking) != hipSuccess)
     {
@@ -491,14 +478,6 @@ extern "C" void pemap_dev_destroy (pemap_dev * d)
         hipEventDestroy (d->evs[i]);
       hipFree (d->d_chunk_ctr);
       hipStreamDestroy (d->stream2);
-      if (d->stream3)
-        {
-          hipStreamSynchronize (d->stream3);
-          hipStreamDestroy (d->stream3);
-          hipEventDestroy (d->ev_lookup_done[0]);
-          hipEventDestroy (d->ev_lookup_done[1]);
-          d->stream3 = nullptr;
-        }
     }
   hipStreamDestroy (d->stream);
   delete d;
@@ -943,44 +922,40 @@ static int alloc_hits (pemap_dev * d, PmHits & h, int n_ends)
   return 0;
 }
 
-static int ensure_work (pemap_dev * d, int n_ends, bool two_sets)
+static int ensure_work (pemap_dev * d, int n_ends)
 {
-  if (n_ends > d->cap_ends || (two_sets && !d->hits2.n_hits))
+  if (n_ends > d->cap_ends || !d->hits2.n_hits)
     {
       free_work (d);
       size_t nh = (size_t) n_ends * PM_MAX_HITS;
       TRY (alloc_hits (d, d->hits, n_ends));
       TRY (dev_alloc (d, &d->d_wins, (size_t) n_ends));
-      if (two_sets)
-        {
-          TRY (alloc_hits (d, d->hits2, n_ends));
-          TRY (dev_alloc (d, &d->d_wins2, (size_t) n_ends));
-          TRY (dev_alloc (d, &d->d_tasks_s2, (size_t) n_ends * 3));       // second third: the problems left to the DP, last third: to the banded DP
-          TRY (dev_alloc (d, &d->d_tasks_m2, nh * 3));
-        }
+      TRY (alloc_hits (d, d->hits2, n_ends));
+      TRY (dev_alloc (d, &d->d_wins2, (size_t) n_ends));
+      TRY (dev_alloc (d, &d->d_tasks_s2, (size_t) n_ends * 3));       // second third: the problems left to the DP, last third: to the banded DP
+      TRY (dev_alloc (d, &d->d_tasks_m2, nh * 3));
       TRY (dev_alloc (d, &d->d_tasks_s, (size_t) n_ends * 3));
       TRY (dev_alloc (d, &d->d_tasks_m, nh * 3));
       TRY (dev_alloc (d, &d->d_redo, (size_t) n_ends));
       d->cap_ends = n_ends;
     }
   if (!d->d_seed_scratch)
-    TRY (dev_alloc (d, &d->d_seed_scratch, (size_t) d->scratch_blocks * 6 * PM_MAX_SEG * PM_SEG_LIST_MAX));
+    TRY (dev_alloc (d, &d->d_seed_scratch, (size_t) d->big_grid * 6 * PM_MAX_SEG * PM_SEG_LIST_MAX));
   size_t need = ((size_t) n_ends + 1) * slab_dwords_for (d, d->max_len_staged);       // + 1: dump slab for task-less lane groups
-  if (need > d->dirbuf_dwords || (two_sets && !d->d_dirbuf2))
+  if (need > d->dirbuf_dwords || !d->d_dirbuf2)
     {
       hipFree (d->d_dirbuf);
       hipFree (d->d_dirbuf2);
       d->d_dirbuf = d->d_dirbuf2 = nullptr;
       d->dirbuf_dwords = 0;
       TRY (dev_alloc (d, &d->d_dirbuf, need));
-      if (two_sets)
-        TRY (dev_alloc (d, &d->d_dirbuf2, need));
+      TRY (dev_alloc (d, &d->d_dirbuf2, need));
       d->dirbuf_dwords = need;
     }
   d->dir_slabs = d->dirbuf_dwords / slab_dwords_for (d, d->max_len_staged);
   // recorded traceback steps: PM_PATH_WORDS words of 32 two-bit steps per read-end
   const int pwords = PM_PATH_WORDS (d->max_len_staged);
-  if (!d->d_path || n_ends > d->path_cap_ends || pwords != d->path_words || (two_sets && !d->d_path2))
+  if (!d->d_path || n_ends > d->path_cap_ends || pwords != d->path_words || !d->d_path2)
     {
       hipFree (d->d_path);
       hipFree (d->d_path2);
@@ -992,11 +967,8 @@ static int ensure_work (pemap_dev * d, int n_ends, bool two_sets)
       d->path_cap_ends = n_ends;
       TRY (dev_alloc (d, &d->d_path, (size_t) n_ends * pwords));
       TRY (dev_alloc (d, &d->d_nsteps, (size_t) n_ends));
-      if (two_sets)
-        {
-          TRY (dev_alloc (d, &d->d_path2, (size_t) n_ends * pwords));
-          TRY (dev_alloc (d, &d->d_nsteps2, (size_t) n_ends));
-        }
+      TRY (dev_alloc (d, &d->d_path2, (size_t) n_ends * pwords));
+      TRY (dev_alloc (d, &d->d_nsteps2, (size_t) n_ends));
     }
   // insertion log: 64 bytes per read-end of a chunk is ample for real data, and at least 512 MB so that runs queued back to
   // back (the log is drained when a run is absorbed) do not fill it; overflow is reported as an error
@@ -1085,7 +1057,7 @@ struct PmChunkCtr
   unsigned long long positions;
   unsigned n_big;
   unsigned next_end;            // work counter of the persistent look-up waves
-  unsigned n_big2;              // read-ends the second tier of the fused seed kernel leaves to the monolithic kernel
+  unsigned n_big2;              // read-ends the second tier of the fused seed kernel leaves to pm_seed_kernel
   unsigned next_end2;           // the second tier's work counter
 };
 
@@ -1098,20 +1070,44 @@ static int seg_template (int L)
   return segs <= 7 ? 7 : segs <= 10 ? 10 : segs <= 13 ? 13 : segs <= 16 ? 16 : 19;
 }
 
-// ---- the memory stream's work for one chunk: look-ups + slice gather into the slot's lists
+// f (std::integral_constant < int, SM >) for the segment template SM of reads up to L bases
+template < class F > static void with_seg_template (int L, F f)
+{
+  switch (seg_template (L))
+    {
+    case 7: f (std::integral_constant < int, 7 > {}); break;
+    case 10: f (std::integral_constant < int, 10 > {}); break;
+    case 13: f (std::integral_constant < int, 13 > {}); break;
+    case 16: f (std::integral_constant < int, 16 > {}); break;
+    default: f (std::integral_constant < int, 19 > {}); break;
+    }
+}
+
 // is the seed stage of this run the fused kernel (pm_seed4_kernel: look-ups and vote of a read-end in one wave)?
 static bool pm_fused (const pemap_dev * d)
 {
   return d->n_rep == 8;
 }
 
-static void launch_lookup (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr * cc, hipEvent_t * ev, bool split)
+// The seed stage's schedule, decided once per run by run_slice ("The seed stage's schedule"):
+//   layout     PEMAP_PIPELINE  seed stream, per chunk                                 ALU stream, per chunk, before the DP
+//   fused      1               tier 0, tier 1, remainder, emit unless emit_on_alu     emit, if emit_on_alu
+//   reference  1               look-ups                                               vote, remainder, emit
+//   either     2               the same kernels in the same order, all on the ALU stream, no look-ahead
+struct PmSchedule
+{
+  hipStream_t seed;             // the seed stage's stream: stream2, or the ALU stream with PEMAP_PIPELINE=2
+  bool ahead;                   // the seed stage runs two chunks ahead of the ALU stream
+  bool emit_on_alu;             // the fused layout's emit kernel goes to the ALU stream in front of the chunk's DP
+};
+
+// ---- the look-ups of one chunk: the fused seed kernel's two tiers, or the reference layout's look-ups into the slot's lists
+static void launch_lookup (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
 {
   PmLists L = d->lists[slot];
   L.n_big = &cc->n_big;
   L.positions = &cc->positions;
   L.next_end = &cc->next_end;
-  hipStream_t st = d->serial_split ? d->stream : d->stream2;
   // (an event recorded straight after a stream wait is stamped when the wait is queued, not when it is satisfied: the empty
   // kernel makes the stamp the moment the look-up kernel can start, so that ev[0]..ev[1] is the kernel's own duration)
   hipLaunchKernelGGL (pm_nop_kernel, dim3 (1), dim3 (1), 0, st);
@@ -1121,20 +1117,18 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr
   // the third form, 19.6 KB and 168 VGPRs, took 25.2 at its best, 7) -- the kernel itself keeps gaining (5.06 / 4.53 / 4.05 / 3.84 ms per
   // launch) while the other stream's DP kernels lose the SIMDs' registers to it
   int lw = d->kn.lookup_waves > 0 ? d->kn.lookup_waves : 9;
-  if (c.ix.n_rep == 8)
+  if (pm_fused (d))
     {
       // (no more workgroups than are resident at once: a workgroup owns its first ends by its number, and one that starts when
       // another ends -- at the launch's end -- would be the launch's tail)
       size_t lds = 0;
       int per_simd = 2;
-      switch (seg_template (c.L))
-        {
-        case 7: lds = sizeof (PmSeed4Shared < 7, 0 >); per_simd = PM_S4_WAVES_PER_EU; break;
-        case 10: lds = sizeof (PmSeed4Shared < 10, 0 >); per_simd = PM_S4_WAVES_PER_EU; break;
-        case 13: lds = sizeof (PmSeed4Shared < 13, 0 >); break;
-        case 16: lds = sizeof (PmSeed4Shared < 16, 0 >); break;
-        default: lds = sizeof (PmSeed4Shared < 19, 0 >); break;
-        }
+      with_seg_template (c.L, [&] (auto sm)
+      {
+        lds = sizeof (PmSeed4Shared < sm.value, 0 >);
+        if (sm.value <= 10)
+          per_simd = PM_S4_WAVES_PER_EU;
+      });
       const int fit = (int) ((size_t) 160 * 1024 / lds);
       if (lw > fit)
         lw = fit;
@@ -1145,181 +1139,149 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr
   if (lgrid > c.b.n_ends)
     lgrid = c.b.n_ends;
   const int lprio = d->kn.lookup_prio;
-  const bool set2 = split && slot;
-  const PmHits & H = set2 ? d->hits2 : d->hits;
-  // the fused seed kernel (pm_seed4_kernel, tier 0) ...
-#define PM_LK(SM) do { if (c.ix.n_rep == 8) \
-      hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed4_kernel < SM, 0 >), dim3 (lgrid), dim3 (64), sizeof (PmSeed4Shared < SM, 0 >), st, c.ix, c.b, c.prm, H, L, \
-                          (const uint32_t *) nullptr, (const unsigned *) nullptr, lprio); \
-    else hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_lookup_wave_kernel < SM, 4 >), dim3 (lgrid), dim3 (64), 0, st, c.ix, c.b, c.prm, L, lprio); } while (0)
-  switch (seg_template (c.L))
+  const PmHits & H = slot ? d->hits2 : d->hits;
+  if (!pm_fused (d))
     {
-    case 7: PM_LK (7); break;
-    case 10: PM_LK (10); break;
-    case 13: PM_LK (13); break;
-    case 16: PM_LK (16); break;
-    default: PM_LK (19); break;
+      with_seg_template (c.L, [&] (auto sm)
+      {
+        hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_lookup_wave_kernel < sm.value, 4 >), dim3 (lgrid), dim3 (64), 0, st, c.ix, c.b, c.prm, L, lprio);
+      });
+      hipEventRecord (ev[1], st);
+      return;
     }
-#undef PM_LK
-  hipEventRecord (ev[1], st);
-  if (pm_fused (d))
-    {
-      // ... then its second tier over the ends it passed over: the same kernel with four times the list (twice, for reads over 160
-      // bases), a few waves per CU -- most launches find a few thousand ends; what THAT leaves goes to the monolithic kernel (launch_vote)
-      PmLists L2 = L;
-      L2.big_list = L.big_list + d->lists_cap;
-      L2.n_big = &cc->n_big2;
-      L2.next_end = &cc->next_end2;
-      const int grid2 = d->kn.tier2_waves * d->n_cus;
-#define PM_LK2(SM) hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed4_kernel < SM, 1 >), dim3 (grid2), dim3 (64), sizeof (PmSeed4Shared < SM, 1 >), st, c.ix, c.b, c.prm, \
-                                       H, L2, (const uint32_t *) L.big_list, (const unsigned *) L.n_big, lprio)
-      switch (seg_template (c.L))
-        {
-        case 7: PM_LK2 (7); break;
-        case 10: PM_LK2 (10); break;
-        case 13: PM_LK2 (13); break;
-        case 16: PM_LK2 (16); break;
-        default: PM_LK2 (19); break;
-        }
-#undef PM_LK2
-    }
-  if (pm_fused (d))
-    {
-      // the vote is part of the kernel: its interval is empty
-      hipEventRecord (ev[2], st);
-      hipEventRecord (ev[3], st);
-    }
+  // the fused seed kernel's first tier, then its second tier over the ends the first passed over: the same kernel with four times
+  // the list (twice, for reads over 160 bases), a few waves per CU -- most launches find a few thousand ends; what THAT leaves goes
+  // to pm_seed_kernel (launch_rest)
+  PmLists L2 = L;
+  L2.big_list = L.big_list + d->lists_cap;
+  L2.n_big = &cc->n_big2;
+  L2.next_end = &cc->next_end2;
+  const int grid2 = d->kn.tier2_waves * d->n_cus;
+  with_seg_template (c.L, [&] (auto sm)
+  {
+    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed4_kernel < sm.value, 0 >), dim3 (lgrid), dim3 (64), sizeof (PmSeed4Shared < sm.value, 0 >), st, c.ix, c.b,
+                        c.prm, H, L, (const uint32_t *) nullptr, (const unsigned *) nullptr, lprio);
+    hipEventRecord (ev[1], st);
+    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed4_kernel < sm.value, 1 >), dim3 (grid2), dim3 (64), sizeof (PmSeed4Shared < sm.value, 1 >), st, c.ix, c.b,
+                        c.prm, H, L2, (const uint32_t *) L.big_list, (const unsigned *) L.n_big, lprio);
+  });
+  // the vote is part of the kernel: its interval is empty
+  hipEventRecord (ev[2], st);
+  hipEventRecord (ev[3], st);
 }
 
-// ---- the seed stage after the look-ups, on stream `st`: vote + list-mode remainder on the slot's lists (split), or the
-//      monolithic seed kernel; then the emit kernel (windows, slab numbers, SW task lists).
-// PEMAP_VOTE_REST_ON_ALU=1: with the vote on a stream of its own only its kernel runs there (part 1); the list-mode remainder
-// of the big read-ends and the emit kernel (part 2) go to the ALU stream in front of the chunk's SW, so that the next chunk's
-// vote starts 0.5 ms earlier.  Measured 43.3 ms per step against 41.7 (the vote kernel itself slows down by as much as it
-// gains: 4.95 ms per launch against 4.5), so it is off by default.
-static bool pm_fused (const pemap_dev * d);
-static bool pm_vote_rest_on_alu (const pemap_dev * d)
+// ---- the reference layout's vote kernel on the slot's lists; ev[2]..ev[3] is its own interval
+static void launch_vote (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
 {
-  return d->rest_on_alu;        // set per run (run_slice)
+  PmLists L = d->lists[slot];
+  L.n_big = &cc->n_big;
+  L.positions = &cc->positions;
+  const PmHits & H = slot ? d->hits2 : d->hits;
+  // PEMAP_VOTE_WAVES=n: at most n one-wave workgroups per CU, each striding over the ends.  Default 1024 = one wave per end: the
+  // dispatcher then places vote waves wherever the look-up and SW waves of the other stream leave room (measured 71.6 ms per
+  // step against 74.9 with 12 persistent waves per CU)
+  const int vprio = d->kn.vote_prio;
+  int vgrid = d->kn.vote_waves * d->n_cus;
+  if (vgrid > c.b.n_ends)
+    vgrid = c.b.n_ends;
+  hipLaunchKernelGGL (pm_nop_kernel, dim3 (1), dim3 (1), 0, st);
+  hipEventRecord (ev[2], st);
+  with_seg_template (c.L, [&] (auto sm)
+  {
+    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_vote_wave_kernel < sm.value >), dim3 (vgrid), dim3 (64), 0, st, c.ix, c.b, c.prm, H, L, vprio);
+  });
+  hipEventRecord (ev[3], st);
 }
 
-// part 0: the whole stage; 1: the vote kernel only; 2: what follows it; 3: of that, the list-mode remainder only; 4: the emit kernel only
-static void launch_vote (pemap_dev * d, const RunCtx & c, bool split, int slot, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st, int part = 0)
+// ---- the big-end remainder: pm_seed_kernel over the read-ends the look-up / vote kernels (the fused kernel's second tier) passed
+//      over; then the slot's lists are consumed
+static void launch_rest (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr * cc, hipStream_t st)
 {
-  const bool set2 = split && slot;
-  const PmHits & H = set2 ? d->hits2 : d->hits;
-  uint32_t *tasks_s = set2 ? d->d_tasks_s2 : d->d_tasks_s, *tasks_m = set2 ? d->d_tasks_m2 : d->d_tasks_m;
-  const int n_ends = c.b.n_ends;
-  PmCounters *ctr = &cc->c;
-  const int phase_limit = d->kn.seed_phase;  // timing probe, 0 unless built with -DPEMAP_TIMING_PROBES
-  if (part != 1 && part != 4)
+  // The remainder appends to the chunk's task lists and uses the one spill scratch: a second launch for the same chunk doubles the
+  // appended tasks past the lists' ends (the fault PEMAP_REST_STREAM3=1 produced in round 3).  Refused here, reported by run_slice.
+  const uint64_t id = (d->run_serial << 24) | (uint64_t) (cc - d->d_chunk_ctr);
+  if (d->rest_id[slot] == id)
     {
-      // The remainder appends to the chunk's task lists and uses the one spill scratch: a second launch for the same chunk doubles the
-      // appended tasks past the lists' ends (the fault PEMAP_REST_STREAM3=1 produced in round 3).  Refused here, reported by run_slice.
-      const uint64_t id = (d->run_serial << 24) | (uint64_t) (cc - d->d_chunk_ctr);
-      if (d->rest_id[slot & 1] == id)
-        {
-          d->rest_twice = true;
-          return;
-        }
-      d->rest_id[slot & 1] = id;
+      d->rest_twice = true;
+      return;
     }
-  if (part < 2)
+  d->rest_id[slot] = id;
+  const PmHits & H = slot ? d->hits2 : d->hits;
+  uint32_t *tasks_s = slot ? d->d_tasks_s2 : d->d_tasks_s, *tasks_m = slot ? d->d_tasks_m2 : d->d_tasks_m;
+  const uint32_t *list = d->lists[slot].big_list;
+  const unsigned *n_list = &cc->n_big;
+  if (pm_fused (d))
     {
-      hipLaunchKernelGGL (pm_nop_kernel, dim3 (1), dim3 (1), 0, st);
-      hipEventRecord (ev[2], st);
+      list += d->lists_cap;
+      n_list = &cc->n_big2;
     }
-  if (part == 4)
-    ;
-  else if (split)
-    {
-      PmLists L = d->lists[slot];
-      L.n_big = &cc->n_big;
-      if (pm_fused (d))
-        {
-          // (the fused seed kernel's second tier has taken most of the first tier's list: the monolithic kernel gets what it left)
-          L.big_list += d->lists_cap;
-          L.n_big = &cc->n_big2;
-        }
-      L.positions = &cc->positions;
-      // PEMAP_VOTE_WAVES=n: at most n one-wave workgroups per CU, each striding over the ends.  Default 1024 = one wave per end: the
-      // dispatcher then places vote waves wherever the look-up and SW waves of the other stream leave room (measured 71.6 ms per
-      // step against 74.9 with 12 persistent waves per CU)
-      const int vw = d->kn.vote_waves;
-      const int vprio = d->kn.vote_prio;
-      int vgrid = vw * d->n_cus;
-      if (vgrid > n_ends)
-        vgrid = n_ends;
-#define PM_VT(SM) hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_vote_wave_kernel < SM >), dim3 (vgrid), dim3 (64), 0, st, c.ix, c.b, c.prm, H, L, vprio)
-      // (the grid never exceeds the blocks d_seed_scratch holds a spill area for; the kernel checks it against its capacity too)
-      const int bgrid = d->big_grid < d->scratch_blocks ? d->big_grid : d->scratch_blocks;
-#define PM_SEEDL(SM) hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed_kernel < SM >), dim3 (bgrid), dim3 (PM_SEED_THREADS), 0, st, c.ix, c.b, \
-                                         c.prm, H, tasks_s, tasks_m, ctr, d->d_seed_scratch, d->scratch_blocks, 0, L.big_list, L.n_big)
-      switch (seg_template (c.L))
-        {
-        // ev[2]..ev[3] = the vote kernel alone; the list-mode remainder and the emit kernel end at ev[10]
-        case 7: if (part < 2) { PM_VT (7); hipEventRecord (ev[3], st); } if (part != 1) PM_SEEDL (7); break;
-        case 10: if (part < 2) { PM_VT (10); hipEventRecord (ev[3], st); } if (part != 1) PM_SEEDL (10); break;
-        case 13: if (part < 2) { PM_VT (13); hipEventRecord (ev[3], st); } if (part != 1) PM_SEEDL (13); break;
-        case 16: if (part < 2) { PM_VT (16); hipEventRecord (ev[3], st); } if (part != 1) PM_SEEDL (16); break;
-        default: if (part < 2) { PM_VT (19); hipEventRecord (ev[3], st); } if (part != 1) PM_SEEDL (19); break;
-        }
-#undef PM_VT
-#undef PM_SEEDL
-      if (part != 1)
-        hipEventRecord (d->ev_lists_free[slot], st);    // the slot's lists are consumed
-    }
-  else
-    {
-      int sgrid = d->seed_grid < n_ends ? d->seed_grid : n_ends;
-      if (sgrid > d->scratch_blocks)
-        sgrid = d->scratch_blocks;
-#define PM_SEED(SM) hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed_kernel < SM >), dim3 (sgrid), dim3 (PM_SEED_THREADS), 0, st, c.ix, c.b, c.prm, \
-                                        H, tasks_s, tasks_m, ctr, d->d_seed_scratch, d->scratch_blocks, phase_limit, (const uint32_t *) nullptr, \
-                                        (const unsigned *) nullptr)
-      switch (seg_template (c.L))
-        {
-        case 7: PM_SEED (7); break;
-        case 10: PM_SEED (10); break;
-        case 13: PM_SEED (13); break;
-        case 16: PM_SEED (16); break;
-        default: PM_SEED (19); break;
-        }
-#undef PM_SEED
-    }
-  if (part == 1 || part == 3)
-    return;
-  hipLaunchKernelGGL (pm_emit_kernel, dim3 ((n_ends + 63) / 64), dim3 (64), 0, st, c.ix, c.b, H, tasks_s, tasks_m, ctr);
-  if (!split)
-    hipEventRecord (ev[3], st);
+  with_seg_template (c.L, [&] (auto sm)
+  {
+    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed_kernel < sm.value >), dim3 (d->big_grid), dim3 (PM_SEED_THREADS), 0, st, c.ix, c.b, c.prm, H, tasks_s,
+                        tasks_m, &cc->c, d->d_seed_scratch, d->big_grid, list, n_list);
+  });
+  hipEventRecord (d->ev_lists_free[slot], st);
+}
+
+// ---- the emit kernel (windows, slab numbers, SW task lists); the seed stage ends at ev[10]
+static void launch_emit (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
+{
+  const PmHits & H = slot ? d->hits2 : d->hits;
+  uint32_t *tasks_s = slot ? d->d_tasks_s2 : d->d_tasks_s, *tasks_m = slot ? d->d_tasks_m2 : d->d_tasks_m;
+  hipLaunchKernelGGL (pm_emit_kernel, dim3 ((c.b.n_ends + 63) / 64), dim3 (64), 0, st, c.ix, c.b, H, tasks_s, tasks_m, &cc->c);
   hipEventRecord (ev[10], st);
 }
 
-// ---- the ALU stream's work for one chunk: (the seed stage unless it ran on the memory stream,) SW, selection, traceback.
-template < int W, int LPA > static void launch_chunk (pemap_dev * d, const RunCtx & c, uint32_t * m1, uint32_t * m2, int *mt, bool split, int slot,
-                                             PmChunkCtr * cc, hipEvent_t * ev)
+// ---- the seed stream's work for chunk g (the chunk's rows in c.b)
+static int enqueue_seed (pemap_dev * d, const PmSchedule & s, const RunCtx & c, int g, const hipEvent_t * copy_ev)
 {
-  // the arrays the walk reads alternate between two sets in the split pipeline
+  const int slot = g & 1;
+  PmChunkCtr *cc = d->d_chunk_ctr + g;
+  hipEvent_t *ev = &d->evs[(size_t) g * PM_NEV];
+  if (copy_ev)
+    HIPCHK (d, hipStreamWaitEvent (s.seed, *copy_ev, 0));
+  // the slot's lists must have been consumed by the remainder of chunk g-2
+  if (g >= 2)
+    HIPCHK (d, hipStreamWaitEvent (s.seed, d->ev_lists_free[slot], 0));
+  if (pm_fused (d))
+    {
+      // the fused kernel writes the hit arrays that the SW / walk of chunk g-2 used
+      if (g >= 2 && s.ahead)
+        HIPCHK (d, hipStreamWaitEvent (s.seed, d->ev_walk_done[slot], 0));
+      launch_lookup (d, c, slot, cc, ev, s.seed);
+      // the remainder: 256-thread workgroups with 31 KB of LDS, which find no room beside the next chunk's persistent seed waves --
+      // here, between two seed launches, they do (and mostly find nothing to do)
+      launch_rest (d, c, slot, cc, s.seed);
+      if (!s.emit_on_alu)
+        launch_emit (d, c, slot, cc, ev, s.seed);
+    }
+  else
+    launch_lookup (d, c, slot, cc, ev, s.seed);
+  HIPCHK (d, hipEventRecord (d->ev_lists_ready[slot], s.seed));
+  return 0;
+}
+
+// ---- the ALU stream's work for one chunk: the rest of the seed stage, SW, selection, traceback.
+template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSchedule & s, const RunCtx & c, uint32_t * m1, uint32_t * m2, int *mt,
+                                             int slot, PmChunkCtr * cc, hipEvent_t * ev)
+{
+  // the arrays the walk reads alternate between two sets
   const int swprio = d->kn.sw_prio;
-  const bool set2 = split && slot;
-  const PmHits & H = set2 ? d->hits2 : d->hits;
-  uint32_t *wins = set2 ? d->d_wins2 : d->d_wins;
-  uint32_t *dirbuf = set2 ? d->d_dirbuf2 : d->d_dirbuf;
-  uint32_t *tasks_s = set2 ? d->d_tasks_s2 : d->d_tasks_s, *tasks_m = set2 ? d->d_tasks_m2 : d->d_tasks_m;
+  const PmHits & H = slot ? d->hits2 : d->hits;
+  uint32_t *wins = slot ? d->d_wins2 : d->d_wins;
+  uint32_t *dirbuf = slot ? d->d_dirbuf2 : d->d_dirbuf;
+  uint32_t *tasks_s = slot ? d->d_tasks_s2 : d->d_tasks_s, *tasks_m = slot ? d->d_tasks_m2 : d->d_tasks_m;
   uint32_t *dump_slab = dirbuf + (c.dump_slab - d->d_dirbuf);
   const int n_ends = c.b.n_ends;
   PmCounters *ctr = &cc->c;
-  if (split && pm_fused (d))
+  if (!pm_fused (d))
     {
-      // the seed stage ran on the look-up's stream (enqueue_lookup); PEMAP_VOTE_REST_ON_ALU=1 leaves the big read-ends' remainder
-      // and the emit kernel to this stream
-      if (pm_vote_rest_on_alu (d) && !d->serial_split)
-        launch_vote (d, c, split, slot, cc, ev, d->stream, 4);
+      launch_vote (d, c, slot, cc, ev, d->stream);
+      launch_rest (d, c, slot, cc, d->stream);
+      launch_emit (d, c, slot, cc, ev, d->stream);
     }
-  else if (!(split && d->vote_on_mem))
-    launch_vote (d, c, split, slot, cc, ev, d->stream);
-  else if (d->vote_stream == 3 && pm_vote_rest_on_alu (d))
-    launch_vote (d, c, split, slot, cc, ev, d->stream, 2);
+  else if (s.emit_on_alu)
+    launch_emit (d, c, slot, cc, ev, d->stream);
   if (pm_gapless_on (d))
     {
       uint32_t *tasks_dp = tasks_s + d->cap_ends;
@@ -1387,8 +1349,8 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const RunCt
   // (the walk on the look-up stream, beside the next chunk's vote and SW, was tried: 107 ms per step against 103; it stays on the ALU
   // stream)
   hipStream_t ws = d->stream;
-  unsigned long long *path = set2 ? d->d_path2 : d->d_path;
-  uint16_t *nsteps = set2 ? d->d_nsteps2 : d->d_nsteps;
+  unsigned long long *path = slot ? d->d_path2 : d->d_path;
+  uint16_t *nsteps = slot ? d->d_nsteps2 : d->d_nsteps;
   hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_walk_kernel < W, LPA >), dim3 (wgrid), dim3 (64), 0, ws, c.b, H, wins, ctr, d->d_cur,
                       dirbuf, c.tstride, pile_of (d), d->d_ins_log, d->ins_cap, path, d->path_words, nsteps);
   {
@@ -1400,16 +1362,13 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const RunCt
     hipLaunchKernelGGL (pm_pile_kernel, dim3 (pgrid), dim3 (64), 0, ws, c.b, H, wins, ctr, pile_of (d), path, d->path_words, nsteps);
   }
   hipEventRecord (ev[8], ws);
-  if (split)
-    hipEventRecord (d->ev_walk_done[slot], ws);
+  hipEventRecord (d->ev_walk_done[slot], ws);
 }
 
 // wait for the run in flight and fold its chunks' counters and kernel times into the run's totals
 static int absorb_run (pemap_dev * d)
 {
   HIPCHK (d, hipStreamSynchronize (d->stream2));
-  if (d->stream3)
-    HIPCHK (d, hipStreamSynchronize (d->stream3));
   HIPCHK (d, hipStreamSynchronize (d->stream));
   const int nch = d->run_chunks;
 #ifdef PEMAP_TIMING_PROBES
@@ -1460,7 +1419,7 @@ static int absorb_run (pemap_dev * d)
       d->last_big2 += hc[k].n_big2;
       hipEvent_t *ev = &d->evs[(size_t) k * PM_NEV];
       float ms = 0.f;
-      if (d->run_split && hipEventElapsedTime (&ms, ev[0], ev[1]) == hipSuccess)
+      if (hipEventElapsedTime (&ms, ev[0], ev[1]) == hipSuccess)
         {
           d->last_ms[0] += ms;
           d->last_ms[6] += ms;
@@ -1532,7 +1491,7 @@ static int ensure_pipeline (pemap_dev * d, int chunk_ends)
 }
 
 // chunk size run_slice cuts a run of n pairs of reads up to L bases into
-static int chunk_pairs_for (const pemap_dev * d, int n, int L, bool split)
+static int chunk_pairs_for (const pemap_dev * d, int n, int L)
 {
   const int per = d->paired ? 2 : 1;
   // one direction slab per read-end must fit the budget; the pipeline wants several chunks per run
@@ -1542,7 +1501,7 @@ static int chunk_pairs_for (const pemap_dev * d, int n, int L, bool split)
     max_ends = 20000000;        // task ids are end * 200 + hit in 32 bits
   int chunk = (int) (max_ends / per);
   const int want = d->kn.chunk_pairs;
-  if (split && want > 0 && chunk > want)
+  if (want > 0 && chunk > want)
     chunk = want;
   if (chunk < 1)
     chunk = 1;
@@ -1568,29 +1527,7 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
     return fail (d, "run: reads were staged in %s mode", d->staged_paired ? "paired" : "single");
   const int L = d->max_len_staged;
   const int per = d->paired ? 2 : 1;
-  // PEMAP_PIPELINE: 1 (default) look-up kernel on a second stream beside vote/SW/walk of the previous chunk;
-  // 0 monolithic seed kernel, one stream; 2 split kernels on one stream (diagnostic).
-  const bool split = d->kn.pipeline != 0 && !d->kn.seed_phase;
-  d->serial_split = d->kn.pipeline == 2;
-  // With the fused seed kernel the big read-ends' remainder and the emit kernel run on the ALU stream for
-  // reads of up to 160 bases (where the seed kernel is the longer side: 29.8 ms per step against 31.4), behind the seed kernel for
-  // longer ones (2 x 245: 56.9 ms against 58.6)
-  d->rest_on_alu = pm_fused (d) && seg_template (L) <= 10;
-  // Where the vote runs -- 1: behind its look-ups on the memory stream (the fused kernel's remainder); 2: on a third stream of its own,
-  // beside the SW / walk of the previous chunk and the look-ups of the next; 0: on the ALU stream.
-  // 2 with the look-up replicas (measured 41.5 ms per step against 44.7 with the vote on the ALU stream: with the
-  // cheap look-ups and the gapless rule no stream is saturated any more, and the vote of chunk k+1 fills the gaps), 0 without
-  // (it was slower beside the look-ups of the reference's layout).
-  { const int vm = (split && pm_fused (d)) ? 1 : (d->n_rep == 8 ? 2 : 0);
-    d->vote_on_mem = split && !d->serial_split && vm != 0;
-    d->vote_stream = (d->vote_on_mem && vm == 2) ? 3 : 2; }
-  if (d->vote_on_mem && d->vote_stream == 3 && !d->stream3)
-    {
-      HIPCHK (d, hipStreamCreateWithFlags (&d->stream3, hipStreamNonBlocking));
-      for (int i = 0; i < 2; i++)
-        HIPCHK (d, hipEventCreateWithFlags (&d->ev_lookup_done[i], hipEventDisableTiming));
-    }
-  const int chunk = chunk_pairs_for (d, n, L, split);
+  const int chunk = chunk_pairs_for (d, n, L);
   const int nch = (n + chunk - 1) / chunk;
   // Asynchronous runs queue up behind each other: the chunks of this run continue the pipeline of the pending ones (same
   // slots, same event chain), so that look-ups of this run's first chunk overlap the previous run's last.  The pending runs
@@ -1599,7 +1536,7 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
   if (d->run_pending)
     {
       // (a smaller chunk than the pending runs' fits their arrays: the tail of a batch continues the pipeline too)
-      const bool same = d->run_split == split && d->run_L == L && split && !d->serial_split && chunk * per <= d->cap_ends
+      const bool same = d->kn.pipeline == 1 && d->run_L == L && chunk * per <= d->cap_ends
         && chunk * per <= d->lists_cap && (size_t) (chunk * per) < d->dir_slabs;
       if (same && d->run_chunks + nch <= PM_MAX_CHUNKS)
         k0 = d->run_chunks;
@@ -1609,8 +1546,16 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
           d->run_pending = false;
         }
     }
-  TRY (ensure_work (d, chunk * per, split));
+  TRY (ensure_work (d, chunk * per));
   TRY (ensure_pipeline (d, chunk * per));
+  // PEMAP_PIPELINE=1 (default): the seed stage on stream2, two chunks ahead of the ALU stream; 2: everything on the ALU stream.
+  // The reference layout's vote runs on the ALU stream (it was slower beside its look-ups).  The fused layout's emit kernel
+  // runs on the ALU stream for reads of up to 160 bases (where the seed kernel is the longer side: 29.8 ms per step against
+  // 31.4), behind the seed kernel for longer ones (2 x 245: 56.9 ms against 58.6).
+  PmSchedule s;
+  s.ahead = d->kn.pipeline == 1;
+  s.seed = s.ahead ? d->stream2 : d->stream;
+  s.emit_on_alu = s.ahead && pm_fused (d) && seg_template (L) <= 10;
   RunCtx c;
   c.ix.pos_index = d->d_pos_index;
   c.ix.mers = d->d_mers;
@@ -1644,12 +1589,11 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
   d->run_n = n;
   d->run_ends += (uint64_t) n * per;
   d->run_chunks = k0 + nch;
-  d->run_split = split;
   d->run_chunk_pairs = chunk;
   d->run_L = L;
-  // fresh per-chunk counters: zeroed on the stream that touches them first (the look-up stream in the split pipeline, so
-  // that a queued run's first look-ups do not wait for the previous run's ALU work)
-  HIPCHK (d, hipMemsetAsync (d->d_chunk_ctr + k0, 0, sizeof (PmChunkCtr) * nch, (split && !d->serial_split) ? d->stream2 : d->stream));
+  // fresh per-chunk counters: zeroed on the stream that touches them first (the seed stream, so that a queued run's first
+  // look-ups do not wait for the previous run's ALU work)
+  HIPCHK (d, hipMemsetAsync (d->d_chunk_ctr + k0, 0, sizeof (PmChunkCtr) * nch, s.seed));
   auto batch_of = [&] (int k, PmBatch & bb, int &f, int &m)
   {
     const int off = k * chunk;
@@ -1664,55 +1608,17 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
     bb.paired = d->paired;
     bb.n_ends = m * per;
   };
-  auto enqueue_lookup = [&] (int k) -> int
+  auto enqueue_seed_k = [&] (int k) -> int
   {
     int f, m;
     RunCtx cl = c;
     batch_of (k, cl.b, f, m);
-    const int g = k0 + k, slot = g & 1;
-    if (copy_evs)
-      HIPCHK (d, hipStreamWaitEvent (d->serial_split ? d->stream : d->stream2, copy_evs[k], 0));
-    // the slot's lists must have been consumed by the vote of chunk g-2
-    if (g >= 2)
-      HIPCHK (d, hipStreamWaitEvent (d->serial_split ? d->stream : d->stream2, d->ev_lists_free[slot], 0));
-    if (pm_fused (d))
-      {
-        // the fused kernel writes the hit arrays that the SW / walk of chunk g-2 used; the list-mode remainder of the big read-ends
-        // and the emit kernel follow it on the same stream
-        hipStream_t fs = d->serial_split ? d->stream : d->stream2;
-        if (g >= 2 && !d->serial_split)
-          HIPCHK (d, hipStreamWaitEvent (fs, d->ev_walk_done[slot], 0));
-        launch_lookup (d, cl, slot, d->d_chunk_ctr + g, &d->evs[(size_t) g * PM_NEV], true);
-        // the monolithic kernel for what both tiers passed over: 256-thread workgroups with 31 KB of LDS, which find no room beside the
-        // next chunk's persistent seed waves -- here, between two seed launches, they do (and mostly find nothing to do).  The emit
-        // kernel goes to the ALU stream in front of the chunk's DP (rest_on_alu), or follows here
-        launch_vote (d, cl, true, slot, d->d_chunk_ctr + g, &d->evs[(size_t) g * PM_NEV], fs, (pm_vote_rest_on_alu (d) && !d->serial_split) ? 3 : 2);
-        HIPCHK (d, hipEventRecord (d->ev_lists_ready[slot], fs));
-        return 0;
-      }
-    launch_lookup (d, cl, slot, d->d_chunk_ctr + g, &d->evs[(size_t) g * PM_NEV], true);
-    if (d->vote_on_mem)
-      {
-        // the vote fills the array set that the SW / walk of chunk g-2 used
-        hipStream_t vs = d->vote_stream == 3 ? d->stream3 : d->stream2;
-        if (vs != d->stream2)
-          {
-            HIPCHK (d, hipEventRecord (d->ev_lookup_done[slot], d->stream2));
-            HIPCHK (d, hipStreamWaitEvent (vs, d->ev_lookup_done[slot], 0));
-          }
-        if (g >= 2)
-          HIPCHK (d, hipStreamWaitEvent (vs, d->ev_walk_done[slot], 0));
-        launch_vote (d, cl, true, slot, d->d_chunk_ctr + g, &d->evs[(size_t) g * PM_NEV], vs, (d->vote_stream == 3 && pm_vote_rest_on_alu (d)) ? 1 : 0);
-        HIPCHK (d, hipEventRecord (d->ev_lists_ready[slot], vs));
-        return 0;
-      }
-    HIPCHK (d, hipEventRecord (d->ev_lists_ready[slot], d->serial_split ? d->stream : d->stream2));
-    return 0;
+    return enqueue_seed (d, s, cl, k0 + k, copy_evs ? &copy_evs[k] : nullptr);
   };
-  // memory stream order: lookup(0), lookup(1), then per chunk k: walk(k), lookup(k+2) -- the look-ups stay one chunk ahead
-  if (split && !d->serial_split)
+  // seed stream order: seed(0), seed(1), then per chunk k: seed(k+2) behind the ALU stream's enqueue of chunk k
+  if (s.ahead)
     for (int k = 0; k < 2 && k < nch; k++)
-      TRY (enqueue_lookup (k));
+      TRY (enqueue_seed_k (k));
   for (int k = 0; k < nch; k++)
     {
       int f, m;
@@ -1720,20 +1626,15 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
       const int g = k0 + k, slot = g & 1;
       PmChunkCtr *cc = d->d_chunk_ctr + g;
       hipEvent_t *ev = &d->evs[(size_t) g * PM_NEV];
-      if (copy_evs && !(split && !d->serial_split))
-        HIPCHK (d, hipStreamWaitEvent (d->stream, copy_evs[k], 0));
-      if (split)
-        {
-          if (d->serial_split)
-            TRY (enqueue_lookup (k));
-          HIPCHK (d, hipStreamWaitEvent (d->stream, d->ev_lists_ready[slot], 0));
-        }
+      if (!s.ahead)
+        TRY (enqueue_seed_k (k));
+      HIPCHK (d, hipStreamWaitEvent (d->stream, d->ev_lists_ready[slot], 0));
       uint32_t *m1 = d->d_m1 + f, *m2 = d->paired ? d->d_m2 + f : nullptr;
       int *mt = d->d_mtype + f;
       {
         int lanes, w;
         pick_geom (d, L, &lanes, &w);
-#define PM_CH(WW, LL) launch_chunk < WW, LL > (d, c, m1, m2, mt, split, slot, cc, ev)
+#define PM_CH(WW, LL) launch_chunk < WW, LL > (d, s, c, m1, m2, mt, slot, cc, ev)
         if (lanes == 8)
           {
             if (w == 13)
@@ -1752,8 +1653,8 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
 #undef PM_CH
       }
       HIPCHK (d, hipGetLastError ());
-      if (split && !d->serial_split && k + 2 < nch)
-        TRY (enqueue_lookup (k + 2));
+      if (s.ahead && k + 2 < nch)
+        TRY (enqueue_seed_k (k + 2));
     }
   if (d->rest_twice)
     return fail (d, "internal: the seed-stage remainder of a chunk was enqueued twice");
@@ -2149,8 +2050,7 @@ extern "C" int pemap_dev_submit_batch (pemap_dev * d, const char *reads1, const 
   if (!d->stream2)
     TRY (ensure_pipeline (d, 0));       // the pipeline's streams must exist before the first copy event is waited on
   // the copies are cut like the kernels' chunks, one event each: chunk k's look-ups start when its rows have landed
-  const bool split = d->kn.pipeline != 0 && !d->kn.seed_phase;
-  const int slice = chunk_pairs_for (d, n, d->max_len_staged, split);
+  const int slice = chunk_pairs_for (d, n, d->max_len_staged);
   const int n_slices = (n + slice - 1) / slice;
   while ((int) r.ev_copy.size () < n_slices)
     {

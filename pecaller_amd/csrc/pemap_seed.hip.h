@@ -2,7 +2,11 @@
 // Included from pemap_kernels.hip.h.
 #pragma once
 
-// One 256-thread workgroup per read-end, persistent over ends.  Template SMAX bounds the number of 16-base segments
+// pm_seed_kernel is the seed stage's big-end remainder: it takes only the read-ends on a big-end list, the ones the look-up /
+// vote kernels of pemap_seed2.hip.h or the fused kernel of pemap_seed4.hip.h passed over (a strand with more positions than
+// their lists hold), and has the global spill path for them.
+//
+// One 256-thread workgroup per read-end, persistent over the list.  Template SMAX bounds the number of 16-base segments
 // and sizes the LDS arrays.
 //
 // Phases per read-end:
@@ -20,13 +24,6 @@
 typedef uint32_t pm_u32x2 __attribute__ ((ext_vector_type (2), aligned (4)));
 #define PM_SEED_TABLE 2048
 #define PM_DIAG_BIAS 300
-// timing probes (kernels cut short after a phase: results are wrong) exist only in builds with -DPEMAP_TIMING_PROBES; the
-// product build compiles them out, whatever a caller passes
-#ifdef PEMAP_TIMING_PROBES
-#define PM_PROBE(x) (x)
-#else
-#define PM_PROBE(x) 0
-#endif
 
 template < int SMAX > struct __align__ (8) PmSeedShared
 {
@@ -94,7 +91,7 @@ __device__ __forceinline__ unsigned pm_bin_hash (uint32_t bin)
 template < class SH, class IdxT >
 __device__ void pm_vote_strand (SH & sh, const uint32_t * ekey, const uint8_t * eseg, uint32_t * bkey, uint8_t * bseg, IdxT * surv, IdxT * order,
                                 uint8_t * tfs, int T, const int *seg_cnt, const int *offsets, int total_cuts, int max_off, int &min_match,
-                                int &tot, bool & go_on, uint8_t strand, int probe = 0)
+                                int &tot, bool & go_on, uint8_t strand)
 {
   constexpr bool LDSP = sizeof (IdxT) == 2;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -151,8 +148,6 @@ __device__ void pm_vote_strand (SH & sh, const uint32_t * ekey, const uint8_t * 
       bseg[pos] = eseg[p];
     }
   pm_barrier < LDSP > ();
-  if (PM_PROBE (probe) == 2)
-    return;
   // ---- tot_found of every anchor the walk can reach: 1 + number of LATER segments holding a position whose diagonal
   //      differs by less than max_off.  An anchor of segment `loop` is only visited while loop <= 1 + max_depth - min_match
   //      (pemapper.c:2216; the bound only shrinks), and only acts if its count reaches min_match (which only grows).
@@ -189,8 +184,6 @@ __device__ void pm_vote_strand (SH & sh, const uint32_t * ekey, const uint8_t * 
         }
     }
   pm_barrier < LDSP > ();
-  if (PM_PROBE (probe) == 3)
-    return;
   const int ns = (int) sh.n_surv;
   // walk order: segment ascending, position ascending inside a segment (same offset, so diagonal ascending)
   for (int sv = tid; sv < ns; sv += PM_SEED_THREADS)
@@ -206,8 +199,6 @@ __device__ void pm_vote_strand (SH & sh, const uint32_t * ekey, const uint8_t * 
       order[rank] = (IdxT) sv;
     }
   pm_barrier < LDSP > ();
-  if (PM_PROBE (probe) == 4)
-    return;
   if (tid < 64)
     {
       bool more = true, done = false;
@@ -517,10 +508,9 @@ __device__ __forceinline__ void pm_seed_stage_a (SH & sh, const PmIndex & ix, co
 template < int SMAX > __global__ __launch_bounds__ (PM_SEED_THREADS, 4) void pm_seed_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h,
                                                                                           uint32_t * tasks_s, uint32_t * tasks_m,
                                                                                           PmCounters * ctr, uint32_t * gscratch, int scratch_blocks,
-                                                                                          int phase_limit,
                                                                                           const uint32_t * end_list, const unsigned *n_list)
 {
-  // end_list != NULL: only the listed read-ends are processed (the ends the split look-up / vote kernels passed over)
+  // only the listed read-ends are processed (the ends the look-up / vote kernels passed over)
   typedef PmSeedShared < SMAX > SH;
   __shared__ SH sh;
   constexpr int NI = (SH::NITEMS + PM_SEED_THREADS - 1) / PM_SEED_THREADS;   // look-ups per thread
@@ -543,17 +533,17 @@ template < int SMAX > __global__ __launch_bounds__ (PM_SEED_THREADS, 4) void pm_
 
   uint32_t v0[NI], v1[NI];
   const uint32_t pos_index_0 = ix.pos_index[0];
-  const int n_iter = end_list ? (int) *n_list : b.n_ends;
+  const int n_iter = (int) *n_list;
   int it = blockIdx.x;
   int buf = 0;
   if (tid < 2)
     sh.ncount[tid] = 0;
   __syncthreads ();
   if (it < n_iter)
-    pm_seed_stage_a < SMAX, NI > (sh, ix, b, prm.bisulfite, end_list ? (int) end_list[it] : it, 0, v0, v1);
+    pm_seed_stage_a < SMAX, NI > (sh, ix, b, prm.bisulfite, (int) end_list[it], 0, v0, v1);
   for (; it < n_iter; it += gridDim.x, buf ^= 1)
     {
-      const int e = end_list ? (int) end_list[it] : it;
+      const int e = (int) end_list[it];
       int len;
       (void) pm_read_ptr (b, e, &len);
       int total_cuts = len / idepth;
@@ -589,7 +579,7 @@ template < int SMAX > __global__ __launch_bounds__ (PM_SEED_THREADS, 4) void pm_
       pm_lds_barrier ();
       int tot = 0;
       int T0 = 0, T1 = 0;
-      if (!skip && PM_PROBE (phase_limit) != 1)
+      if (!skip)
         {
           // ---- a segment with any bucket >= too_many_spots is emptied (pemapper.c:1602-1606)
           if (tid < 2 * S)
@@ -652,8 +642,8 @@ template < int SMAX > __global__ __launch_bounds__ (PM_SEED_THREADS, 4) void pm_
       // ---- stage A of the workgroup's NEXT end: its look-ups fly while this end is voted on
       const int it2 = it + gridDim.x;
       if (it2 < n_iter)
-        pm_seed_stage_a < SMAX, NI > (sh, ix, b, prm.bisulfite, end_list ? (int) end_list[it2] : it2, buf ^ 1, v0, v1);
-      if (!skip && PM_PROBE (phase_limit) != 1 && PM_PROBE (phase_limit) != 2)
+        pm_seed_stage_a < SMAX, NI > (sh, ix, b, prm.bisulfite, (int) end_list[it2], buf ^ 1, v0, v1);
+      if (!skip)
         {
           int min_match = max (1, total_cuts);       // pemapper.c:1642-1645
           if (total_cuts > 4)

@@ -6,8 +6,8 @@
 //   pm_vote_wave_kernel     one WAVE per read-end: lists -> find_matches -> raw hits (pm_emit_kernel makes windows and SW tasks).
 //
 // Read-ends whose strand holds more than PM_SEED_CAP positions (repeats) are appended to a list and handled afterwards
-// by the monolithic pm_seed_kernel (list mode), which has the global spill path.  With the replicas the fused kernel of
-// pemap_seed3.hip.h does both halves in one wave.  (Round 1's and round 2's other forms -- a workgroup per read-end for either
+// by pm_seed_kernel (pemap_seed.hip.h), which has the global spill path.  With the replicas the fused kernel of
+// pemap_seed4.hip.h does both halves in one wave.  (Round 1's and round 2's other forms -- a workgroup per read-end for either
 // half, the look-ups against the replicas as a kernel of their own, plain and software-pipelined -- were measured slower, had no
 // test that selected them and are gone; DESIGN.md section 5 keeps their numbers.)
 #pragma once
@@ -27,7 +27,7 @@ struct PmLists
   PmEndHeader *hdr;                    // [n_ends]
   uint32_t *key;                       // [n_ends][2][PM_SEED_CAP]
   uint8_t *seg;                        // [n_ends][2][PM_SEED_CAP]
-  uint32_t *big_list;                  // ends left to the monolithic kernel
+  uint32_t *big_list;                  // ends left to pm_seed_kernel
   unsigned *n_big;
   unsigned long long *positions;       // P counter
   unsigned *next_end;                  // work counter of the persistent look-up waves (ends beyond the first grid-ful)
@@ -341,7 +341,7 @@ template < int SMAX > __global__ __launch_bounds__ (64) void pm_vote_wave_kernel
       pm_vote_prefetch (nxt, in, e + gridDim.x, b.n_ends, lane);
       const int kind = (int) (__shfl (cur.hw, 21) & 0xFFu);
       if (kind == PM_KIND_BIG)
-        continue;               // left to pm_seed_kernel in list mode
+        continue;               // left to pm_seed_kernel
       int len;
       (void) pm_read_ptr (b, e, &len);
       int total_cuts = len / idepth;

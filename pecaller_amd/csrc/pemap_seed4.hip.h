@@ -24,7 +24,7 @@
 //   vote      no sort.  A table of bins (16 diagonals wide) holds per bin the SET of segments with a position there; a position can
 //             only be an anchor with tot_found >= min_match if the three bins around its diagonal hold min_match - 1 LATER
 //             segments; the positions in or next to a bin with such a candidate are compacted (at most RCAP; more = a repeat, left
-//             to the monolithic kernel) and the exact tot_found (pemapper.c:2241-2249) is an all-pairs test among them; the
+//             to pm_seed_kernel) and the exact tot_found (pemapper.c:2241-2249) is an all-pairs test among them; the
 //             surviving anchors are ranked (segment, position) per strand and the reference's walk (2251-2284) is replayed;
 //   pipeline  three read-ends in flight per wave: the bytes of end k+2 and the table lines of end k+1 travel while end k is decoded
 //             and voted on; ends are handed out through a counter, PM_S4_GRAB at a time.

@@ -348,14 +348,14 @@ def _family_reads(contigs, spots, seed, n, L):
     return refio.pack_reads(r1) + refio.pack_reads(r2)
 
 
-@pytest.mark.parametrize("env", [{}, {"PEMAP_SEED_BLOCKS_PER_CU": "1"}, {"PEMAP_SEED_BLOCKS_PER_CU": "1", "PEMAP_BIG_BLOCKS_PER_CU": "8"},
-                                 {"PEMAP_PIPELINE": "0", "PEMAP_SEED_BLOCKS_PER_CU": "2"}])
+@pytest.mark.parametrize("env", [{}, {"PEMAP_BIG_BLOCKS_PER_CU": "1"}, {"PEMAP_REPLICAS": "0"},
+                                 pytest.param({"PEMAP_REPLICAS": "0", "PEMAP_BIG_BLOCKS_PER_CU": "2"}, id="no_replicas_big_grid_2")])
 def test_big_ends_take_the_spill_path(env, monkeypatch):
-    """Read-ends with more than 1,024 positions on a strand leave the wave-per-end kernels and are seeded by pm_seed_kernel in
-    list mode with its per-block spill area in HBM.  Asserted: such ends occur (stats["big_ends"]), and hits, scores,
-    coordinates, classes, pileup and insertions equal the oracle's.  The grid knobs cover the geometry that faulted in round 1
-    (list-mode grid larger than the grid the spill scratch was sized for: gpurun_out/ab_rep15.log) -- the scratch is now sized
-    for the larger grid and the kernel is told its capacity -- and the monolithic one-stream form of the seed stage."""
+    """Read-ends with more than 1,024 positions on a strand leave the wave-per-end kernels and are seeded by pm_seed_kernel
+    with its per-block spill area in HBM.  Asserted: such ends occur (stats["big_ends"]), and hits, scores, coordinates,
+    classes, pileup and insertions equal the oracle's.  The settings cover both table layouts (the fused seed kernel's and,
+    without replicas, the reference's) and other grids of pm_seed_kernel: round 1 faulted on a grid larger than the one the
+    spill scratch was sized for -- the scratch is now sized for the kernel's own grid and the kernel is told its capacity."""
     from pecaller_amd import PemapDev
     for k, v in env.items():
         monkeypatch.setenv(k, v)           # the knobs are read by pemap_dev_create, once per object
@@ -375,8 +375,7 @@ def test_big_ends_take_the_spill_path(env, monkeypatch):
     dev.close()
     o = oracle_py.Oracle(ix, paired=True, min_dist=0, max_dist=500, min_align=0.85)
     om1, om2, omt, d1, d2 = o.map_batch(b1, l1, b2, l2, debug=True, threads=8)
-    if env.get("PEMAP_PIPELINE") != "0":
-        assert stats["big_ends"] > n // 4, stats        # (the monolithic form has no big-end list: every end is its own)
+    assert stats["big_ends"] > n // 4, stats
     assert np.array_equal(m1, om1), np.nonzero(m1 != om1)[0][:10]
     assert np.array_equal(m2, om2), np.nonzero(m2 != om2)[0][:10]
     assert np.array_equal(mt, omt)

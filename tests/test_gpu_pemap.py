@@ -391,10 +391,11 @@ print("wrap ok")
     assert r.returncode == 0 and b"wrap ok" in r.stdout, r.stdout[-2000:]
 
 
-def test_gapless_rule_counts_and_can_be_switched_off(dev):
+def test_gapless_rule_counts_and_dp_schedules_match_golden(dev):
     """the gapless rule (pm_gapless_kernel) decides most alignments of the golden read set without the DP; its results are
     already pinned by the golden tests above -- here: it is in use, and the full-DP path (PEMAP_GAPLESS=0, a process of
-    its own because the setting is read once) still reproduces the reference's outputs, hit scores included"""
+    its own because the setting is read once) still reproduces the reference's outputs, hit scores included; so do the
+    one-stream schedules (PEMAP_PIPELINE=2) of both table layouts"""
     import os
     import subprocess
     import sys
@@ -432,8 +433,8 @@ print("full dp ok")
     here = os.path.dirname(os.path.abspath(__file__))
     # the full DP in the default pipeline (8 lanes x 19 columns per alignment for 150 bases); the gapless rule without the banded
     # DP behind it (what the rule leaves goes to the full DP, 16 lanes x 10); the two-stream pipeline's kernels on ONE stream; and
-    # the one-stream form with the monolithic seed kernel on the reference's table layout, which shares no launch code with the default
-    for extra in (dict(PEMAP_GAPLESS="0"), dict(PEMAP_BAND="0"), dict(PEMAP_PIPELINE="2"), dict(PEMAP_PIPELINE="0", PEMAP_REPLICAS="0")):
+    # the same on the reference's table layout (the schedule no other test runs)
+    for extra in (dict(PEMAP_GAPLESS="0"), dict(PEMAP_BAND="0"), dict(PEMAP_PIPELINE="2"), dict(PEMAP_PIPELINE="2", PEMAP_REPLICAS="0")):
         env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(here), here]), **extra)
         r = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
         assert r.returncode == 0 and b"full dp ok" in r.stdout, (extra, r.stdout[-2000:])
@@ -474,9 +475,32 @@ print("knob ok")
         dict(PEMAP_SW_PRIO="1", PEMAP_VOTE_PRIO="1", PEMAP_SW_WAVES_PER_CU="3", PEMAP_BAND_WAVES_PER_CU="2", PEMAP_GAPLESS_BLOCKS_PER_CU="3"),
         dict(PEMAP_WALK_BLOCKS_PER_CU="1", PEMAP_PILE_BLOCKS_PER_CU="1"),
         # the table layout of the reference (no replicas): the two-kernel seed stage, its vote on few waves
-        dict(PEMAP_REPLICAS="0", PEMAP_VOTE_WAVES="64", PEMAP_SEED_BLOCKS_PER_CU="2", PEMAP_BIG_BLOCKS_PER_CU="2"),
+        dict(PEMAP_REPLICAS="0", PEMAP_VOTE_WAVES="64", PEMAP_BIG_BLOCKS_PER_CU="2"),
+        # (0 is clamped to one wave per CU: the second tier still runs)
+        dict(PEMAP_TIER2_WAVES="0"),
     ]
     for extra in settings:
         env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(here), here]), **extra)
         r = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
         assert r.returncode == 0 and b"knob ok" in r.stdout, (extra, r.stdout[-2000:])
+
+
+@pytest.mark.gpu
+def test_pipeline_setting_outside_its_range_is_refused():
+    """PEMAP_PIPELINE is 1 or 2; any other value (0 once selected a seed path that is gone) makes pemap_dev_create fail with an
+    error that names the variable, instead of measuring something else.  In a child process, as the knob test does."""
+    import os
+    import subprocess
+    import sys
+    code = r'''
+from pecaller_amd import PemapDev, PemapError
+try:
+    PemapDev(0)
+except PemapError as e:
+    assert "PEMAP_PIPELINE" in str(e), str(e)
+    print("refused ok")
+'''
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(here), here]), PEMAP_PIPELINE="0")
+    r = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    assert r.returncode == 0 and b"refused ok" in r.stdout, r.stdout[-2000:]

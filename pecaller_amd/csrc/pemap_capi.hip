@@ -8,6 +8,7 @@
 #include <stdarg.h>
 #include <unistd.h>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <type_traits>
@@ -27,17 +28,37 @@ struct PmChunkCtr;
 #define PM_RING 3
 struct PmRingSlot
 {
-  bool active;
-  unsigned long long seq;       // ticket of the batch that owns the slot
-  int n, first;
-  uint32_t *m1, *m2;            // the caller's result buffers
-  int *mt;
-  int *h_len;                   // pinned: len1 | len2
-  uint32_t *h_res;              // pinned: m1 | m2 | mapping_type
-  char *h_rows;                 // pinned staging for read rows submitted from pageable memory: reads1 | reads2 (allocated on first need)
-  size_t h_rows_bytes;
-  hipEvent_t ev_done;           // recorded behind the device-to-host copy of the results
+  bool active = false;
+  unsigned long long seq = 0;   // ticket of the batch that owns the slot
+  int n = 0, first = 0;
+  uint32_t *m1 = nullptr, *m2 = nullptr;        // the caller's result buffers
+  int *mt = nullptr;
+  int *h_len = nullptr;         // pinned: len1 | len2
+  uint32_t *h_res = nullptr;    // pinned: m1 | m2 | mapping_type
+  char *h_rows = nullptr;       // pinned staging for read rows submitted from pageable memory: reads1 | reads2 (allocated on first need)
+  size_t h_rows_bytes = 0;
+  hipEvent_t ev_done = nullptr; // recorded behind the device-to-host copy of the results
   std::vector < hipEvent_t > ev_copy;   // one per slice: the slice's rows are on the device
+};
+
+// ---- chunks in flight.  The pipeline keeps PM_SETS chunks in flight (the seed stage of chunk k+1 beside the SW / walk of chunk k),
+// so everything a chunk works on exists PM_SETS times: chunk g of a run, counted over the runs queued behind each other, uses set
+// g % PM_SETS.  All sets have the same sizes (the capacities are members of the object) and are allocated and released together.
+#define PM_SETS 2
+// A third set is this constant plus what the constant does not say: the waits of enqueue_seed on ev_lists_free / ev_walk_done are
+// written for "the chunk PM_SETS back" but were only ever run with two sets, the seed stage would run three chunks ahead of the ALU
+// stream (run_slice), and at the seam a third batch has to be in flight for a third chunk to exist.
+static_assert (PM_SETS == 2, "the wait rules of enqueue_seed and the look-ahead of run_slice are only validated for two sets");
+struct PmChunkSet
+{
+  PmHits hits = {};
+  uint32_t *wins = nullptr, *dirbuf = nullptr;
+  uint32_t *tasks_s = nullptr, *tasks_m = nullptr;      // each in thirds: all problems, those left to the DP, those left to the banded DP
+  unsigned long long *path = nullptr;   // recorded traceback steps per winning alignment
+  uint16_t *nsteps = nullptr;
+  PmLists lists = {};
+  hipEvent_t ev_lists_ready = nullptr, ev_lists_free = nullptr, ev_walk_done = nullptr;
+  uint64_t rest_id = 0;         // run serial and chunk number of the last remainder enqueued on the set (launch_rest)
 };
 
 // Host ranges page-locked through pemap_dev_pin_host.  HIP's registrations are process-wide and keyed by the pointer, so the
@@ -114,77 +135,68 @@ static void read_knobs (PmKnobs & k)
 
 struct pemap_dev
 {
-  int device;
-  PmKnobs kn;
-  hipStream_t stream;
-  char err[512];
+  int device = 0;
+  PmKnobs kn = {};
+  hipStream_t stream = nullptr;
+  char err[512] = "";
   // index
-  uint32_t *d_pos_index, *d_mers;
-  uint32_t *d_rep, *d_multi;    // look-up replicas (pemap_aux.hip.h), built by index_commit
-  uint32_t multi_base;
-  int n_rep, rep_want;          // rep_want: -1 = when the memory is there (default), 0 = never, 8 = required
-  uint64_t multi_units;
-  uint8_t *d_genome, *d_genome_alloc;   // the letters, and the allocation they sit in (padded in front)
-  uint32_t *d_contig_starts;
-  uint64_t n_mers, gsize;
-  int n_contigs, idepth;
-  bool index_ready;
-  uint32_t *d_counts;           // the pileup counter planes (PmPile): 6 planes of pile_plane_words words
-  size_t pile_plane_words;
+  uint32_t *d_pos_index = nullptr, *d_mers = nullptr;
+  uint32_t *d_rep = nullptr, *d_multi = nullptr;        // look-up replicas (pemap_aux.hip.h), built by index_commit
+  uint32_t multi_base = 0;
+  int n_rep = 0, rep_want = -1; // rep_want: -1 = when the memory is there (default), 0 = never, 8 = required
+  uint64_t multi_units = 0;
+  uint8_t *d_genome = nullptr, *d_genome_alloc = nullptr;       // the letters, and the allocation they sit in (padded in front)
+  uint32_t *d_contig_starts = nullptr;
+  uint64_t n_mers = 0, gsize = 0;
+  int n_contigs = 0, idepth = 16;
+  bool index_ready = false;
+  uint32_t *d_counts = nullptr; // the pileup counter planes (PmPile): 6 planes of pile_plane_words words
+  size_t pile_plane_words = 0;
   // each chunk's big-end remainder is enqueued exactly once: checked in launch_rest (the round-3 fault)
-  uint64_t run_serial, rest_id[2];
-  bool rest_twice;
+  uint64_t run_serial = 0;
+  bool rest_twice = false;
   // params
-  int paired, min_dist, max_dist, bisulfite;
-  double min_align;
+  int paired = 1, min_dist = 0, max_dist = 500, bisulfite = 0;
+  double min_align = 0.9;       // MIN_ALIGN default, pemapper.c:151
   // staged reads (capacity cap_reads rows each)
-  uint8_t *d_reads1, *d_reads2;
-  int *d_len1, *d_len2;
-  int cap_reads, n_staged, stride, staged_paired, max_len_staged, min_len_staged;
+  uint8_t *d_reads1 = nullptr, *d_reads2 = nullptr;
+  int *d_len1 = nullptr, *d_len2 = nullptr;
+  int cap_reads = 0, n_staged = 0, stride = 0, staged_paired = 0, max_len_staged = 0, min_len_staged = 0;
   std::vector < int >h_len1, h_len2;
-  // per-run work arrays (capacity cap_ends read-ends)
-  int cap_ends;
-  PmHits hits;
-  uint32_t *d_tasks_s, *d_tasks_m, *d_redo, *d_wins;
-  uint32_t *d_tasks_s2, *d_tasks_m2;      // second set: the vote of the next chunk runs beside the SW of this one
-  // second set of the arrays the walk kernel reads, so that walk(chunk k) can run beside vote/SW(chunk k+1)
-  PmHits hits2;
-  uint32_t *d_wins2, *d_dirbuf2;
-  unsigned long long *d_path, *d_path2;        // recorded traceback steps per winning alignment (two sets)
-  uint16_t *d_nsteps, *d_nsteps2;
-  int path_words, path_cap_ends;
-  hipEvent_t ev_walk_done[2];
-  uint32_t *d_m1, *d_m2;
-  int *d_mtype;
-  int cap_out;
-  PmCounters *d_ctr;
-  PmInsCursor *d_cur;
-  uint32_t *d_seed_scratch;
-  uint32_t *d_dirbuf;
-  size_t dirbuf_dwords;
-  size_t dir_slabs;             // slabs d_dirbuf holds for the staged read length; the last one is the dump slab of task-less lane groups
-  uint8_t *d_ins_log;
-  unsigned ins_cap;
-  int sw_grid;
+  // per-chunk work arrays and events, one set per chunk in flight, and the capacities all sets share
+  PmChunkSet set[PM_SETS];
+  int cap_ends = 0;             // read-ends the hit, winner and task arrays hold
+  size_t dirbuf_dwords = 0;
+  size_t dir_slabs = 0;         // slabs a dirbuf holds for the staged read length; the last one is the dump slab of task-less lane groups
+  int path_words = 0, path_cap_ends = 0;
+  int lists_cap = 0;
+  bool lists_arrays = false;    // the (key, segment) lists exist (not needed, and not allocated, while the fused seed kernel serves)
+  // work arrays of the object: used by one stream at a time
+  uint32_t *d_redo = nullptr;
+  uint32_t *d_m1 = nullptr, *d_m2 = nullptr;
+  int *d_mtype = nullptr;
+  int cap_out = 0;
+  PmCounters *d_ctr = nullptr;
+  PmInsCursor *d_cur = nullptr;
+  uint32_t *d_seed_scratch = nullptr;
+  uint8_t *d_ins_log = nullptr;
+  unsigned ins_cap = 0;
+  int sw_grid = 0;
   // run bookkeeping
-  int run_first, run_n;
-  bool run_pending;             // kernels of the last run still in flight / not yet accounted
-  int run_chunks, run_chunk_pairs, run_L;
-  uint64_t run_ends;
-  hipEvent_t ev[7];
+  int run_first = 0, run_n = 0;
+  bool run_pending = false;     // kernels of the last run still in flight / not yet accounted
+  int run_chunks = 0, run_chunk_pairs = 0, run_L = 0;
+  uint64_t run_ends = 0;
+  hipEvent_t ev[7] = {};
   // two-stream pipeline: the look-up kernel of chunk k+1 (memory stream) runs beside vote/SW/walk of chunk k
-  hipStream_t stream2;
-  int n_cus;
-  hipEvent_t ev_lists_ready[2], ev_lists_free[2];
-  PmLists lists[2];
-  int lists_cap;
-  bool lists_arrays;            // the (key, segment) lists exist (not needed, and not allocated, while the fused seed kernel serves)
-  PmChunkCtr *d_chunk_ctr;
+  hipStream_t stream2 = nullptr;
+  int n_cus = 0;
+  PmChunkCtr *d_chunk_ctr = nullptr;
   std::vector < hipEvent_t > evs;
-  int big_grid;
-  uint64_t last_big, last_big2;  // read-ends the fused seed kernel's first tier passed over; of them, left to pm_seed_kernel
-  PmCounters last_ctr;          // summed over the chunks of the last run
-  PmInsCursor last_cur;
+  int big_grid = 0;
+  uint64_t last_big = 0, last_big2 = 0;  // read-ends the fused seed kernel's first tier passed over; of them, left to pm_seed_kernel
+  PmCounters last_ctr = {};     // summed over the chunks of the last run
+  PmInsCursor last_cur = {};
   // batches in flight
   std::mutex mu;                // guards the enqueue state: submit / wait may be called from several host threads
   // Submitters are serialised for the whole of a submit (taken BEFORE mu).  ring_finish drops mu while the host blocks on the old
@@ -193,12 +205,12 @@ struct pemap_dev
   // Waiters take mu only, so a wait is never held up by a submit that blocks on a full ring.
   std::mutex submit_mu;
   PmRingSlot ring[PM_RING];
-  int ring_cap;                 // rows per slot, 0 = the ring is not set up (the staged arrays hold a resident read set)
-  unsigned long long ring_seq;
-  hipStream_t stream_h2d;
-  float last_ms[8];
+  int ring_cap = 0;             // rows per slot, 0 = the ring is not set up (the staged arrays hold a resident read set)
+  unsigned long long ring_seq = 0;
+  hipStream_t stream_h2d = nullptr;
+  float last_ms[8] = {};
   std::vector < uint8_t > h_ins;        // host copy of all insertion-log bytes so far
-  long summary[13];
+  long summary[13] = {};
 };
 
 static inline PmPile pile_of (const pemap_dev * d)
@@ -230,6 +242,23 @@ template < class T > static int dev_alloc (pemap_dev * d, T ** p, size_t n)
   return 0;
 }
 
+template < class T > static void dev_free (T * &p)
+{
+  hipFree (p);
+  p = nullptr;
+}
+
+// a device temporary of one function: freed when it goes out of scope, on the early returns of TRY / HIPCHK too
+template < class T > struct DevTmp
+{
+  T *p = nullptr;
+  DevTmp () = default;
+  DevTmp (const DevTmp &) = delete;
+  DevTmp & operator= (const DevTmp &) = delete;
+  ~DevTmp () { hipFree (p); }
+  operator T * () const { return p; }
+};
+
 #define TRY(x) do { int r_ = (x); if (r_) return r_; } while (0)
 
 extern "C" const char *pemap_dev_last_error (const pemap_dev * dev)
@@ -245,100 +274,19 @@ extern "C" int pemap_dev_create (pemap_dev ** out, int device_id)
     return fail (nullptr, "no HIP device visible: this library has no CPU path");
   if (device_id < 0 || device_id >= n)
     return fail (nullptr, "device %d out of range (0..%d)", device_id, n - 1);
-  pemap_dev *d = new pemap_dev ();
-  memset (d->err, 0, sizeof (d->err));
+  std::unique_ptr < pemap_dev > d (new pemap_dev ());
   d->device = device_id;
-  d->d_pos_index = d->d_mers = nullptr;
-  d->d_rep = d->d_multi = nullptr;
-  d->multi_base = 0;
-  d->n_rep = 0;
-  d->rep_want = -1;
-  d->multi_units = 0;
-  d->d_genome = d->d_genome_alloc = nullptr;
-  d->d_contig_starts = nullptr;
-  d->d_counts = nullptr;
-  d->n_mers = d->gsize = 0;
-  d->n_contigs = 0;
-  d->idepth = 16;
-  d->index_ready = false;
-  d->paired = 1;
-  d->min_dist = 0;
-  d->max_dist = 500;
-  d->bisulfite = 0;
-  d->min_align = 0.9;           // MIN_ALIGN default, pemapper.c:151
-  d->d_reads1 = d->d_reads2 = nullptr;
-  d->d_len1 = d->d_len2 = nullptr;
-  d->cap_reads = d->n_staged = d->stride = 0;
-  d->staged_paired = 0;
-  d->cap_ends = 0;
-  memset (&d->hits, 0, sizeof (d->hits));
-  memset (&d->hits2, 0, sizeof (d->hits2));
-  d->d_wins2 = d->d_dirbuf2 = nullptr;
-  d->d_path = d->d_path2 = nullptr;
-  d->d_nsteps = d->d_nsteps2 = nullptr;
-  d->path_words = d->path_cap_ends = 0;
-  d->d_tasks_s = d->d_tasks_m = d->d_redo = d->d_wins = d->d_m1 = d->d_m2 = nullptr;
-  d->d_tasks_s2 = d->d_tasks_m2 = nullptr;
-  d->d_cur = nullptr;
-  d->dirbuf_dwords = 0;
-  memset (&d->last_cur, 0, sizeof (d->last_cur));
-  d->d_mtype = nullptr;
-  d->cap_out = 0;
-  d->d_ctr = nullptr;
-  d->d_seed_scratch = nullptr;
-  d->d_dirbuf = nullptr;
-  d->d_ins_log = nullptr;
-  d->ins_cap = 0;
-  d->run_first = d->run_n = 0;
-  d->run_pending = false;
-  d->run_chunks = 0;
-  d->stream2 = nullptr;
-  memset (d->lists, 0, sizeof (d->lists));
-  d->lists_cap = 0;
-  d->lists_arrays = false;
-  d->d_chunk_ctr = nullptr;
-  d->last_big = 0;
-  d->ring_cap = 0;
-  d->ring_seq = 0;
-  d->stream_h2d = nullptr;
-  for (int i = 0; i < PM_RING; i++)
-    {
-      d->ring[i].active = false;
-      d->ring[i].seq = 0;
-      d->ring[i].h_len = nullptr;
-      d->ring[i].h_res = nullptr;
-      d->ring[i].h_rows = nullptr;
-      d->ring[i].h_rows_bytes = 0;
-      d->ring[i].ev_done = nullptr;
-    }
-  memset (&d->last_ctr, 0, sizeof (d->last_ctr));
-  memset (d->last_ms, 0, sizeof (d->last_ms));
-  memset (d->summary, 0, sizeof (d->summary));
   if (hipSetDevice (device_id) != hipSuccess)
-    {
-      delete d;
-      return fail (nullptr, "hipSetDevice(%d) failed", device_id);
-    }
+    return fail (nullptr, "hipSetDevice(%d) failed", device_id);
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties (&prop, device_id) != hipSuccess)
-    {
-      delete d;
-      return fail (nullptr, "hipGetDeviceProperties failed");
-    }
+    return fail (nullptr, "hipGetDeviceProperties failed");
   if (strncmp (prop.gcnArchName, "gfx950", 6) != 0)
-    {
-      fail (nullptr, "device %d is %s: this library is built for gfx950 (MI355X) only", device_id, prop.gcnArchName);
-      delete d;
-      return 1;
-    }
+    return fail (nullptr, "device %d is %s: this library is built for gfx950 (MI355X) only", device_id, prop.gcnArchName);
   int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   read_knobs (d->kn);
   if (d->kn.pipeline != 1 && d->kn.pipeline != 2)
-    {
-      fail (nullptr, "PEMAP_PIPELINE=%d: the settings are 1 (the default) and 2", d->kn.pipeline);
-      delete d;
-      return 1;
-    }
+    return fail (nullptr, "PEMAP_PIPELINE=%d: the settings are 1 (the default) and 2", d->kn.pipeline);
   // pm_seed_kernel is launched with big_grid blocks; every block owns one spill area of d_seed_scratch, which is sized for
   // big_grid blocks and passed to the kernel as its capacity.  (Round 1: the area was sized by another grid, an A/B run
   // raised big_grid above it through an environment knob, and the blocks beyond it wrote past the allocation: the memory
@@ -347,76 +295,91 @@ extern "C" int pemap_dev_create (pemap_dev ** out, int device_id)
   d->big_grid = cus * d->kn.big_blocks_per_cu;
   d->n_cus = cus;
   if (hipStreamCreateWithFlags (&d->stream, hipStreamNonBlocking) != hipSuccess)
-    {
-      delete d;
-      return fail (nullptr, "hipStreamCreate failed");
-    }
+    return fail (nullptr, "hipStreamCreate failed");
   for (int i = 0; i < 7; i++)
     hipEventCreate (&d->ev[i]);
+  for (PmChunkSet & s : d->set)
+    for (hipEvent_t * e : { &s.ev_lists_ready, &s.ev_lists_free, &s.ev_walk_done })
+      if (hipEventCreateWithFlags (e, hipEventDisableTiming) != hipSuccess)
+        return fail (nullptr, "hipEventCreate failed");
   if (hipMalloc ((void **) &d->d_ctr, sizeof (PmCounters)) != hipSuccess || hipMalloc ((void **) &d->d_cur, sizeof (PmInsCursor)) != hipSuccess)
-    {
-      delete d;
-      return fail (nullptr, "hipMalloc failed");
-    }
+    return fail (nullptr, "hipMalloc failed");
   hipMemset (d->d_ctr, 0, sizeof (PmCounters));
   hipMemset (d->d_cur, 0, sizeof (PmInsCursor));
-  *out = d;
+  *out = d.release ();
   return 0;
 }
 
 static void free_index (pemap_dev * d)
 {
-  hipFree (d->d_pos_index);
-  hipFree (d->d_mers);
-  hipFree (d->d_multi);         // d_rep is kept for the next index (pemap_dev_destroy frees it)
-  d->d_multi = nullptr;
+  dev_free (d->d_pos_index);
+  dev_free (d->d_mers);
+  dev_free (d->d_multi);        // d_rep is kept for the next index (pemap_dev_destroy frees it)
   d->n_rep = 0;
-  hipFree (d->d_genome_alloc);
-  d->d_genome_alloc = nullptr;
-  hipFree (d->d_contig_starts);
-  hipFree (d->d_counts);
-  d->d_pos_index = d->d_mers = nullptr;
+  dev_free (d->d_genome_alloc);
   d->d_genome = nullptr;
-  d->d_contig_starts = nullptr;
-  d->d_counts = nullptr;
+  dev_free (d->d_contig_starts);
+  dev_free (d->d_counts);
   d->index_ready = false;
 }
 
+// ---- the chunk sets' arrays, in four groups by what sizes them: the read-ends of a chunk (free_work), the direction slabs, the path
+// words, the lists.  A group is released here and allocated in ensure_work / ensure_pipeline, always for every set.
 static void free_hits (PmHits & h)
 {
-  hipFree (h.n_hits);
-  hipFree (h.spot);
-  hipFree (h.gpos);
-  hipFree (h.nn);
-  hipFree (h.orient);
-  hipFree (h.score);
-  hipFree (h.sti);
-  hipFree (h.stk);
-  hipFree (h.slot);
-  memset (&h, 0, sizeof (h));
+  dev_free (h.n_hits);
+  dev_free (h.spot);
+  dev_free (h.gpos);
+  dev_free (h.nn);
+  dev_free (h.orient);
+  dev_free (h.score);
+  dev_free (h.sti);
+  dev_free (h.stk);
+  dev_free (h.slot);
+}
+
+static void free_paths (pemap_dev * d)
+{
+  for (PmChunkSet & s : d->set)
+    {
+      dev_free (s.path);
+      dev_free (s.nsteps);
+    }
+  d->path_words = d->path_cap_ends = 0;
+}
+
+static void free_dirs (pemap_dev * d)
+{
+  for (PmChunkSet & s : d->set)
+    dev_free (s.dirbuf);
+  d->dirbuf_dwords = 0;
+}
+
+static void free_lists (pemap_dev * d)
+{
+  for (PmChunkSet & s : d->set)
+    {
+      dev_free (s.lists.hdr);
+      dev_free (s.lists.key);
+      dev_free (s.lists.seg);
+      dev_free (s.lists.big_list);
+    }
+  d->lists_cap = 0;
+  d->lists_arrays = false;
 }
 
 static void free_work (pemap_dev * d)
 {
-  free_hits (d->hits);
-  free_hits (d->hits2);
-  hipFree (d->d_tasks_s);
-  hipFree (d->d_tasks_m);
-  hipFree (d->d_tasks_s2);
-  hipFree (d->d_tasks_m2);
-  d->d_tasks_s2 = d->d_tasks_m2 = nullptr;
-  hipFree (d->d_redo);
-  hipFree (d->d_wins);
-  hipFree (d->d_wins2);
-  hipFree (d->d_path);
-  hipFree (d->d_path2);
-  hipFree (d->d_nsteps);
-  hipFree (d->d_nsteps2);
-  d->d_path = d->d_path2 = nullptr;
-  d->d_nsteps = d->d_nsteps2 = nullptr;
-  d->path_words = d->path_cap_ends = 0;
-  d->d_tasks_s = d->d_tasks_m = d->d_redo = d->d_wins = d->d_wins2 = nullptr;
+  for (PmChunkSet & s : d->set)
+    {
+      free_hits (s.hits);
+      dev_free (s.wins);
+      dev_free (s.tasks_s);
+      dev_free (s.tasks_m);
+    }
+  dev_free (d->d_redo);
   d->cap_ends = 0;
+  free_paths (d);
 }
 
 extern "C" void pemap_dev_destroy (pemap_dev * d)
@@ -425,10 +388,17 @@ extern "C" void pemap_dev_destroy (pemap_dev * d)
     return;
   hipSetDevice (d->device);
   hipStreamSynchronize (d->stream);
+  if (d->stream2)
+    hipStreamSynchronize (d->stream2);
   free_index (d);
   hipFree (d->d_rep);
-  d->d_rep = nullptr;
   free_work (d);
+  free_dirs (d);
+  free_lists (d);
+  for (PmChunkSet & s : d->set)
+    for (hipEvent_t e : { s.ev_lists_ready, s.ev_lists_free, s.ev_walk_done })
+      if (e)
+        hipEventDestroy (e);
   hipFree (d->d_reads1);
   hipFree (d->d_reads2);
   hipFree (d->d_len1);
@@ -439,8 +409,6 @@ extern "C" void pemap_dev_destroy (pemap_dev * d)
   hipFree (d->d_ctr);
   hipFree (d->d_cur);
   hipFree (d->d_seed_scratch);
-  hipFree (d->d_dirbuf);
-  hipFree (d->d_dirbuf2);
   hipFree (d->d_ins_log);
   for (int i = 0; i < PM_RING; i++)
     {
@@ -456,29 +424,14 @@ extern "C" void pemap_dev_destroy (pemap_dev * d)
         hipEventDestroy (d->ring[i].ev_copy[k]);
     }
   if (d->stream_h2d)
-    {
-      hipStreamDestroy (d->stream_h2d);
-    }
+    hipStreamDestroy (d->stream_h2d);
   for (int i = 0; i < 7; i++)
     hipEventDestroy (d->ev[i]);
+  for (size_t i = 0; i < d->evs.size (); i++)
+    hipEventDestroy (d->evs[i]);
+  hipFree (d->d_chunk_ctr);
   if (d->stream2)
-    {
-      hipStreamSynchronize (d->stream2);
-      for (int i = 0; i < 2; i++)
-        {
-          hipEventDestroy (d->ev_lists_ready[i]);
-          hipEventDestroy (d->ev_lists_free[i]);
-          hipEventDestroy (d->ev_walk_done[i]);
-          hipFree (d->lists[i].hdr);
-          hipFree (d->lists[i].key);
-          hipFree (d->lists[i].seg);
-          hipFree (d->lists[i].big_list);
-        }
-      for (size_t i = 0; i < d->evs.size (); i++)
-        hipEventDestroy (d->evs[i]);
-      hipFree (d->d_chunk_ctr);
-      hipStreamDestroy (d->stream2);
-    }
+    hipStreamDestroy (d->stream2);
   hipStreamDestroy (d->stream);
   delete d;
 }
@@ -521,16 +474,14 @@ extern "C" int pemap_dev_index_alloc (pemap_dev * d, uint64_t n_mers, uint64_t g
 // The 8 look-up replicas and the records of the multi-position buckets (pemap_aux.hip.h), from pos_index / mers.
 static int build_replicas (pemap_dev * d)
 {
-  hipFree (d->d_multi);
-  d->d_multi = nullptr;
+  dev_free (d->d_multi);
   d->n_rep = 0;
   int want = d->rep_want;
   if (want < 0 && d->kn.replicas >= 0)
     want = d->kn.replicas ? 8 : 0;
   if (want == 0)
     {
-      hipFree (d->d_rep);
-      d->d_rep = nullptr;
+      dev_free (d->d_rep);
       return 0;
     }
   const size_t rep_bytes = 8ull * (1ull << 32) * sizeof (uint32_t);
@@ -597,10 +548,10 @@ static int build_replicas (pemap_dev * d)
   const unsigned grid = (unsigned) d->n_cus * 64u;
   hipLaunchKernelGGL (ix_rep_units_kernel, dim3 (grid), dim3 (256), 0, d->stream, d->d_pos_index, units);
   const uint64_t sc_tiles = (n + SC_TILE - 1) / SC_TILE;
-  uint32_t *d_tsum = nullptr;
-  unsigned long long *d_total = nullptr;
-  TRY (dev_alloc (d, &d_tsum, sc_tiles));
-  TRY (dev_alloc (d, &d_total, 1));
+  DevTmp < unsigned long long > d_total;
+  DevTmp < uint32_t > d_tsum;
+  TRY (dev_alloc (d, &d_tsum.p, sc_tiles));
+  TRY (dev_alloc (d, &d_total.p, 1));
   hipLaunchKernelGGL (ix_sumscan_reduce_kernel, dim3 ((unsigned) sc_tiles), dim3 (SC_BLOCK), 0, d->stream, units, n, d_tsum);
   hipLaunchKernelGGL (ix_sumscan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d_tsum, sc_tiles, d_total);
   unsigned long long total = 0;
@@ -612,12 +563,7 @@ static int build_replicas (pemap_dev * d)
   if (fits)
     {
       hipLaunchKernelGGL (ix_sumscan_apply_kernel, dim3 ((unsigned) sc_tiles), dim3 (SC_BLOCK), 0, d->stream, units, n, d_tsum);
-      if (dev_alloc (d, &d->d_multi, (size_t) total * 4 + 64))
-        {
-          hipFree (d_tsum);
-          hipFree (d_total);
-          return 1;
-        }
+      TRY (dev_alloc (d, &d->d_multi, (size_t) total * 4 + 64));
       hipLaunchKernelGGL (ix_rep_encode_kernel, dim3 (grid), dim3 (256), 0, d->stream, d->d_pos_index, d->d_mers, units, d->multi_base, d->d_rep,
                           d->d_multi);
       for (int p = 1; p < 8; p++)
@@ -626,8 +572,6 @@ static int build_replicas (pemap_dev * d)
     }
   HIPCHK (d, hipStreamSynchronize (d->stream));
   HIPCHK (d, hipGetLastError ());
-  hipFree (d_tsum);
-  hipFree (d_total);
   if (!fits)
     {
       if (want == 8)
@@ -702,60 +646,50 @@ static int build_from_device_genome (pemap_dev * d, const uint32_t * contig_len,
     return fail (d, "build_index: contig lengths sum to %llu, genome has %llu letters", (unsigned long long) real_starts[n_contigs],
                  (unsigned long long) gsize);
   HIPCHK (d, hipMemcpy (d->d_contig_starts, cstarts.data (), (n_contigs + 1) * sizeof (uint32_t), hipMemcpyHostToDevice));
-  uint64_t *d_real = nullptr;
-  TRY (dev_alloc (d, &d_real, (size_t) n_contigs + 1));
-  HIPCHK (d, hipMemcpy (d_real, real_starts.data (), (n_contigs + 1) * sizeof (uint64_t), hipMemcpyHostToDevice));
-  const uint64_t n_tiles = (gsize + IX_PER_BLOCK - 1) / IX_PER_BLOCK;
-  uint32_t *d_tc = nullptr;
-  uint64_t *d_to = nullptr, *d_total = nullptr;
-  TRY (dev_alloc (d, &d_tc, n_tiles));
-  TRY (dev_alloc (d, &d_to, n_tiles));
-  TRY (dev_alloc (d, &d_total, 1));
-  hipLaunchKernelGGL (ix_count_kernel, dim3 ((unsigned) n_tiles), dim3 (IX_BLOCK), 0, d->stream, d->d_genome, d_real, n_contigs, gsize,
-                      bisulfite, d_tc);
-  hipLaunchKernelGGL (ix_scan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d_tc, d_to, n_tiles, d_total);
-  uint64_t n_mers = 0;
-  HIPCHK (d, hipMemcpyAsync (&n_mers, d_total, sizeof (uint64_t), hipMemcpyDeviceToHost, d->stream));
-  HIPCHK (d, hipStreamSynchronize (d->stream));
-  if (n_mers == 0)
-    return fail (d, "build_index: the genome has no 16-mer free of N");
-  uint32_t *d_keys = nullptr, *d_vals = nullptr, *d_keys2 = nullptr;
-  TRY (dev_alloc (d, &d_keys, n_mers));
-  TRY (dev_alloc (d, &d_vals, n_mers));
-  TRY (dev_alloc (d, &d_keys2, n_mers));
-  hipFree (d->d_mers);
-  d->d_mers = nullptr;
-  TRY (dev_alloc (d, &d->d_mers, n_mers + 128));
-  d->n_mers = n_mers;
-  hipLaunchKernelGGL (ix_emit_kernel, dim3 ((unsigned) n_tiles), dim3 (IX_BLOCK), 0, d->stream, d->d_genome, d_real, n_contigs, gsize,
-                      bisulfite, d_to, d_keys, d_vals);
-  // stable LSD radix sort by k-mer: equal k-mers keep genome order, which is the .mdx order
-  size_t tmp_bytes = 0;
-  HIPCHK (d, rocprim::radix_sort_pairs (nullptr, tmp_bytes, d_keys, d_keys2, d_vals, d->d_mers, (size_t) n_mers, 0, 32, d->stream));
-  void *d_tmp = nullptr;
-  HIPCHK (d, hipMalloc (&d_tmp, tmp_bytes ? tmp_bytes : 1));
-  HIPCHK (d, rocprim::radix_sort_pairs (d_tmp, tmp_bytes, d_keys, d_keys2, d_vals, d->d_mers, (size_t) n_mers, 0, 32, d->stream));
-  // prefix table: bucket ends scattered, then a running maximum over 2^32 + 1 entries
-  HIPCHK (d, hipMemsetAsync (d->d_pos_index, 0, POS_INDEX_N * sizeof (uint32_t), d->stream));
-  hipLaunchKernelGGL (ix_run_ends_kernel, dim3 ((unsigned) ((n_mers + 255) / 256)), dim3 (256), 0, d->stream, d_keys2, n_mers,
-                      d->d_pos_index);
-  const uint64_t sc_tiles = (POS_INDEX_N + SC_TILE - 1) / SC_TILE;
-  uint32_t *d_tmax = nullptr;
-  TRY (dev_alloc (d, &d_tmax, sc_tiles));
-  hipLaunchKernelGGL (ix_maxscan_reduce_kernel, dim3 ((unsigned) sc_tiles), dim3 (SC_BLOCK), 0, d->stream, d->d_pos_index, POS_INDEX_N, d_tmax);
-  hipLaunchKernelGGL (ix_maxscan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d_tmax, sc_tiles);
-  hipLaunchKernelGGL (ix_maxscan_apply_kernel, dim3 ((unsigned) sc_tiles), dim3 (SC_BLOCK), 0, d->stream, d->d_pos_index, POS_INDEX_N, d_tmax);
-  HIPCHK (d, hipStreamSynchronize (d->stream));
-  HIPCHK (d, hipGetLastError ());
-  hipFree (d_tmp);
-  hipFree (d_tmax);
-  hipFree (d_keys);
-  hipFree (d_keys2);
-  hipFree (d_vals);
-  hipFree (d_tc);
-  hipFree (d_to);
-  hipFree (d_total);
-  hipFree (d_real);
+  {
+    // the temporaries (some 3 x n_mers words) are released, last one first, before the replicas are built
+    DevTmp < uint64_t > d_real, d_total, d_to;
+    DevTmp < uint32_t > d_tc, d_vals, d_keys2, d_keys, d_tmax;
+    DevTmp < void > d_tmp;
+    TRY (dev_alloc (d, &d_real.p, (size_t) n_contigs + 1));
+    HIPCHK (d, hipMemcpy (d_real, real_starts.data (), (n_contigs + 1) * sizeof (uint64_t), hipMemcpyHostToDevice));
+    const uint64_t n_tiles = (gsize + IX_PER_BLOCK - 1) / IX_PER_BLOCK;
+    TRY (dev_alloc (d, &d_tc.p, n_tiles));
+    TRY (dev_alloc (d, &d_to.p, n_tiles));
+    TRY (dev_alloc (d, &d_total.p, 1));
+    hipLaunchKernelGGL (ix_count_kernel, dim3 ((unsigned) n_tiles), dim3 (IX_BLOCK), 0, d->stream, d->d_genome, d_real, n_contigs, gsize,
+                        bisulfite, d_tc);
+    hipLaunchKernelGGL (ix_scan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d_tc, d_to, n_tiles, d_total);
+    uint64_t n_mers = 0;
+    HIPCHK (d, hipMemcpyAsync (&n_mers, d_total, sizeof (uint64_t), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK (d, hipStreamSynchronize (d->stream));
+    if (n_mers == 0)
+      return fail (d, "build_index: the genome has no 16-mer free of N");
+    TRY (dev_alloc (d, &d_keys.p, n_mers));
+    TRY (dev_alloc (d, &d_vals.p, n_mers));
+    TRY (dev_alloc (d, &d_keys2.p, n_mers));
+    dev_free (d->d_mers);
+    TRY (dev_alloc (d, &d->d_mers, n_mers + 128));
+    d->n_mers = n_mers;
+    hipLaunchKernelGGL (ix_emit_kernel, dim3 ((unsigned) n_tiles), dim3 (IX_BLOCK), 0, d->stream, d->d_genome, d_real, n_contigs, gsize,
+                        bisulfite, d_to, d_keys, d_vals);
+    // stable LSD radix sort by k-mer: equal k-mers keep genome order, which is the .mdx order
+    size_t tmp_bytes = 0;
+    HIPCHK (d, rocprim::radix_sort_pairs (nullptr, tmp_bytes, d_keys.p, d_keys2.p, d_vals.p, d->d_mers, (size_t) n_mers, 0, 32, d->stream));
+    HIPCHK (d, hipMalloc (&d_tmp.p, tmp_bytes ? tmp_bytes : 1));
+    HIPCHK (d, rocprim::radix_sort_pairs (d_tmp.p, tmp_bytes, d_keys.p, d_keys2.p, d_vals.p, d->d_mers, (size_t) n_mers, 0, 32, d->stream));
+    // prefix table: bucket ends scattered, then a running maximum over 2^32 + 1 entries
+    HIPCHK (d, hipMemsetAsync (d->d_pos_index, 0, POS_INDEX_N * sizeof (uint32_t), d->stream));
+    hipLaunchKernelGGL (ix_run_ends_kernel, dim3 ((unsigned) ((n_mers + 255) / 256)), dim3 (256), 0, d->stream, d_keys2, n_mers,
+                        d->d_pos_index);
+    const uint64_t sc_tiles = (POS_INDEX_N + SC_TILE - 1) / SC_TILE;
+    TRY (dev_alloc (d, &d_tmax.p, sc_tiles));
+    hipLaunchKernelGGL (ix_maxscan_reduce_kernel, dim3 ((unsigned) sc_tiles), dim3 (SC_BLOCK), 0, d->stream, d->d_pos_index, POS_INDEX_N, d_tmax);
+    hipLaunchKernelGGL (ix_maxscan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d_tmax, sc_tiles);
+    hipLaunchKernelGGL (ix_maxscan_apply_kernel, dim3 ((unsigned) sc_tiles), dim3 (SC_BLOCK), 0, d->stream, d->d_pos_index, POS_INDEX_N, d_tmax);
+    HIPCHK (d, hipStreamSynchronize (d->stream));
+    HIPCHK (d, hipGetLastError ());
+  }
   return pemap_dev_index_commit (d);
 }
 
@@ -924,51 +858,43 @@ static int alloc_hits (pemap_dev * d, PmHits & h, int n_ends)
 
 static int ensure_work (pemap_dev * d, int n_ends)
 {
-  if (n_ends > d->cap_ends || !d->hits2.n_hits)
+  if (n_ends > d->cap_ends)
     {
       free_work (d);
-      size_t nh = (size_t) n_ends * PM_MAX_HITS;
-      TRY (alloc_hits (d, d->hits, n_ends));
-      TRY (dev_alloc (d, &d->d_wins, (size_t) n_ends));
-      TRY (alloc_hits (d, d->hits2, n_ends));
-      TRY (dev_alloc (d, &d->d_wins2, (size_t) n_ends));
-      TRY (dev_alloc (d, &d->d_tasks_s2, (size_t) n_ends * 3));       // second third: the problems left to the DP, last third: to the banded DP
-      TRY (dev_alloc (d, &d->d_tasks_m2, nh * 3));
-      TRY (dev_alloc (d, &d->d_tasks_s, (size_t) n_ends * 3));
-      TRY (dev_alloc (d, &d->d_tasks_m, nh * 3));
+      const size_t nh = (size_t) n_ends * PM_MAX_HITS;
+      for (PmChunkSet & s : d->set)
+        {
+          TRY (alloc_hits (d, s.hits, n_ends));
+          TRY (dev_alloc (d, &s.wins, (size_t) n_ends));
+          TRY (dev_alloc (d, &s.tasks_s, (size_t) n_ends * 3));       // second third: the problems left to the DP, last third: to the banded DP
+          TRY (dev_alloc (d, &s.tasks_m, nh * 3));
+        }
       TRY (dev_alloc (d, &d->d_redo, (size_t) n_ends));
       d->cap_ends = n_ends;
     }
   if (!d->d_seed_scratch)
     TRY (dev_alloc (d, &d->d_seed_scratch, (size_t) d->big_grid * 6 * PM_MAX_SEG * PM_SEG_LIST_MAX));
-  size_t need = ((size_t) n_ends + 1) * slab_dwords_for (d, d->max_len_staged);       // + 1: dump slab for task-less lane groups
-  if (need > d->dirbuf_dwords || !d->d_dirbuf2)
+  const size_t need = ((size_t) n_ends + 1) * slab_dwords_for (d, d->max_len_staged); // + 1: dump slab for task-less lane groups
+  if (need > d->dirbuf_dwords)
     {
-      hipFree (d->d_dirbuf);
-      hipFree (d->d_dirbuf2);
-      d->d_dirbuf = d->d_dirbuf2 = nullptr;
-      d->dirbuf_dwords = 0;
-      TRY (dev_alloc (d, &d->d_dirbuf, need));
-      TRY (dev_alloc (d, &d->d_dirbuf2, need));
+      free_dirs (d);
+      for (PmChunkSet & s : d->set)
+        TRY (dev_alloc (d, &s.dirbuf, need));
       d->dirbuf_dwords = need;
     }
   d->dir_slabs = d->dirbuf_dwords / slab_dwords_for (d, d->max_len_staged);
   // recorded traceback steps: PM_PATH_WORDS words of 32 two-bit steps per read-end
   const int pwords = PM_PATH_WORDS (d->max_len_staged);
-  if (!d->d_path || n_ends > d->path_cap_ends || pwords != d->path_words || !d->d_path2)
+  if (n_ends > d->path_cap_ends || pwords != d->path_words)
     {
-      hipFree (d->d_path);
-      hipFree (d->d_path2);
-      hipFree (d->d_nsteps);
-      hipFree (d->d_nsteps2);
-      d->d_path = d->d_path2 = nullptr;
-      d->d_nsteps = d->d_nsteps2 = nullptr;
+      free_paths (d);
+      for (PmChunkSet & s : d->set)
+        {
+          TRY (dev_alloc (d, &s.path, (size_t) n_ends * pwords));
+          TRY (dev_alloc (d, &s.nsteps, (size_t) n_ends));
+        }
       d->path_words = pwords;
       d->path_cap_ends = n_ends;
-      TRY (dev_alloc (d, &d->d_path, (size_t) n_ends * pwords));
-      TRY (dev_alloc (d, &d->d_nsteps, (size_t) n_ends));
-      TRY (dev_alloc (d, &d->d_path2, (size_t) n_ends * pwords));
-      TRY (dev_alloc (d, &d->d_nsteps2, (size_t) n_ends));
     }
   // insertion log: 64 bytes per read-end of a chunk is ample for real data, and at least 512 MB so that runs queued back to
   // back (the log is drained when a run is absorbed) do not fill it; overflow is reported as an error
@@ -1047,7 +973,7 @@ struct RunCtx
   PmBatch b;
   PmParams prm;
   int tstride, L;
-  uint32_t *dump_slab;
+  size_t dump_off;              // dwords from the start of a set's dirbuf to its dump slab
 };
 
 // per-chunk device counters: the kernels' PmCounters plus what the look-up kernel counts
@@ -1097,14 +1023,14 @@ static bool pm_fused (const pemap_dev * d)
 struct PmSchedule
 {
   hipStream_t seed;             // the seed stage's stream: stream2, or the ALU stream with PEMAP_PIPELINE=2
-  bool ahead;                   // the seed stage runs two chunks ahead of the ALU stream
+  bool ahead;                   // the seed stage runs PM_SETS chunks ahead of the ALU stream
   bool emit_on_alu;             // the fused layout's emit kernel goes to the ALU stream in front of the chunk's DP
 };
 
-// ---- the look-ups of one chunk: the fused seed kernel's two tiers, or the reference layout's look-ups into the slot's lists
-static void launch_lookup (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
+// ---- the look-ups of one chunk: the fused seed kernel's two tiers, or the reference layout's look-ups into the set's lists
+static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
 {
-  PmLists L = d->lists[slot];
+  PmLists L = S.lists;
   L.n_big = &cc->n_big;
   L.positions = &cc->positions;
   L.next_end = &cc->next_end;
@@ -1139,7 +1065,7 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr
   if (lgrid > c.b.n_ends)
     lgrid = c.b.n_ends;
   const int lprio = d->kn.lookup_prio;
-  const PmHits & H = slot ? d->hits2 : d->hits;
+  const PmHits & H = S.hits;
   if (!pm_fused (d))
     {
       with_seg_template (c.L, [&] (auto sm)
@@ -1170,13 +1096,13 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr
   hipEventRecord (ev[3], st);
 }
 
-// ---- the reference layout's vote kernel on the slot's lists; ev[2]..ev[3] is its own interval
-static void launch_vote (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
+// ---- the reference layout's vote kernel on the set's lists; ev[2]..ev[3] is its own interval
+static void launch_vote (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
 {
-  PmLists L = d->lists[slot];
+  PmLists L = S.lists;
   L.n_big = &cc->n_big;
   L.positions = &cc->positions;
-  const PmHits & H = slot ? d->hits2 : d->hits;
+  const PmHits & H = S.hits;
   // PEMAP_VOTE_WAVES=n: at most n one-wave workgroups per CU, each striding over the ends.  Default 1024 = one wave per end: the
   // dispatcher then places vote waves wherever the look-up and SW waves of the other stream leave room (measured 71.6 ms per
   // step against 74.9 with 12 persistent waves per CU)
@@ -1194,21 +1120,19 @@ static void launch_vote (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr *
 }
 
 // ---- the big-end remainder: pm_seed_kernel over the read-ends the look-up / vote kernels (the fused kernel's second tier) passed
-//      over; then the slot's lists are consumed
-static void launch_rest (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr * cc, hipStream_t st)
+//      over; then the set's lists are consumed
+static void launch_rest (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChunkCtr * cc, hipStream_t st)
 {
   // The remainder appends to the chunk's task lists and uses the one spill scratch: a second launch for the same chunk doubles the
   // appended tasks past the lists' ends (the fault PEMAP_REST_STREAM3=1 produced in round 3).  Refused here, reported by run_slice.
   const uint64_t id = (d->run_serial << 24) | (uint64_t) (cc - d->d_chunk_ctr);
-  if (d->rest_id[slot] == id)
+  if (S.rest_id == id)
     {
       d->rest_twice = true;
       return;
     }
-  d->rest_id[slot] = id;
-  const PmHits & H = slot ? d->hits2 : d->hits;
-  uint32_t *tasks_s = slot ? d->d_tasks_s2 : d->d_tasks_s, *tasks_m = slot ? d->d_tasks_m2 : d->d_tasks_m;
-  const uint32_t *list = d->lists[slot].big_list;
+  S.rest_id = id;
+  const uint32_t *list = S.lists.big_list;
   const unsigned *n_list = &cc->n_big;
   if (pm_fused (d))
     {
@@ -1217,71 +1141,66 @@ static void launch_rest (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr *
     }
   with_seg_template (c.L, [&] (auto sm)
   {
-    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed_kernel < sm.value >), dim3 (d->big_grid), dim3 (PM_SEED_THREADS), 0, st, c.ix, c.b, c.prm, H, tasks_s,
-                        tasks_m, &cc->c, d->d_seed_scratch, d->big_grid, list, n_list);
+    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed_kernel < sm.value >), dim3 (d->big_grid), dim3 (PM_SEED_THREADS), 0, st, c.ix, c.b, c.prm, S.hits, S.tasks_s,
+                        S.tasks_m, &cc->c, d->d_seed_scratch, d->big_grid, list, n_list);
   });
-  hipEventRecord (d->ev_lists_free[slot], st);
+  hipEventRecord (S.ev_lists_free, st);
 }
 
 // ---- the emit kernel (windows, slab numbers, SW task lists); the seed stage ends at ev[10]
-static void launch_emit (pemap_dev * d, const RunCtx & c, int slot, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
+static void launch_emit (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
 {
-  const PmHits & H = slot ? d->hits2 : d->hits;
-  uint32_t *tasks_s = slot ? d->d_tasks_s2 : d->d_tasks_s, *tasks_m = slot ? d->d_tasks_m2 : d->d_tasks_m;
-  hipLaunchKernelGGL (pm_emit_kernel, dim3 ((c.b.n_ends + 63) / 64), dim3 (64), 0, st, c.ix, c.b, H, tasks_s, tasks_m, &cc->c);
+  hipLaunchKernelGGL (pm_emit_kernel, dim3 ((c.b.n_ends + 63) / 64), dim3 (64), 0, st, c.ix, c.b, S.hits, S.tasks_s, S.tasks_m, &cc->c);
   hipEventRecord (ev[10], st);
 }
 
 // ---- the seed stream's work for chunk g (the chunk's rows in c.b)
 static int enqueue_seed (pemap_dev * d, const PmSchedule & s, const RunCtx & c, int g, const hipEvent_t * copy_ev)
 {
-  const int slot = g & 1;
+  PmChunkSet & S = d->set[g % PM_SETS];
   PmChunkCtr *cc = d->d_chunk_ctr + g;
   hipEvent_t *ev = &d->evs[(size_t) g * PM_NEV];
   if (copy_ev)
     HIPCHK (d, hipStreamWaitEvent (s.seed, *copy_ev, 0));
-  // the slot's lists must have been consumed by the remainder of chunk g-2
-  if (g >= 2)
-    HIPCHK (d, hipStreamWaitEvent (s.seed, d->ev_lists_free[slot], 0));
+  // the set's lists must have been consumed by the remainder of chunk g - PM_SETS
+  if (g >= PM_SETS)
+    HIPCHK (d, hipStreamWaitEvent (s.seed, S.ev_lists_free, 0));
   if (pm_fused (d))
     {
-      // the fused kernel writes the hit arrays that the SW / walk of chunk g-2 used
-      if (g >= 2 && s.ahead)
-        HIPCHK (d, hipStreamWaitEvent (s.seed, d->ev_walk_done[slot], 0));
-      launch_lookup (d, c, slot, cc, ev, s.seed);
+      // the fused kernel writes the hit arrays that the SW / walk of chunk g - PM_SETS used
+      if (g >= PM_SETS && s.ahead)
+        HIPCHK (d, hipStreamWaitEvent (s.seed, S.ev_walk_done, 0));
+      launch_lookup (d, c, S, cc, ev, s.seed);
       // the remainder: 256-thread workgroups with 31 KB of LDS, which find no room beside the next chunk's persistent seed waves --
       // here, between two seed launches, they do (and mostly find nothing to do)
-      launch_rest (d, c, slot, cc, s.seed);
+      launch_rest (d, c, S, cc, s.seed);
       if (!s.emit_on_alu)
-        launch_emit (d, c, slot, cc, ev, s.seed);
+        launch_emit (d, c, S, cc, ev, s.seed);
     }
   else
-    launch_lookup (d, c, slot, cc, ev, s.seed);
-  HIPCHK (d, hipEventRecord (d->ev_lists_ready[slot], s.seed));
+    launch_lookup (d, c, S, cc, ev, s.seed);
+  HIPCHK (d, hipEventRecord (S.ev_lists_ready, s.seed));
   return 0;
 }
 
 // ---- the ALU stream's work for one chunk: the rest of the seed stage, SW, selection, traceback.
 template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSchedule & s, const RunCtx & c, uint32_t * m1, uint32_t * m2, int *mt,
-                                             int slot, PmChunkCtr * cc, hipEvent_t * ev)
+                                             PmChunkSet & S, PmChunkCtr * cc, hipEvent_t * ev)
 {
-  // the arrays the walk reads alternate between two sets
   const int swprio = d->kn.sw_prio;
-  const PmHits & H = slot ? d->hits2 : d->hits;
-  uint32_t *wins = slot ? d->d_wins2 : d->d_wins;
-  uint32_t *dirbuf = slot ? d->d_dirbuf2 : d->d_dirbuf;
-  uint32_t *tasks_s = slot ? d->d_tasks_s2 : d->d_tasks_s, *tasks_m = slot ? d->d_tasks_m2 : d->d_tasks_m;
-  uint32_t *dump_slab = dirbuf + (c.dump_slab - d->d_dirbuf);
+  const PmHits & H = S.hits;
+  uint32_t *wins = S.wins, *dirbuf = S.dirbuf, *tasks_s = S.tasks_s, *tasks_m = S.tasks_m;
+  uint32_t *dump_slab = dirbuf + c.dump_off;
   const int n_ends = c.b.n_ends;
   PmCounters *ctr = &cc->c;
   if (!pm_fused (d))
     {
-      launch_vote (d, c, slot, cc, ev, d->stream);
-      launch_rest (d, c, slot, cc, d->stream);
-      launch_emit (d, c, slot, cc, ev, d->stream);
+      launch_vote (d, c, S, cc, ev, d->stream);
+      launch_rest (d, c, S, cc, d->stream);
+      launch_emit (d, c, S, cc, ev, d->stream);
     }
   else if (s.emit_on_alu)
-    launch_emit (d, c, slot, cc, ev, d->stream);
+    launch_emit (d, c, S, cc, ev, d->stream);
   if (pm_gapless_on (d))
     {
       uint32_t *tasks_dp = tasks_s + d->cap_ends;
@@ -1349,8 +1268,8 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
   // (the walk on the look-up stream, beside the next chunk's vote and SW, was tried: 107 ms per step against 103; it stays on the ALU
   // stream)
   hipStream_t ws = d->stream;
-  unsigned long long *path = slot ? d->d_path2 : d->d_path;
-  uint16_t *nsteps = slot ? d->d_nsteps2 : d->d_nsteps;
+  unsigned long long *path = S.path;
+  uint16_t *nsteps = S.nsteps;
   hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_walk_kernel < W, LPA >), dim3 (wgrid), dim3 (64), 0, ws, c.b, H, wins, ctr, d->d_cur,
                       dirbuf, c.tstride, pile_of (d), d->d_ins_log, d->ins_cap, path, d->path_words, nsteps);
   {
@@ -1362,7 +1281,7 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
     hipLaunchKernelGGL (pm_pile_kernel, dim3 (pgrid), dim3 (64), 0, ws, c.b, H, wins, ctr, pile_of (d), path, d->path_words, nsteps);
   }
   hipEventRecord (ev[8], ws);
-  hipEventRecord (d->ev_walk_done[slot], ws);
+  hipEventRecord (S.ev_walk_done, ws);
 }
 
 // wait for the run in flight and fold its chunks' counters and kernel times into the run's totals
@@ -1445,12 +1364,6 @@ static int ensure_pipeline (pemap_dev * d, int chunk_ends)
     {
       // (a CU mask and stream priorities for the look-up stream were tried in rounds 1 and 2 and gave nothing)
       HIPCHK (d, hipStreamCreateWithFlags (&d->stream2, hipStreamNonBlocking));
-      for (int i = 0; i < 2; i++)
-        {
-          HIPCHK (d, hipEventCreateWithFlags (&d->ev_lists_ready[i], hipEventDisableTiming));
-          HIPCHK (d, hipEventCreateWithFlags (&d->ev_lists_free[i], hipEventDisableTiming));
-          HIPCHK (d, hipEventCreateWithFlags (&d->ev_walk_done[i], hipEventDisableTiming));
-        }
       TRY (dev_alloc (d, &d->d_chunk_ctr, (size_t) PM_MAX_CHUNKS));
       d->evs.resize ((size_t) PM_MAX_CHUNKS * PM_NEV);
       for (size_t i = 0; i < d->evs.size (); i++)
@@ -1466,23 +1379,16 @@ static int ensure_pipeline (pemap_dev * d, int chunk_ends)
           TRY (absorb_run (d));
           d->run_pending = false;
         }
-      for (int i = 0; i < 2; i++)
+      free_lists (d);
+      // (the fused seed kernel keeps the lists in LDS: only the big-end list is needed then)
+      const size_t list_ends = pm_fused (d) ? 0 : (size_t) chunk_ends;
+      for (PmChunkSet & s : d->set)
         {
-          hipFree (d->lists[i].hdr);
-          hipFree (d->lists[i].key);
-          hipFree (d->lists[i].seg);
-          hipFree (d->lists[i].big_list);
-          // (the fused seed kernel keeps the lists in LDS: only the big-end list is needed then)
-          const size_t list_ends = pm_fused (d) ? 0 : (size_t) chunk_ends;
-          d->lists[i].hdr = nullptr;
-          d->lists[i].key = nullptr;
-          d->lists[i].seg = nullptr;
-          d->lists[i].big_list = nullptr;
-          TRY (dev_alloc (d, &d->lists[i].hdr, list_ends));
-          TRY (dev_alloc (d, &d->lists[i].key, list_ends * 2 * PM_SEED_CAP));
-          TRY (dev_alloc (d, &d->lists[i].seg, list_ends * 2 * PM_SEED_CAP));
+          TRY (dev_alloc (d, &s.lists.hdr, list_ends));
+          TRY (dev_alloc (d, &s.lists.key, list_ends * 2 * PM_SEED_CAP));
+          TRY (dev_alloc (d, &s.lists.seg, list_ends * 2 * PM_SEED_CAP));
           // (first half: the ends the fused seed kernel passes over; second half: what its second tier leaves of them)
-          TRY (dev_alloc (d, &d->lists[i].big_list, 2 * (size_t) chunk_ends));
+          TRY (dev_alloc (d, &s.lists.big_list, 2 * (size_t) chunk_ends));
         }
       d->lists_arrays = !pm_fused (d);
       d->lists_cap = chunk_ends;
@@ -1530,7 +1436,7 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
   const int chunk = chunk_pairs_for (d, n, L);
   const int nch = (n + chunk - 1) / chunk;
   // Asynchronous runs queue up behind each other: the chunks of this run continue the pipeline of the pending ones (same
-  // slots, same event chain), so that look-ups of this run's first chunk overlap the previous run's last.  The pending runs
+  // sets, same event chain), so that look-ups of this run's first chunk overlap the previous run's last.  The pending runs
   // are absorbed first only when the per-chunk bookkeeping would overflow or the geometry changes.
   int k0 = 0;
   if (d->run_pending)
@@ -1548,7 +1454,7 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
     }
   TRY (ensure_work (d, chunk * per));
   TRY (ensure_pipeline (d, chunk * per));
-  // PEMAP_PIPELINE=1 (default): the seed stage on stream2, two chunks ahead of the ALU stream; 2: everything on the ALU stream.
+  // PEMAP_PIPELINE=1 (default): the seed stage on stream2, PM_SETS chunks ahead of the ALU stream; 2: everything on the ALU stream.
   // The reference layout's vote runs on the ALU stream (it was slower beside its look-ups).  The fused layout's emit kernel
   // runs on the ALU stream for reads of up to 160 bases (where the seed kernel is the longer side: 29.8 ms per step against
   // 31.4), behind the seed kernel for longer ones (2 x 245: 56.9 ms against 58.6).
@@ -1576,7 +1482,7 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
   c.L = L;
   c.tstride = tstride_for (d, L);
   // (the last slab of the allocation, whatever this run's chunk size: chunks of earlier, larger runs may still be in flight)
-  c.dump_slab = d->d_dirbuf + (d->dir_slabs - 1) * slab_dwords_for (d, L);
+  c.dump_off = (d->dir_slabs - 1) * slab_dwords_for (d, L);
   if (k0 == 0)
     {
       memset (&d->last_ctr, 0, sizeof (d->last_ctr));
@@ -1615,26 +1521,27 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
     batch_of (k, cl.b, f, m);
     return enqueue_seed (d, s, cl, k0 + k, copy_evs ? &copy_evs[k] : nullptr);
   };
-  // seed stream order: seed(0), seed(1), then per chunk k: seed(k+2) behind the ALU stream's enqueue of chunk k
+  // seed stream order: seed(0) .. seed(PM_SETS-1), then per chunk k: seed(k+PM_SETS) behind the ALU stream's enqueue of chunk k
   if (s.ahead)
-    for (int k = 0; k < 2 && k < nch; k++)
+    for (int k = 0; k < PM_SETS && k < nch; k++)
       TRY (enqueue_seed_k (k));
   for (int k = 0; k < nch; k++)
     {
       int f, m;
       batch_of (k, c.b, f, m);
-      const int g = k0 + k, slot = g & 1;
+      const int g = k0 + k;
+      PmChunkSet & S = d->set[g % PM_SETS];
       PmChunkCtr *cc = d->d_chunk_ctr + g;
       hipEvent_t *ev = &d->evs[(size_t) g * PM_NEV];
       if (!s.ahead)
         TRY (enqueue_seed_k (k));
-      HIPCHK (d, hipStreamWaitEvent (d->stream, d->ev_lists_ready[slot], 0));
+      HIPCHK (d, hipStreamWaitEvent (d->stream, S.ev_lists_ready, 0));
       uint32_t *m1 = d->d_m1 + f, *m2 = d->paired ? d->d_m2 + f : nullptr;
       int *mt = d->d_mtype + f;
       {
         int lanes, w;
         pick_geom (d, L, &lanes, &w);
-#define PM_CH(WW, LL) launch_chunk < WW, LL > (d, s, c, m1, m2, mt, slot, cc, ev)
+#define PM_CH(WW, LL) launch_chunk < WW, LL > (d, s, c, m1, m2, mt, S, cc, ev)
         if (lanes == 8)
           {
             if (w == 13)
@@ -1653,8 +1560,8 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
 #undef PM_CH
       }
       HIPCHK (d, hipGetLastError ());
-      if (s.ahead && k + 2 < nch)
-        TRY (enqueue_seed_k (k + 2));
+      if (s.ahead && k + PM_SETS < nch)
+        TRY (enqueue_seed_k (k + PM_SETS));
     }
   if (d->rest_twice)
     return fail (d, "internal: the seed-stage remainder of a chunk was enqueued twice");
@@ -2169,6 +2076,7 @@ extern "C" int pemap_dev_run_stats (pemap_dev * d, uint64_t * s, float *t)
   return 0;
 }
 
+// The hit records of the last run's first chunk (set 0): meaningful for a run of one chunk only.
 extern "C" int pemap_dev_debug_hits (pemap_dev * d, int *n_hits, uint32_t * spot, uint8_t * orient, uint32_t * win_start,
                                      int *win_len, double *score, int *start_k, int *start_i)
 {
@@ -2176,28 +2084,29 @@ extern "C" int pemap_dev_debug_hits (pemap_dev * d, int *n_hits, uint32_t * spot
   HIPCHK (d, hipStreamSynchronize (d->stream));
   const int n_ends = d->paired ? 2 * d->run_n : d->run_n;
   const size_t nh = (size_t) n_ends * PM_MAX_HITS;
+  const PmHits & H = d->set[0].hits;
   if (n_hits)
-    HIPCHK (d, hipMemcpy (n_hits, d->hits.n_hits, (size_t) n_ends * sizeof (int), hipMemcpyDeviceToHost));
+    HIPCHK (d, hipMemcpy (n_hits, H.n_hits, (size_t) n_ends * sizeof (int), hipMemcpyDeviceToHost));
   if (spot)
-    HIPCHK (d, hipMemcpy (spot, d->hits.spot, nh * 4, hipMemcpyDeviceToHost));
+    HIPCHK (d, hipMemcpy (spot, H.spot, nh * 4, hipMemcpyDeviceToHost));
   if (orient)
-    HIPCHK (d, hipMemcpy (orient, d->hits.orient, nh, hipMemcpyDeviceToHost));
+    HIPCHK (d, hipMemcpy (orient, H.orient, nh, hipMemcpyDeviceToHost));
   if (win_start)
-    HIPCHK (d, hipMemcpy (win_start, d->hits.gpos, nh * 4, hipMemcpyDeviceToHost));
+    HIPCHK (d, hipMemcpy (win_start, H.gpos, nh * 4, hipMemcpyDeviceToHost));
   if (score)
-    HIPCHK (d, hipMemcpy (score, d->hits.score, nh * 8, hipMemcpyDeviceToHost));
+    HIPCHK (d, hipMemcpy (score, H.score, nh * 8, hipMemcpyDeviceToHost));
   if (win_len || start_i)
     {
       std::vector < int16_t > t (nh);
       if (win_len)
         {
-          HIPCHK (d, hipMemcpy (t.data (), d->hits.nn, nh * 2, hipMemcpyDeviceToHost));
+          HIPCHK (d, hipMemcpy (t.data (), H.nn, nh * 2, hipMemcpyDeviceToHost));
           for (size_t i = 0; i < nh; i++)
             win_len[i] = t[i];
         }
       if (start_i)
         {
-          HIPCHK (d, hipMemcpy (t.data (), d->hits.sti, nh * 2, hipMemcpyDeviceToHost));
+          HIPCHK (d, hipMemcpy (t.data (), H.sti, nh * 2, hipMemcpyDeviceToHost));
           for (size_t i = 0; i < nh; i++)
             start_i[i] = t[i];
         }
@@ -2205,7 +2114,7 @@ extern "C" int pemap_dev_debug_hits (pemap_dev * d, int *n_hits, uint32_t * spot
   if (start_k)
     {
       std::vector < uint8_t > t (nh);
-      HIPCHK (d, hipMemcpy (t.data (), d->hits.stk, nh, hipMemcpyDeviceToHost));
+      HIPCHK (d, hipMemcpy (t.data (), H.stk, nh, hipMemcpyDeviceToHost));
       for (size_t i = 0; i < nh; i++)
         start_k[i] = t[i] & 3;  // (bit 2 = decided by the gapless rule)
     }
@@ -2236,8 +2145,8 @@ extern "C" int pemap_dev_fetch_pileup (pemap_dev * d, uint16_t * counts, pemap_i
   if (counts)
     {
       const uint64_t chunk = 48ull << 20;       // positions per round (6 counters each)
-      uint16_t *d_tmp = nullptr;
-      TRY (dev_alloc (d, &d_tmp, (size_t) (d->gsize < chunk ? d->gsize : chunk) * 6));
+      DevTmp < uint16_t > d_tmp;
+      TRY (dev_alloc (d, &d_tmp.p, (size_t) (d->gsize < chunk ? d->gsize : chunk) * 6));
       for (uint64_t o = 0; o < d->gsize; o += chunk)
         {
           const uint64_t m = d->gsize - o < chunk ? d->gsize - o : chunk;
@@ -2245,7 +2154,6 @@ extern "C" int pemap_dev_fetch_pileup (pemap_dev * d, uint16_t * counts, pemap_i
           HIPCHK (d, hipStreamSynchronize (d->stream));
           HIPCHK (d, hipMemcpy (counts + o * 6, d_tmp, m * 6 * sizeof (uint16_t), hipMemcpyDeviceToHost));
         }
-      hipFree (d_tmp);
     }
   if (cb)
     {
@@ -2285,42 +2193,30 @@ extern "C" int pemap_dev_fetch_records (pemap_dev * d, uint64_t first, uint64_t 
     return fail (d, "fetch_records: at most 2^31 sites per call");
   HIPCHK (d, hipStreamSynchronize (d->stream));
   const uint64_t n_tiles = (count + PR_BLOCK - 1) / PR_BLOCK;
-  uint32_t *d_tc = nullptr;
-  uint64_t *d_to = nullptr, *d_total = nullptr;
-  TRY (dev_alloc (d, &d_tc, n_tiles));
-  TRY (dev_alloc (d, &d_to, n_tiles));
-  TRY (dev_alloc (d, &d_total, 1));
+  DevTmp < uint64_t > d_total, d_to;
+  DevTmp < uint32_t > d_tc;
+  TRY (dev_alloc (d, &d_tc.p, n_tiles));
+  TRY (dev_alloc (d, &d_to.p, n_tiles));
+  TRY (dev_alloc (d, &d_total.p, 1));
   hipLaunchKernelGGL (pile_count_kernel, dim3 ((unsigned) n_tiles), dim3 (PR_BLOCK), 0, d->stream, pile_of (d), first, count, d_tc);
   hipLaunchKernelGGL (ix_scan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d_tc, d_to, n_tiles, d_total);
   uint64_t total = 0;
   HIPCHK (d, hipMemcpyAsync (&total, d_total, 8, hipMemcpyDeviceToHost, d->stream));
   HIPCHK (d, hipStreamSynchronize (d->stream));
   *n_records = total;
-  int rc = 0;
-  if (out && total)
-    {
-      if (total > out_capacity)
-        rc = fail (d, "fetch_records: %llu records do not fit the caller's %llu", (unsigned long long) total,
-                   (unsigned long long) out_capacity);
-      else
-        {
-          PileRec *d_out = nullptr;
-          rc = dev_alloc (d, &d_out, (size_t) total);
-          if (!rc)
-            {
-              hipLaunchKernelGGL (pile_emit_kernel, dim3 ((unsigned) n_tiles), dim3 (PR_BLOCK), 0, d->stream, pile_of (d), first, count, d_to,
-                                  d_out, total);
-              if (hipStreamSynchronize (d->stream) != hipSuccess
-                  || hipMemcpy (out, d_out, total * sizeof (PileRec), hipMemcpyDeviceToHost) != hipSuccess)
-                rc = fail (d, "fetch_records: copy failed");
-              hipFree (d_out);
-            }
-        }
-    }
-  hipFree (d_tc);
-  hipFree (d_to);
-  hipFree (d_total);
-  return rc;
+  if (!out || !total)
+    return 0;
+  if (total > out_capacity)
+    return fail (d, "fetch_records: %llu records do not fit the caller's %llu", (unsigned long long) total,
+                 (unsigned long long) out_capacity);
+  DevTmp < PileRec > d_out;
+  TRY (dev_alloc (d, &d_out.p, (size_t) total));
+  hipLaunchKernelGGL (pile_emit_kernel, dim3 ((unsigned) n_tiles), dim3 (PR_BLOCK), 0, d->stream, pile_of (d), first, count, d_to,
+                      d_out, total);
+  if (hipStreamSynchronize (d->stream) != hipSuccess
+      || hipMemcpy (out, d_out, total * sizeof (PileRec), hipMemcpyDeviceToHost) != hipSuccess)
+    return fail (d, "fetch_records: copy failed");
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2355,14 +2251,13 @@ extern "C" int pemap_dev_synth_genome (pemap_dev * d, uint64_t seed, uint64_t ge
     return fail (d, "synth_genome: contig split failed");
   uint8_t *g = nullptr;
   TRY (dev_alloc (d, &g, genome_size + 512));
-  uint64_t *d_real = nullptr;
-  TRY (dev_alloc (d, &d_real, (size_t) n_contigs + 1));
+  DevTmp < uint64_t > d_real;
+  TRY (dev_alloc (d, &d_real.p, (size_t) n_contigs + 1));
   HIPCHK (d, hipMemcpy (d_real, real.data (), (n_contigs + 1) * 8, hipMemcpyHostToDevice));
   unsigned thr = (unsigned) (repeat_frac * 16777216.0);
   hipLaunchKernelGGL (sy_genome_kernel, dim3 ((unsigned) ((genome_size + 255) / 256)), dim3 (256), 0, d->stream, seed, g, genome_size, d_real,
                       n_contigs, thr);
   HIPCHK (d, hipStreamSynchronize (d->stream));
-  hipFree (d_real);
   *d_genome_out = g;
   return 0;
 }

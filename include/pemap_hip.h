@@ -262,6 +262,44 @@ int pecall_dev_sites_stage (pecall_dev * dev, const uint16_t * reads, const uint
 int pecall_dev_sites_run (pecall_dev * dev, int haploid, double threshold, double theta, float *kernel_ms);
 int pecall_dev_sites_collect (pecall_dev * dev, int8_t * call, double *posterior, int8_t * site_type, int32_t * allele_count,
                               int8_t * n_pass, int32_t * denovo);
+/* ---- PECaller: pileup columns made on the device from the samples' record streams ----
+ * What the host otherwise does before pecall_dev_call_sites: the k-way merge of the pileup streams (find_lowest and the dispatcher's
+ * per-column loop, pecaller.c:865-923, 1820-1833).  A record is the pileup file's own 16 bytes, little-endian:
+ * {u32 pos; u16 A,C,G,T,Del,Ins} -- what pemapper_hip writes and pemap_dev_fetch_records returns.
+ * pecall_dev_sites_stage_records takes every sample's records of the positions [p0, p0 + span) and leaves the columns staged as
+ * pecall_dev_sites_stage does (pecall_dev_sites_run / _collect follow unchanged):
+ *   recs[indiv], n_recs[indiv]        host arrays of records, one per sample (NULL where n_recs is 0); ranges page-locked with
+ *                                     pecall_dev_pin_host are copied from directly, others through the object's staging buffer.
+ *                                     Each sample's positions ascend strictly and lie in [p0, p0 + span).
+ *   ref_letters[ref_len <= span]      the .seq letters of the range from p0 on: a column's reference byte is its letter's index in
+ *                                     "ACGTDIMRWSYKEHN" (gen_to_int, pecaller.c:2869-2907), 255 for any other byte and for
+ *                                     positions at or beyond ref_len (the caller skips such columns: anything above 3)
+ *   chrom_by_slot[span] (may be NULL) the chromosome class of every position of the range (chrom_type above); NULL: 0
+ *   *n_cols                           columns made: a position is a column if and only if some sample has a record there (all six
+ *                                     counts zero or not); a sample without a record there has six zeros.  Ascending positions.
+ *   col_slot[span] (may be NULL)      position - p0 of each of the n_cols columns
+ * Limits: 1 <= indiv <= 512, 1 <= span <= 2^22.  Returns 0; PECALL_RC_UNORDERED when a stream does not ascend strictly or leaves
+ * the range (no other path returns that value; the error text names the lowest such sample and its record's index; nothing is
+ * staged); another non-zero value for bad arguments.  No records at all: 0, *n_cols = 0, nothing staged. */
+#define PECALL_RC_UNORDERED 3
+int pecall_dev_sites_stage_records (pecall_dev * dev, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0, uint32_t span,
+                                    const char *ref_letters, uint32_t ref_len, const uint8_t * chrom_by_slot /* may be NULL */ ,
+                                    long *n_cols, uint32_t * col_slot /* [span], may be NULL */ );
+/* The staged columns back on the host -- the result of the merge above (merge_columns' reads[n][indiv][6], reference and chromosome
+ * bytes; in the reference the columns of pecaller.c:865-923): columns cols[0 .. n) (NULL: columns 0 .. n - 1) through a gather
+ * kernel and one device-to-host copy (per 64 MB).  Any output may be NULL.  Valid for whatever is staged, until the next stage or call. */
+int pecall_dev_sites_gather (pecall_dev * dev, const uint32_t * cols /* NULL: columns 0..n-1 */ , uint64_t n,
+                             uint16_t * reads_out, uint8_t * ref_base_out, uint8_t * chrom_out /* any may be NULL */ );
+/* Kernel durations of the last pecall_dev_sites_stage_records in ms (HIP events): mark, scan, tile. */
+int pecall_dev_sites_merge_ms (pecall_dev * dev, float *ms3);
+/* The one-call form (the merge of pecaller.c:865-923, 1820-1833 and call_single_base behind it): pecall_dev_sites_stage_records,
+ * then the chunk pipeline of pecall_dev_call_sites_sparse over the resident columns, without its host-to-device copies.  The result
+ * arrays are sized by the caller for span columns and filled for *n_cols; post_cap too small: as pecall_dev_call_sites_sparse. */
+int pecall_dev_call_records (pecall_dev * dev, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0, uint32_t span,
+                             const char *ref_letters, uint32_t ref_len, const uint8_t * chrom_by_slot, long *n_cols, uint32_t * col_slot,
+                             int haploid, double threshold, double theta, int8_t * call, uint32_t * post_site, double *post_rows,
+                             uint64_t post_cap, uint64_t * n_post, int8_t * site_type, int32_t * allele_count, int8_t * n_pass,
+                             int32_t * denovo);
 /* use_pedfile = y (pecaller.c:376-392, 561-604): parents as sample indices (-1 = not sampled), sex (1 male, 2 female), and each
  * sample's kids in ped-file order: kids of i = kid_list[kid_off[i] .. kid_off[i + 1]).  denovo_rate = argv[11] (<= theta).
  * The configuration prior then carries no_denovo * ln(denovo_rate) (add_denovo, 2396-2445, tables of main 312-374).

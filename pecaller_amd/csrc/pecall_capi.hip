@@ -10,6 +10,7 @@
 #include "../../include/pemap_hip.h"
 #include "pecall_kernels.hip.h"
 #include "pecall_site.hip.h"
+#include "pecall_merge.hip.h"
 
 static char g_pc_err[512] = "";
 #define PCS_SLOTS 3             // staging buffers of the seam's pipeline (chunks in flight between the two host copies)
@@ -84,6 +85,22 @@ struct pecall_dev
   hipEvent_t *ev_h2d, *ev_fast, *ev_call, *ev_d2h;      // [cap_chunks]
   char *h_in[PCS_SLOTS], *h_out[PCS_SLOTS];            // pinned staging for callers whose buffers are not pinned
   size_t h_in_bytes, h_out_bytes;
+  // pecall_dev_sites_stage_records (pecall_merge.hip.h): the samples' records one behind the other and where each sample's begin; per
+  // slot of the range its mark, its column, its reference letter and chromosome class; per column its slot; the blocks' counts of the scan
+  uint4 *d_mrecs;
+  size_t cap_mrecs;
+  unsigned long long *d_moff;   // [PCS_MAXN + 1]
+  uint8_t *d_mmarks, *d_mletters, *d_mchrom;
+  unsigned *d_mcolof, *d_mcolslot, *d_mbsum;
+  size_t cap_mspan;
+  PcmCtl *d_mctl;
+  char *h_mstage;               // page-locked: what comes back (PcmCtl, col_slot), then what goes up (offsets, letters, classes, records that are not pinned)
+  size_t h_mstage_bytes;
+  hipEvent_t ev_m[6];           // around the mark kernel, the scan's first two kernels, its third, the tile kernel
+  float merge_ms[3];            // mark, scan, tile of the last pecall_dev_sites_stage_records
+  // pecall_dev_sites_gather
+  char *d_gather, *h_gather;
+  size_t cap_gather;
 };
 
 static int pc_fail (pecall_dev * d, const char *fmt, ...)
@@ -206,6 +223,23 @@ extern "C" void pecall_dev_destroy (pecall_dev * d)
   hipFree (d->d_sp_n);
   if (d->h_ctrs)
     hipHostFree (d->h_ctrs);
+  hipFree (d->d_mrecs);
+  hipFree (d->d_moff);
+  hipFree (d->d_mmarks);
+  hipFree (d->d_mletters);
+  hipFree (d->d_mchrom);
+  hipFree (d->d_mcolof);
+  hipFree (d->d_mcolslot);
+  hipFree (d->d_mbsum);
+  hipFree (d->d_mctl);
+  hipFree (d->d_gather);
+  if (d->h_mstage)
+    hipHostFree (d->h_mstage);
+  if (d->h_gather)
+    hipHostFree (d->h_gather);
+  for (int i = 0; i < 6; i++)
+    if (d->ev_m[i])
+      hipEventDestroy (d->ev_m[i]);
   hipFree (d->d_next_site);
   if (d->ev_site[0])
     {
@@ -1033,12 +1067,13 @@ extern "C" int pecall_dev_unpin_host (pecall_dev * d, const void *host_ptr)
 static int pcs_call_sites_impl (pecall_dev * d, const uint16_t * reads, const uint8_t * ref_base, const uint8_t * chrom_type, long n_sites,
                                 int indiv, int haploid, double threshold, double theta, int8_t * call, double *posterior,
                                 int8_t * site_type, int32_t * allele_count, int8_t * n_pass, int32_t * denovo,
-                                bool sparse, uint32_t * post_site, double *post_rows, uint64_t post_cap, uint64_t * n_post)
+                                bool sparse, uint32_t * post_site, double *post_rows, uint64_t post_cap, uint64_t * n_post, bool resident = false)
 {
+  // resident: the columns are on the device already (pecall_dev_sites_stage_records): no host arrays, no host-to-device copies
   PCCHK (d, hipSetDevice (d->device));
   if (n_sites <= 0 || indiv <= 0 || indiv > PCS_MAXN)
     return pc_fail (d, "call_sites: n_sites %ld, indiv %d (1..%d samples per call)", n_sites, indiv, PCS_MAXN);
-  if (!reads || !ref_base || !call || (!sparse && !posterior))
+  if ((!resident && (!reads || !ref_base)) || !call || (!sparse && !posterior))
     return pc_fail (d, "call_sites: a required pointer is NULL");
   if (sparse && (!post_site || !post_rows || !n_post || post_cap == 0))
     return pc_fail (d, "call_sites_sparse: the list of posteriors needs post_site, post_rows, a capacity and n_post");
@@ -1079,8 +1114,8 @@ static int pcs_call_sites_impl (pecall_dev * d, const uint16_t * reads, const ui
   const size_t N = (size_t) indiv;
   // per column: in = reads + reference base + chromosome class; out = calls + posteriors + type + passes + allele counts + de-novo count
   const size_t in_col = N * PCS_NA * 2 + 2, out_col = N * (sparse ? 1 : 9) + 2 + PCS_NA * 4 + 4;
-  const bool in_direct = pm_host_pin_lookup (reads, (size_t) n_sites * N * PCS_NA * 2) && pm_host_pin_lookup (ref_base, (size_t) n_sites)
-    && (!chrom_type || pm_host_pin_lookup (chrom_type, (size_t) n_sites));
+  const bool in_direct = resident || (pm_host_pin_lookup (reads, (size_t) n_sites * N * PCS_NA * 2) && pm_host_pin_lookup (ref_base, (size_t) n_sites)
+    && (!chrom_type || pm_host_pin_lookup (chrom_type, (size_t) n_sites)));
   const bool out_direct = pm_host_pin_lookup (call, (size_t) n_sites * N) && (sparse || pm_host_pin_lookup (posterior, (size_t) n_sites * N * 8))
     && (!site_type || pm_host_pin_lookup (site_type, (size_t) n_sites)) && (!allele_count || pm_host_pin_lookup (allele_count, (size_t) n_sites * PCS_NA * 4))
     && (!n_pass || pm_host_pin_lookup (n_pass, (size_t) n_sites)) && (!denovo || pm_host_pin_lookup (denovo, (size_t) n_sites * 4));
@@ -1169,31 +1204,34 @@ static int pcs_call_sites_impl (pecall_dev * d, const uint16_t * reads, const ui
       const double t0 = since ();
       // ---- in: (a staging slot is free again when the chunk that used it PCS_SLOTS chunks ago has been copied to the device; the
       //      result slot of the same number when that chunk's results have been handed over: finish (k - PCS_SLOTS))
-      const uint16_t *src_r = reads + off * N * PCS_NA;
-      const uint8_t *src_b = ref_base + off, *src_c = chrom_type ? chrom_type + off : nullptr;
-      if (!in_direct)
+      if (!resident)
         {
-          if (k >= PCS_SLOTS)
-            PCCHK (d, hipEventSynchronize (d->ev_h2d[k - PCS_SLOTS]));
-          char *st = d->h_in[k % PCS_SLOTS];
-          pm_par_memcpy (st, (const char *) src_r, (size_t) m * N * PCS_NA * 2);
-          src_r = (const uint16_t *) st;
-          st += (size_t) m * N * PCS_NA * 2;
-          memcpy (st, src_b, (size_t) m);
-          src_b = (const uint8_t *) st;
-          st += m;
-          if (src_c)
+          const uint16_t *src_r = reads + off * N * PCS_NA;
+          const uint8_t *src_b = ref_base + off, *src_c = chrom_type ? chrom_type + off : nullptr;
+          if (!in_direct)
             {
-              memcpy (st, src_c, (size_t) m);
-              src_c = (const uint8_t *) st;
+              if (k >= PCS_SLOTS)
+                PCCHK (d, hipEventSynchronize (d->ev_h2d[k - PCS_SLOTS]));
+              char *st = d->h_in[k % PCS_SLOTS];
+              pm_par_memcpy (st, (const char *) src_r, (size_t) m * N * PCS_NA * 2);
+              src_r = (const uint16_t *) st;
+              st += (size_t) m * N * PCS_NA * 2;
+              memcpy (st, src_b, (size_t) m);
+              src_b = (const uint8_t *) st;
+              st += m;
+              if (src_c)
+                {
+                  memcpy (st, src_c, (size_t) m);
+                  src_c = (const uint8_t *) st;
+                }
             }
+          PCCHK (d, hipMemcpyAsync (d->d_sreads + off * N * PCS_NA, src_r, (size_t) m * N * PCS_NA * 2, hipMemcpyHostToDevice, d->stream_h2d));
+          PCCHK (d, hipMemcpyAsync (d->d_dom + off, src_b, (size_t) m, hipMemcpyHostToDevice, d->stream_h2d));
+          if (src_c)
+            PCCHK (d, hipMemcpyAsync (d->d_chromy + off, src_c, (size_t) m, hipMemcpyHostToDevice, d->stream_h2d));
+          else
+            PCCHK (d, hipMemsetAsync (d->d_chromy + off, 0, (size_t) m, d->stream_h2d));
         }
-      PCCHK (d, hipMemcpyAsync (d->d_sreads + off * N * PCS_NA, src_r, (size_t) m * N * PCS_NA * 2, hipMemcpyHostToDevice, d->stream_h2d));
-      PCCHK (d, hipMemcpyAsync (d->d_dom + off, src_b, (size_t) m, hipMemcpyHostToDevice, d->stream_h2d));
-      if (src_c)
-        PCCHK (d, hipMemcpyAsync (d->d_chromy + off, src_c, (size_t) m, hipMemcpyHostToDevice, d->stream_h2d));
-      else
-        PCCHK (d, hipMemsetAsync (d->d_chromy + off, 0, (size_t) m, d->stream_h2d));
       PCCHK (d, hipEventRecord (d->ev_h2d[k], d->stream_h2d));
       // ---- the chunk's kernels behind its copy, its results behind its kernels: all queued, the host goes on to the next chunk
       PCCHK (d, hipStreamWaitEvent (d->stream, d->ev_h2d[k], 0));
@@ -1266,6 +1304,267 @@ static int pcs_call_sites_impl (pecall_dev * d, const uint16_t * reads, const ui
   if (trace)
     fprintf (stderr, "[pecall seam] done at %.2f ms\n", since ());
   return 0;
+}
+
+// ---- columns from record streams (pecall_merge.hip.h)
+
+static inline size_t pcm_up64 (size_t x)
+{
+  return (x + 63) & ~(size_t) 63;
+}
+
+// Replaces the host's k-way merge of the pileup streams (find_lowest and the per-column loop, pecaller.c:865-923, 1820-1833) for a
+// range of positions: the samples' records go up as they are, the kernels of pecall_merge.hip.h make the columns.  The host waits
+// twice: for the number of columns (the column arrays are sized by it) and for the end.
+extern "C" int pecall_dev_sites_stage_records (pecall_dev * d, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0, uint32_t span,
+                                               const char *ref_letters, uint32_t ref_len, const uint8_t * chrom_by_slot, long *n_cols, uint32_t * col_slot)
+{
+  PCCHK (d, hipSetDevice (d->device));
+  if (n_cols)
+    *n_cols = 0;
+  if (!recs || !n_recs || !n_cols)
+    return pc_fail (d, "stage_records: recs, n_recs and n_cols are required");
+  if (indiv < 1 || indiv > PCS_MAXN || span < 1 || span > PCM_MAX_SPAN)
+    return pc_fail (d, "stage_records: indiv %d (1..%d), span %u (1..%u)", indiv, PCS_MAXN, span, PCM_MAX_SPAN);
+  if (ref_len > span || (ref_len && !ref_letters))
+    return pc_fail (d, "stage_records: %u reference letters for a range of %u positions", ref_len, span);
+  // (a stream of more than span records has a record out of order or out of range among its first span + 1: those go up)
+  unsigned long long off[PCS_MAXN + 1];
+  size_t staged_bytes = 0;
+  off[0] = 0;
+  for (int i = 0; i < indiv; i++)
+    {
+      const unsigned long long n = n_recs[i] > (uint64_t) span + 1 ? (unsigned long long) span + 1 : (unsigned long long) n_recs[i];
+      if (n && !recs[i])
+        return pc_fail (d, "stage_records: sample %d has %llu records and no array", i, (unsigned long long) n_recs[i]);
+      off[i + 1] = off[i] + n;
+      if (n && !pm_host_pin_lookup (recs[i], (size_t) n * 16))
+        staged_bytes += (size_t) n * 16;
+    }
+  d->staged_sites = 0;
+  const size_t total = (size_t) off[indiv];
+  if (total == 0)
+    return 0;
+  const size_t span_pad = ((size_t) span + PCM_SCAN_TILE - 1) / PCM_SCAN_TILE * PCM_SCAN_TILE;
+  const unsigned nb = (unsigned) (span_pad / PCM_SCAN_TILE);
+  if (!d->d_mbsum)
+    {
+      for (int i = 0; i < 6; i++)
+        if (!d->ev_m[i])
+          PCCHK (d, hipEventCreate (&d->ev_m[i]));
+      hipFree (d->d_moff);
+      hipFree (d->d_mctl);
+      d->d_moff = nullptr;
+      d->d_mctl = nullptr;
+      PCCHK (d, hipMalloc ((void **) &d->d_moff, sizeof (unsigned long long) * (PCS_MAXN + 1)));
+      PCCHK (d, hipMalloc ((void **) &d->d_mctl, sizeof (PcmCtl)));
+      PCCHK (d, hipMalloc ((void **) &d->d_mbsum, sizeof (unsigned) * PCM_MAX_SCAN_BLOCKS));
+    }
+  if (total > d->cap_mrecs)
+    {
+      hipFree (d->d_mrecs);
+      d->d_mrecs = nullptr;
+      d->cap_mrecs = 0;
+      PCCHK (d, hipMalloc ((void **) &d->d_mrecs, total * 16));
+      d->cap_mrecs = total;
+    }
+  if (span_pad > d->cap_mspan)
+    {
+      hipFree (d->d_mmarks); hipFree (d->d_mletters); hipFree (d->d_mchrom); hipFree (d->d_mcolof); hipFree (d->d_mcolslot);
+      d->d_mmarks = d->d_mletters = d->d_mchrom = nullptr;
+      d->d_mcolof = d->d_mcolslot = nullptr;
+      d->cap_mspan = 0;
+      PCCHK (d, hipMalloc ((void **) &d->d_mmarks, span_pad));
+      PCCHK (d, hipMalloc ((void **) &d->d_mletters, span_pad));
+      PCCHK (d, hipMalloc ((void **) &d->d_mchrom, span_pad));
+      PCCHK (d, hipMalloc ((void **) &d->d_mcolof, span_pad * sizeof (unsigned)));
+      PCCHK (d, hipMalloc ((void **) &d->d_mcolslot, span_pad * sizeof (unsigned)));
+      d->cap_mspan = span_pad;
+    }
+  // staging: [PcmCtl][col_slot span][offsets][letters][classes][records of ranges that are not pinned]
+  const size_t at_slot = 64, at_off = at_slot + pcm_up64 ((size_t) span * 4), at_let = at_off + pcm_up64 (sizeof off), at_chr = at_let + pcm_up64 (span),
+    at_rec = at_chr + pcm_up64 (span), need = at_rec + staged_bytes;
+  if (need > d->h_mstage_bytes)
+    {
+      if (d->h_mstage)
+        hipHostFree (d->h_mstage);
+      d->h_mstage = nullptr;
+      d->h_mstage_bytes = 0;
+      PCCHK (d, hipHostMalloc ((void **) &d->h_mstage, need + need / 4, hipHostMallocDefault));
+      d->h_mstage_bytes = need + need / 4;
+    }
+  char *st = d->h_mstage;
+  memcpy (st + at_off, off, sizeof (unsigned long long) * (size_t) (indiv + 1));
+  PCCHK (d, hipMemcpyAsync (d->d_moff, st + at_off, sizeof (unsigned long long) * (size_t) (indiv + 1), hipMemcpyHostToDevice, d->stream));
+  if (ref_len)
+    {
+      memcpy (st + at_let, ref_letters, ref_len);
+      PCCHK (d, hipMemcpyAsync (d->d_mletters, st + at_let, ref_len, hipMemcpyHostToDevice, d->stream));
+    }
+  if (chrom_by_slot)
+    {
+      memcpy (st + at_chr, chrom_by_slot, span);
+      PCCHK (d, hipMemcpyAsync (d->d_mchrom, st + at_chr, span, hipMemcpyHostToDevice, d->stream));
+    }
+  {
+    char *sr = st + at_rec;
+    for (int i = 0; i < indiv; i++)
+      {
+        const size_t bytes = (size_t) (off[i + 1] - off[i]) * 16;
+        if (!bytes)
+          continue;
+        const void *src = recs[i];
+        if (!pm_host_pin_lookup (src, bytes))
+          {
+            pm_par_memcpy (sr, (const char *) src, bytes);
+            src = sr;
+            sr += bytes;
+          }
+        PCCHK (d, hipMemcpyAsync (d->d_mrecs + off[i], src, bytes, hipMemcpyHostToDevice, d->stream));
+      }
+  }
+  PCCHK (d, hipMemsetAsync (d->d_mmarks, 0, span_pad, d->stream));
+  PCCHK (d, hipMemsetAsync (&d->d_mctl->bad, 0xff, sizeof (unsigned long long), d->stream));
+  PCCHK (d, hipMemsetAsync (&d->d_mctl->n_cols, 0, 2 * sizeof (unsigned), d->stream));
+  // ---- stage 1: the marks; stage 2's first half: the number of columns
+  unsigned long long most = 0;
+  for (int i = 0; i < indiv; i++)
+    if (off[i + 1] - off[i] > most)
+      most = off[i + 1] - off[i];
+  const unsigned gx = (unsigned) ((most + PCM_BLOCK - 1) / PCM_BLOCK < 1024 ? (most + PCM_BLOCK - 1) / PCM_BLOCK : 1024);
+  PCCHK (d, hipEventRecord (d->ev_m[0], d->stream));
+  hipLaunchKernelGGL (pcm_mark_kernel, dim3 (gx, (unsigned) indiv), dim3 (PCM_BLOCK), 0, d->stream, (const uint4 *) d->d_mrecs, (const unsigned long long *) d->d_moff, p0, span,
+                      d->d_mmarks, d->d_mctl);
+  PCCHK (d, hipEventRecord (d->ev_m[1], d->stream));
+  hipLaunchKernelGGL (pcm_scan_reduce_kernel, dim3 (nb), dim3 (PCM_BLOCK), 0, d->stream, (const uint4 *) d->d_mmarks, d->d_mbsum);
+  hipLaunchKernelGGL (pcm_scan_top_kernel, dim3 (1), dim3 (PCM_MAX_SCAN_BLOCKS), 0, d->stream, d->d_mbsum, nb, d->d_mctl);
+  PCCHK (d, hipGetLastError ());
+  PCCHK (d, hipEventRecord (d->ev_m[2], d->stream));
+  PCCHK (d, hipMemcpyAsync (st, d->d_mctl, sizeof (PcmCtl), hipMemcpyDeviceToHost, d->stream));
+  PCCHK (d, hipStreamSynchronize (d->stream));
+  const PcmCtl ctl = *(const PcmCtl *) st;
+  if (ctl.bad != PCM_NO_BAD)
+    {
+      const int bs = (int) (ctl.bad >> PCM_BAD_SHIFT);
+      const unsigned long long bj = ctl.bad & ((1ull << PCM_BAD_SHIFT) - 1);
+      uint32_t bp = 0;
+      memcpy (&bp, (const char *) recs[bs] + (size_t) bj * 16, 4);
+      snprintf (d->err, sizeof d->err, "stage_records: sample %d, record %llu (position %u) is not beyond its predecessor or lies outside [%u, %llu): "
+                "the streams must ascend strictly inside the range", bs, bj, bp, p0, (unsigned long long) p0 + span);
+      return PECALL_RC_UNORDERED;
+    }
+  const long n = (long) ctl.n_cols;
+  int rc = pcs_ensure (d, n, indiv);
+  if (rc)
+    return rc;
+  // ---- stage 2's second half: the slots' columns; stage 3: the columns' reads
+  PCCHK (d, hipEventRecord (d->ev_m[3], d->stream));
+  hipLaunchKernelGGL (pcm_scan_apply_kernel, dim3 (nb), dim3 (PCM_BLOCK), 0, d->stream, (const uint4 *) d->d_mmarks, (const unsigned *) d->d_mbsum, span,
+                      (const uint8_t *) d->d_mletters, ref_len, chrom_by_slot ? (const uint8_t *) d->d_mchrom : (const uint8_t *) nullptr, d->d_mcolof, d->d_mcolslot,
+                      d->d_dom, d->d_chromy);
+  PCCHK (d, hipEventRecord (d->ev_m[4], d->stream));
+  const int S = pcm_tile_slots (indiv);
+  const size_t lds = (size_t) S * indiv * 12 + (size_t) S * 4 + (size_t) indiv * 4;
+  hipLaunchKernelGGL (pcm_tile_kernel, dim3 ((span + (unsigned) S - 1) / (unsigned) S), dim3 (PCM_BLOCK), lds, d->stream, (const uint4 *) d->d_mrecs,
+                      (const unsigned long long *) d->d_moff, indiv, p0, span, S, (const uint8_t *) d->d_mmarks, (const unsigned *) d->d_mcolof, (const PcmCtl *) d->d_mctl,
+                      d->d_sreads);
+  PCCHK (d, hipGetLastError ());
+  PCCHK (d, hipEventRecord (d->ev_m[5], d->stream));
+  if (col_slot)
+    PCCHK (d, hipMemcpyAsync (st + at_slot, d->d_mcolslot, (size_t) n * 4, hipMemcpyDeviceToHost, d->stream));
+  PCCHK (d, hipStreamSynchronize (d->stream));
+  if (col_slot)
+    memcpy (col_slot, st + at_slot, (size_t) n * 4);
+  float a = 0, b = 0;
+  PCCHK (d, hipEventElapsedTime (&d->merge_ms[0], d->ev_m[0], d->ev_m[1]));
+  PCCHK (d, hipEventElapsedTime (&a, d->ev_m[1], d->ev_m[2]));
+  PCCHK (d, hipEventElapsedTime (&b, d->ev_m[3], d->ev_m[4]));
+  d->merge_ms[1] = a + b;
+  PCCHK (d, hipEventElapsedTime (&d->merge_ms[2], d->ev_m[4], d->ev_m[5]));
+  d->staged_sites = n;
+  d->staged_indiv = indiv;
+  *n_cols = n;
+  return 0;
+}
+
+extern "C" int pecall_dev_sites_merge_ms (pecall_dev * d, float *ms3)
+{
+  if (!ms3)
+    return pc_fail (d, "sites_merge_ms: no array");
+  memcpy (ms3, d->merge_ms, sizeof d->merge_ms);
+  return 0;
+}
+
+extern "C" int pecall_dev_sites_gather (pecall_dev * d, const uint32_t * cols, uint64_t n, uint16_t * reads_out, uint8_t * ref_base_out, uint8_t * chrom_out)
+{
+  PCCHK (d, hipSetDevice (d->device));
+  const long staged = d->staged_sites;
+  const size_t N = (size_t) d->staged_indiv;
+  if (staged <= 0)
+    return pc_fail (d, "sites_gather: nothing staged");
+  if (!cols && n > (uint64_t) staged)
+    return pc_fail (d, "sites_gather: %llu columns asked for, %ld staged", (unsigned long long) n, staged);
+  for (uint64_t i = 0; cols && i < n; i++)
+    if (cols[i] >= (uint64_t) staged)
+      return pc_fail (d, "sites_gather: cols[%llu] = %u, %ld columns are staged", (unsigned long long) i, cols[i], staged);
+  if (n == 0)
+    return 0;
+  // a piece of the columns at a time: [column numbers][reads][reference bytes][chromosome bytes], the last three in one copy
+  const size_t row = N * PCS_NA * 2, per_col = 4 + row + 2;
+  const size_t piece = n * per_col <= ((size_t) 64 << 20) ? (size_t) n : (((size_t) 64 << 20) / per_col > 0 ? ((size_t) 64 << 20) / per_col : 1);
+  const size_t need = piece * per_col;
+  if (need > d->cap_gather)
+    {
+      PCCHK (d, hipStreamSynchronize (d->stream));
+      hipFree (d->d_gather);
+      if (d->h_gather)
+        hipHostFree (d->h_gather);
+      d->d_gather = d->h_gather = nullptr;
+      d->cap_gather = 0;
+      PCCHK (d, hipMalloc ((void **) &d->d_gather, need));
+      PCCHK (d, hipHostMalloc ((void **) &d->h_gather, need, hipHostMallocDefault));
+      d->cap_gather = need;
+    }
+  for (size_t at = 0; at < (size_t) n; at += piece)
+    {
+      const size_t m = (size_t) n - at < piece ? (size_t) n - at : piece;
+      const size_t o_reads = piece * 4, o_ref = o_reads + m * row, o_chr = o_ref + m;
+      if (cols)
+        {
+          memcpy (d->h_gather, cols + at, m * 4);
+          PCCHK (d, hipMemcpyAsync (d->d_gather, d->h_gather, m * 4, hipMemcpyHostToDevice, d->stream));
+        }
+      const unsigned grid = (unsigned) (m < (size_t) d->grid * 8 ? m : (size_t) d->grid * 8);
+      // (cols == nullptr: columns at .. at + m - 1, the arrays offset instead)
+      hipLaunchKernelGGL (pcm_gather_kernel, dim3 (grid), dim3 (PCM_BLOCK), 0, d->stream, (const uint16_t *) d->d_sreads + (cols ? 0 : at * N * PCS_NA),
+                          (const uint8_t *) d->d_dom + (cols ? 0 : at), (const uint8_t *) d->d_chromy + (cols ? 0 : at), cols ? staged : staged - (long) at, (int) N,
+                          cols ? (const unsigned *) d->d_gather : (const unsigned *) nullptr, (unsigned long long) m, (unsigned *) (d->d_gather + o_reads),
+                          (uint8_t *) d->d_gather + o_ref, (uint8_t *) d->d_gather + o_chr);
+      PCCHK (d, hipGetLastError ());
+      PCCHK (d, hipMemcpyAsync (d->h_gather + o_reads, d->d_gather + o_reads, m * (row + 2), hipMemcpyDeviceToHost, d->stream));
+      PCCHK (d, hipStreamSynchronize (d->stream));
+      if (reads_out)
+        pm_par_memcpy ((char *) reads_out + at * row, d->h_gather + o_reads, m * row);
+      if (ref_base_out)
+        memcpy (ref_base_out + at, d->h_gather + o_ref, m);
+      if (chrom_out)
+        memcpy (chrom_out + at, d->h_gather + o_chr, m);
+    }
+  return 0;
+}
+
+extern "C" int pecall_dev_call_records (pecall_dev * d, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0, uint32_t span, const char *ref_letters,
+                                        uint32_t ref_len, const uint8_t * chrom_by_slot, long *n_cols, uint32_t * col_slot, int haploid, double threshold, double theta,
+                                        int8_t * call, uint32_t * post_site, double *post_rows, uint64_t post_cap, uint64_t * n_post, int8_t * site_type,
+                                        int32_t * allele_count, int8_t * n_pass, int32_t * denovo)
+{
+  if (n_post)
+    *n_post = 0;
+  const int rc = pecall_dev_sites_stage_records (d, recs, n_recs, indiv, p0, span, ref_letters, ref_len, chrom_by_slot, n_cols, col_slot);
+  if (rc || *n_cols == 0)
+    return rc;
+  return pcs_call_sites_impl (d, nullptr, nullptr, nullptr, *n_cols, indiv, haploid, threshold, theta, call, nullptr, site_type, allele_count, n_pass, denovo, true, post_site,
+                              post_rows, post_cap, n_post, true);
 }
 
 extern "C" int pecall_dev_call_sites (pecall_dev * d, const uint16_t * reads, const uint8_t * ref_base, const uint8_t * chrom_type, long n_sites,

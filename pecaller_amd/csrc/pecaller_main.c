@@ -131,6 +131,13 @@ typedef struct
   uint64_t n_post, post_cap;
   int32_t *ac, *denovo;
   long n;
+  /* PECALLER_DEVICE_MERGE=1 (NULL otherwise): the range's records as the streams gave them, per sample, for pecall_dev_call_records;
+     the columns come back with their slots, and `reads` holds the variant columns' rows only: column s has row vrow[s] */
+  char *recs;                   /* [indiv][TILE] records of 16 bytes */
+  uint64_t *n_recs;             /* [indiv] */
+  uint8_t *chrom_slot;          /* [TILE]: chromosome class of position p0 + slot */
+  uint32_t *col_slot, *vrow, *vlist;    /* [TILE] */
+  unsigned int p0;
 } tile_t;
 
 /* The rows of <outfile>.base.gz are put together in memory and handed to the parallel gz writer tile by tile (host_io.h: gzip
@@ -234,7 +241,7 @@ emit_rows (const tile_t * t, long s0, long s1, int indiv, char **contig_names, s
       for (int i = 0; i < indiv; i++)
         {
           sb->n += (size_t) sprintf (sb_room (sb, 64), "\t%c\t%g", GEN[call[i]], p ? p[i] : 1.0);
-          const uint16_t *r = t->reads + ((size_t) s * indiv + i) * NA;
+          const uint16_t *r = t->reads + ((size_t) (t->vrow ? t->vrow[s] : (uint32_t) s) * indiv + i) * NA;
           for (int a = 0; a < NA; a++)
             pb->n += (size_t) sprintf (sb_room (pb, 16), "\t%d", (int) r[a]);
         }
@@ -434,6 +441,68 @@ merge_streams (void *arg)
   return NULL;
 }
 
+/* PECALLER_DEVICE_MERGE=1: the same walk with the stream's own part kept -- the statistics of <outfile>.dist, the pending record, the
+   end of the stream, the check of the order -- and the records of the range appended to the sample's buffer of the tile as they are:
+   the columns are made on the device (pecall_dev_call_records) */
+static void *
+merge_streams_dev (void *arg)
+{
+  merge_ctx *c = (merge_ctx *) arg;
+  for (int i = c->k; i < c->no_files; i += c->T)
+    {
+      sample_t *s = &c->sm[i];
+      char *out = c->t->recs + (size_t) i * TILE * 16;
+      size_t n_out = 0;
+      unsigned long long next_min = c->p0;      /* the lowest position the next record may have */
+      unsigned long long cov_sum = 0;
+      unsigned int cov_max = s->max_coverage;
+      zreader *z = &s->f;
+      while (s->cur != 0 && (unsigned long long) s->cur < c->p1)
+        {
+          unsigned int pos = s->cur;
+          const char *rec = NULL;       /* NULL: the counters are in s->data */
+          for (;;)
+            {
+              if ((unsigned long long) pos < next_min)
+                {
+                  g_unordered = 1;      /* (as in merge_streams) */
+                  return NULL;
+                }
+              char *dst = out + n_out * 16;
+              if (rec)
+                memcpy (dst, rec, 16);
+              else
+                {
+                  memcpy (dst, &pos, sizeof pos);
+                  memcpy (dst + 4, s->data, NA * sizeof (uint16_t));
+                }
+              uint16_t cnt[NA];
+              memcpy (cnt, dst + 4, sizeof cnt);
+              const unsigned int cov = (unsigned int) cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[4] + cnt[5];
+              cov_sum += cov;
+              if (cov > cov_max)
+                cov_max = cov;
+              s->counts[cov < MAX_DIST - 1 ? cov : MAX_DIST - 1]++;
+              n_out++;
+              next_min = (unsigned long long) pos + 1;
+              if (z->pos + 16 > z->cur_len)
+                break;
+              rec = z->ring[z->head] + z->pos;
+              memcpy (&pos, rec, sizeof pos);
+              if (pos == 0 || (unsigned long long) pos >= c->p1)
+                break;
+              z->pos += 16;
+            }
+          advance_nr (s);
+        }
+      s->mean += (double) cov_sum;
+      s->max_coverage = cov_max;
+      s->base_count += (unsigned int) n_out;
+      c->t->n_recs[i] = n_out;
+    }
+  return NULL;
+}
+
 static int
 slot_marked (const merge_ctx * c, size_t slot)
 {
@@ -551,6 +620,13 @@ typedef struct consumer_s
   const char *outname;
   double sec_dev, sec_text;
   long tot_cols;
+  /* PECALLER_DEVICE_MERGE=1: what the columns' contig, position and reference letter are made of behind the device call */
+  int device_merge;
+  const char *genome;
+  size_t gsize;
+  const unsigned int *frag_pos;
+  int no_contigs, start_chrom;
+  long dev_cols, dev_ranges;
 } consumer_t;
 
 static void consumer_wait_idle (consumer_t * c);
@@ -565,6 +641,49 @@ consumer_give (consumer_t * c, tile_t t)
   c->has_job = 1;
   pthread_cond_broadcast (&c->cv);
   pthread_mutex_unlock (&c->mu);
+}
+
+static int
+device_call (consumer_t * c, tile_t * t)
+{
+  if (!c->device_merge)
+    return pecall_dev_call_sites_sparse (c->pc, t->reads, t->ref_base, t->chrom, t->n, c->indiv, c->haploid, c->threshold, c->theta, t->call,
+                                         t->post_site, t->post_rows, t->post_cap, &t->n_post, t->type, t->ac, NULL, t->denovo);
+  const void *ptr[MAX_SAMPLES];
+  for (int i = 0; i < c->indiv; i++)
+    ptr[i] = t->recs + (size_t) i * TILE * 16;
+  const size_t left = (size_t) t->p0 < c->gsize ? c->gsize - t->p0 : 0;
+  t->n = 0;
+  return pecall_dev_call_records (c->pc, ptr, t->n_recs, c->indiv, t->p0, (uint32_t) TILE, c->genome + (left ? t->p0 : 0), (uint32_t) (left < TILE ? left : TILE),
+                                  t->chrom_slot, &t->n, t->col_slot, c->haploid, c->threshold, c->theta, t->call, t->post_site, t->post_rows, t->post_cap, &t->n_post,
+                                  t->type, t->ac, NULL, t->denovo);
+}
+
+/* behind pecall_dev_call_records: the columns' contig, position and reference letter from their slots (what merge_columns fills on
+   the host path), and the variant columns' reads for the rows of <outfile>.piles.gz */
+static void
+device_merge_columns (consumer_t * c, tile_t * t)
+{
+  long nv = 0;
+  for (long col = 0; col < t->n; col++)
+    {
+      const unsigned int lowest = t->p0 + t->col_slot[col];
+      const int which = find_chrom (c->frag_pos, 0, c->no_contigs - 1, c->start_chrom, lowest);
+      const char ref = lowest < c->gsize ? c->genome[lowest] : '\0';
+      t->ref_char[col] = ref;
+      (void) gen_to_int (ref);
+      t->contig[col] = which;
+      t->pos[col] = 1 + lowest - c->frag_pos[which - 1];
+      if (t->type[col] > 0)
+        {
+          t->vrow[col] = (uint32_t) nv;
+          t->vlist[nv++] = (uint32_t) col;
+        }
+    }
+  if (nv && pecall_dev_sites_gather (c->pc, t->vlist, (uint64_t) nv, t->reads, NULL, NULL))
+    die ("\n pecaller_hip: %s", pecall_dev_last_error (c->pc));
+  c->dev_cols += t->n;
+  c->dev_ranges++;
 }
 
 static void *
@@ -589,8 +708,7 @@ consumer_main (void *arg)
       clock_gettime (CLOCK_MONOTONIC, &a);
       if (c->role == 0)
         {
-          int rc = pecall_dev_call_sites_sparse (c->pc, t->reads, t->ref_base, t->chrom, t->n, c->indiv, c->haploid, c->threshold, c->theta, t->call,
-                                                 t->post_site, t->post_rows, t->post_cap, &t->n_post, t->type, t->ac, NULL, t->denovo);
+          int rc = device_call (c, t);
           if (rc && t->n_post > t->post_cap)
             {
               /* more columns with a posterior that is not 1 than the list holds (one per 8 columns to begin with): a list of the size
@@ -600,11 +718,19 @@ consumer_main (void *arg)
               t->post_rows = (double *) realloc (t->post_rows, t->post_cap * (size_t) c->indiv * sizeof (double));
               if (!t->post_site || !t->post_rows)
                 die ("\n pecaller_hip: out of memory for %s", "the list of posteriors");
-              rc = pecall_dev_call_sites_sparse (c->pc, t->reads, t->ref_base, t->chrom, t->n, c->indiv, c->haploid, c->threshold, c->theta, t->call,
-                                                 t->post_site, t->post_rows, t->post_cap, &t->n_post, t->type, t->ac, NULL, t->denovo);
+              rc = device_call (c, t);
             }
-          if (rc)
+          if (rc == PECALL_RC_UNORDERED && c->device_merge)
+            {
+              /* (the walk's own check comes first: this is the library's word for the same thing) */
+              g_unordered = 1;
+              t->n = 0;
+              t->n_post = 0;
+            }
+          else if (rc)
             die ("\n pecaller_hip: %s", pecall_dev_last_error (c->pc));
+          else if (c->device_merge)
+            device_merge_columns (c, t);
           clock_gettime (CLOCK_MONOTONIC, &b);
           c->sec_dev += (double) (b.tv_sec - a.tv_sec) + 1e-9 * (double) (b.tv_nsec - a.tv_nsec);
           consumer_give (c->next, *t);
@@ -637,8 +763,24 @@ consumer_wait_idle (consumer_t * c)
 }
 
 static void
-tile_alloc (tile_t * t, int indiv)
+tile_alloc (tile_t * t, int indiv, int device_merge)
 {
+  t->recs = NULL;
+  t->n_recs = NULL;
+  t->chrom_slot = NULL;
+  t->col_slot = t->vrow = t->vlist = NULL;
+  t->p0 = 0;
+  if (device_merge)
+    {
+      t->recs = (char *) malloc ((size_t) indiv * TILE * 16);
+      t->n_recs = (uint64_t *) calloc ((size_t) indiv, sizeof (uint64_t));
+      t->chrom_slot = (uint8_t *) malloc (TILE);
+      t->col_slot = (uint32_t *) malloc (TILE * sizeof (uint32_t));
+      t->vrow = (uint32_t *) malloc (TILE * sizeof (uint32_t));
+      t->vlist = (uint32_t *) malloc (TILE * sizeof (uint32_t));
+      if (!t->recs || !t->n_recs || !t->chrom_slot || !t->col_slot || !t->vrow || !t->vlist)
+        die ("\n pecaller_hip: out of memory for %s", "a tile's records");
+    }
   t->reads = (uint16_t *) malloc ((size_t) TILE * indiv * NA * sizeof (uint16_t));
   t->ref_base = (uint8_t *) malloc (TILE);
   t->chrom = (uint8_t *) malloc (TILE);
@@ -954,6 +1096,9 @@ run_once (int argc, char *argv[], int serial_merge)
     if (gr && atol (gr) >= 1)
       GUIDE_RANGE_MIN = (unsigned long long) atol (gr);
   }
+  /* PECALLER_DEVICE_MERGE=1: the columns of a range are made on the device from the streams' records (pecall_dev_call_records) -- where
+     the streams are walked a range at a time: not with a guide file, not with the serial merge */
+  const int device_merge = !guide_file && !serial_merge && getenv ("PECALLER_DEVICE_MERGE") && atoi (getenv ("PECALLER_DEVICE_MERGE")) == 1;
   tile_pool pool;
   memset (&pool, 0, sizeof pool);
   pthread_mutex_init (&pool.mu, NULL);
@@ -963,11 +1108,16 @@ run_once (int argc, char *argv[], int serial_merge)
   for (int k = 0; k < N_TILES; k++)
     {
       tile_t one;
-      tile_alloc (&one, indiv);
+      tile_alloc (&one, indiv, device_merge);
       tile_t *tt = &one;
-      (void) pecall_dev_pin_host (pc, tt->reads, (uint64_t) TILE * indiv * NA * sizeof (uint16_t));
-      (void) pecall_dev_pin_host (pc, tt->ref_base, (uint64_t) TILE);
-      (void) pecall_dev_pin_host (pc, tt->chrom, (uint64_t) TILE);
+      if (device_merge)
+        (void) pecall_dev_pin_host (pc, tt->recs, (uint64_t) indiv * TILE * 16);        /* (the columns' arrays do not travel then) */
+      else
+        {
+          (void) pecall_dev_pin_host (pc, tt->reads, (uint64_t) TILE * indiv * NA * sizeof (uint16_t));
+          (void) pecall_dev_pin_host (pc, tt->ref_base, (uint64_t) TILE);
+          (void) pecall_dev_pin_host (pc, tt->chrom, (uint64_t) TILE);
+        }
       (void) pecall_dev_pin_host (pc, tt->call, (uint64_t) TILE * indiv);
       /* (the list of posteriors is filled by the library with plain copies: not page-locked, so that it can be re-allocated freely) */
       (void) pecall_dev_pin_host (pc, tt->type, (uint64_t) TILE);
@@ -994,6 +1144,7 @@ run_once (int argc, char *argv[], int serial_merge)
   uint16_t *planes = NULL;
   uint8_t *marks = NULL;
   /* (with a guide file too: its long intervals go through the same merge) */
+  if (!device_merge)
     {
       planes = (uint16_t *) malloc ((size_t) no_files * TILE * NA * sizeof (uint16_t));
       marks = (uint8_t *) malloc ((size_t) MT * TILE);
@@ -1034,6 +1185,12 @@ run_once (int argc, char *argv[], int serial_merge)
   cons.pilefile = pilefile;
   cons.outfile = &outfile;
   cons.outname = argv[4];
+  cons.device_merge = device_merge;
+  cons.genome = genome;
+  cons.gsize = gsize;
+  cons.frag_pos = frag_pos;
+  cons.no_contigs = no_contigs;
+  cons.start_chrom = (no_contigs - 1) / 2 > 0 ? (no_contigs - 1) / 2 : 0;
   rows = cons;
   pthread_mutex_init (&rows.mu, NULL);
   pthread_cond_init (&rows.cv, NULL);
@@ -1130,12 +1287,44 @@ run_once (int argc, char *argv[], int serial_merge)
               mc[k].p0 = p0;
               mc[k].p1 = (unsigned long long) p0 + TILE;
             }
-          run_threads (merge_streams, mc, MT);
+          if (g_unordered)      /* (the library's word on an earlier range, device merge) */
+            {
+              running = 0;
+              t.n = 0;
+              continue;
+            }
+          run_threads (device_merge ? merge_streams_dev : merge_streams, mc, MT);
           if (g_unordered)
             {
               running = 0;      /* (the run is abandoned: what is in flight is finished and closed, run_once returns RC_UNORDERED) */
               t.n = 0;
               continue;
+            }
+          if (device_merge)
+            {
+              /* the positions' chromosome classes, a stretch between two contig boundaries at a time: find_chrom's answer changes at
+                 a contig's last position and the one behind it only */
+              unsigned long long q = p0;
+              const unsigned long long end = (unsigned long long) p0 + TILE;
+              while (q < end)
+                {
+                  const int which = find_chrom (frag_pos, 0, no_contigs - 1, start_chrom, (unsigned int) (q > 0xffffffffull ? 0xffffffffull : q));
+                  unsigned long long stop = end;
+                  for (int w = which - 2; w <= which + 1; w++)
+                    if (w >= -1 && w < no_contigs)
+                      for (unsigned long long b = frag_pos[w]; b <= (unsigned long long) frag_pos[w] + 1; b++)
+                        if (b > q && b < stop)
+                          stop = b;
+                  memset (t.chrom_slot + (q - p0), chrom_type[which], (size_t) (stop - q));
+                  q = stop;
+                }
+              t.p0 = p0;
+              t.n = 0;          /* (known when the device has made the columns: the device thread counts them) */
+              running = 0;
+              for (int i = 0; i < no_files; i++)
+                running += sm[i].cur != 0;
+              tile_done = 1;
+              goto hand_over;
             }
           run_threads (merge_count, mc, MT);
           long ncol = 0;
@@ -1256,6 +1445,7 @@ run_once (int argc, char *argv[], int serial_merge)
           if (lowest > gend && !next_guide_interval (guide_file, contig_names, no_contigs, frag_pos, &gwhich, &lowest, &gend))
             running = 0;
         }
+    hand_over:
       if (tile_done || (size_t) t.n == TILE || (running <= 0 && t.n > 0))
         {
           clock_gettime (CLOCK_MONOTONIC, &tc1);
@@ -1281,6 +1471,7 @@ run_once (int argc, char *argv[], int serial_merge)
   sec_dev = cons.sec_dev;
   sec_text = rows.sec_text;
   tot_cols = rows.tot_cols;
+  tot_bases += (unsigned int) cons.dev_cols;
 
   /* ---- <outfile>.dist, pecaller.c:1077-1140 */
   unsigned int *tot_1x = (unsigned int *) calloc (no_files, sizeof (unsigned int)), *tot_8x = (unsigned int *) calloc (no_files, sizeof (unsigned int));
@@ -1348,6 +1539,8 @@ run_once (int argc, char *argv[], int serial_merge)
     const double sec = (double) (tc1.tv_sec - tstart.tv_sec) + 1e-9 * (double) (tc1.tv_nsec - tstart.tv_nsec);
     printf ("\n pecaller_hip: %ld columns x %d samples merged, called and written in %.3f s (%.3f M columns/s; stream merge %.3f s + %.3f s waiting for the other thread: device calls %.3f s, rows and gz %.3f s) \n",
             tot_cols, indiv, sec, (double) tot_cols / (sec > 0 ? sec : 1) / 1e6, sec_merge, sec_wait, sec_dev, sec_text);
+    if (device_merge && !g_unordered)
+      printf (" pecaller_hip: device merge: %ld columns in %ld ranges\n", cons.dev_cols, cons.dev_ranges);
   }
   for (int i = 0; i < no_files; i++)
     zr_close (&sm[i].f);

@@ -5,6 +5,14 @@ from .pemap import load_library, PemapError
 
 MAX_GEN = 14
 ALLELES = 6
+RC_UNORDERED = 3  # PECALL_RC_UNORDERED
+# a pileup record: the 16 bytes of the pileup file
+RECORD = np.dtype([("pos", "<u4"), ("counts", "<u2", (6,))])
+
+
+class PecallUnordered(PemapError):
+    """a record stream does not ascend strictly or leaves the range (PECALL_RC_UNORDERED); .rc is the return code"""
+    rc = RC_UNORDERED
 
 
 def _p(a):
@@ -32,6 +40,12 @@ class PecallDev:
         L.pecall_dev_sites_collect.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.pecall_dev_pin_host.argtypes = [vp, vp, C.c_uint64]
         L.pecall_dev_unpin_host.argtypes = [vp, vp]
+        u32, u64 = C.c_uint32, C.c_uint64
+        L.pecall_dev_sites_stage_records.argtypes = [vp, vp, vp, i, u32, u32, vp, u32, vp, C.POINTER(C.c_long), vp]
+        L.pecall_dev_sites_gather.argtypes = [vp, vp, u64, vp, vp, vp]
+        L.pecall_dev_sites_merge_ms.argtypes = [vp, vp]
+        L.pecall_dev_call_records.argtypes = [vp, vp, vp, i, u32, u32, vp, u32, vp, C.POINTER(C.c_long), vp,
+                                              i, dbl, dbl, vp, vp, vp, u64, vp, vp, vp, vp, vp]
         self.L = L
         h = vp()
         if L.pecall_dev_create(C.byref(h), device_id):
@@ -110,6 +124,85 @@ class PecallDev:
         self.denovo = np.zeros(n_sites, np.int32)
         self._ck(self.L.pecall_dev_sites_collect(self.h, _p(call), _p(post), _p(typ), _p(ac), _p(npass), _p(self.denovo)))
         return call, post, typ, ac, npass
+
+    def _ck_records(self, rc):
+        if rc == RC_UNORDERED:
+            raise PecallUnordered(self.L.pecall_dev_last_error(self.h).decode())
+        self._ck(rc)
+
+    @staticmethod
+    def _record_args(recs, span, ref_letters, chrom):
+        """recs: per sample an array of records ((n, 16) bytes, RECORD, or anything of 16 bytes a row) -> the arrays (kept alive by
+        the caller), their addresses, their lengths, the letters and the chromosome bytes"""
+        keep = []
+        for r in recs:
+            r = np.ascontiguousarray(r)
+            if r.size and r.nbytes % 16:
+                raise ValueError("a record is 16 bytes")
+            keep.append(r)
+        ptrs = (C.c_void_p * len(keep))(*[r.ctypes.data if r.nbytes else None for r in keep])
+        n = np.array([r.nbytes // 16 for r in keep], np.uint64)
+        if isinstance(ref_letters, str):
+            ref_letters = ref_letters.encode()
+        letters = np.frombuffer(bytes(ref_letters), np.uint8) if not isinstance(ref_letters, np.ndarray) else np.ascontiguousarray(ref_letters).view(np.uint8)
+        cy = None
+        if chrom is not None:
+            cy = np.ascontiguousarray(chrom, np.uint8)
+            if cy.size != span:
+                raise ValueError("chrom has one byte per position of the range")
+        return keep, ptrs, n, letters, cy
+
+    def sites_stage_records(self, recs, p0, span, ref_letters, chrom=None):
+        """columns from the samples' records of [p0, p0 + span) (pecall_dev_sites_stage_records): recs = a list of per-sample record
+        arrays, ref_letters = the reference letters from p0 on (at most span), chrom = per position of the range or None
+        -> n_cols, col_slot [n_cols]; the columns are staged for sites_run / sites_collect / sites_gather"""
+        keep, ptrs, n, letters, cy = self._record_args(recs, span, ref_letters, chrom)
+        col_slot = np.zeros(max(int(span), 1), np.uint32)
+        n_cols = C.c_long(0)
+        rc = self.L.pecall_dev_sites_stage_records(self.h, C.addressof(ptrs), _p(n), len(keep), int(p0), int(span), _p(letters) if letters.size else None,
+                                                   letters.size, _p(cy), C.byref(n_cols), _p(col_slot))
+        self._ck_records(rc)
+        self._sshape = (n_cols.value, len(keep))
+        return n_cols.value, col_slot[:n_cols.value]
+
+    def sites_gather(self, cols=None):
+        """the staged columns (all, or those listed) -> reads [n][indiv][6] u16, ref [n] u8, chrom [n] u8"""
+        n_sites, indiv = self._sshape
+        c = None if cols is None else np.ascontiguousarray(cols, np.uint32)
+        n = n_sites if c is None else c.size
+        reads = np.zeros((n, indiv, ALLELES), np.uint16)
+        ref = np.zeros(n, np.uint8)
+        cy = np.zeros(n, np.uint8)
+        if n:
+            self._ck(self.L.pecall_dev_sites_gather(self.h, _p(c), n, _p(reads), _p(ref), _p(cy)))
+        return reads, ref, cy
+
+    def sites_merge_ms(self):
+        """kernel times of the last sites_stage_records in ms: mark, scan, tile"""
+        ms = np.zeros(3, np.float32)
+        self._ck(self.L.pecall_dev_sites_merge_ms(self.h, _p(ms)))
+        return ms
+
+    def call_records(self, recs, p0, span, ref_letters, threshold=0.95, theta=0.001, haploid=False, chrom=None, cap=None):
+        """sites_stage_records and the caller in one call (pecall_dev_call_records)
+        -> call, (post_site, post_rows), site_type, allele_count, n_pass as call_sites_sparse returns them, for the n_cols columns, and col_slot"""
+        keep, ptrs, n, letters, cy = self._record_args(recs, span, ref_letters, chrom)
+        indiv = len(keep)
+        call, _, typ, ac, npass, den = self.out_arrays(max(int(span), 1), indiv, posterior=False)
+        cap = int(cap) if cap is not None else max(1024, int(span) // 8)
+        site, rows = np.empty(cap, np.uint32), np.empty((cap, indiv), np.float64)
+        col_slot = np.zeros(max(int(span), 1), np.uint32)
+        n_cols, n_post = C.c_long(0), C.c_uint64(0)
+        self.sparse_needed = 0
+        rc = self.L.pecall_dev_call_records(self.h, C.addressof(ptrs), _p(n), indiv, int(p0), int(span), _p(letters) if letters.size else None, letters.size, _p(cy),
+                                            C.byref(n_cols), _p(col_slot), int(haploid), float(threshold), float(theta), _p(call), _p(site), _p(rows), cap,
+                                            C.byref(n_post), _p(typ), _p(ac), _p(npass), _p(den))
+        self.sparse_needed = int(n_post.value)
+        self._ck_records(rc)
+        m = n_cols.value
+        self._sshape = (m, indiv)
+        self.denovo = den[:m]
+        return call[:m], (site[:n_post.value], rows[:n_post.value]), typ[:m], ac[:m], npass[:m], col_slot[:m]
 
     def pin_host(self, a):
         self._ck(self.L.pecall_dev_pin_host(self.h, a.ctypes.data, a.nbytes))

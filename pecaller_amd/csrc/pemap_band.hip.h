@@ -42,6 +42,22 @@
 // column) is the FIRST cell lane q + 1 computes in the same step -- it crosses after that cell, before this lane's last one.
 // A quarter of the chain per wave, four times the waves (~4 per SIMD), 70 registers instead of 256.  The arithmetic of a cell,
 // the order of the last column's scan (rows ascending: lane 0's cells, then lane 1's ...) and the slab's layout are unchanged.
+//
+// When the traceback is the diagonal (DIRS only).  A problem is sent here because the read lies whole on one diagonal with a few
+// mismatches, and its traceback is almost always mm diagonal steps in plane 0 -- which pm_pile_kernel can apply without a recorded
+// walk, as it does for the problems pm_gapless_kernel decides (PM_GAPLESS).  This kernel can tell: diagonal b = 8 q + c is nibble
+// 7 - c of lane q's direction dword in EVERY column, so the OR of a lane's dwords over its columns holds, per diagonal, the OR of
+// the nibbles of all its cells (one instruction per step).  pm_walk_kernel, started in plane k = 0 at (i_b, mm), steps to
+// (i_b - 1, mm - 1) and takes its next plane from bits 0-1 of that cell's nibble (bit 1: plane 2, bit 0: plane 1, neither: plane 0
+// again); in plane 0 it goes on the same way.  So if bits 0-1 are clear in every cell of the start cell's diagonal in columns
+// 1 .. mm - 1, the walk is diagonal steps until i or j reaches 0, and with i_b >= mm it is j: mm diagonal steps, the last row
+// >= 0, no insertion pending -- exactly what PM_GAPLESS promises.  (With i_b < mm the diagonal meets the top border first and the
+// walk ends early with read bases left over: not flagged.)  With i_b >= mm every cell of the diagonal in columns 1 .. mm lies
+// inside the matrix (rows 1 .. nn), so the OR holds no bits of cells computed outside it; it also covers column mm's own cell,
+// whose bits 0-1 name the start plane and are clear when that is plane 0.  The lane whose cell takes the lead in the last
+// column's scan notes "bits 0-1 of my diagonal's OR are clear" in bit 2 of k_b, which travels down the quad with the plane number;
+// lane 3 sets PM_GAPLESS beside PM_BANDED iff that bit is set (which implies plane 0) and i_b >= mm.  The test can only err
+// towards walking: a flagged alignment's walk is the diagonal.
 #pragma once
 
 // PM_BAND_K, PM_BAND_W = 21 + 2 K + 1 and the mismatch bound PM_BAND_MAXX_ are defined beside pm_gapless_kernel (pemap_sw.hip.h)
@@ -121,7 +137,8 @@ template < bool DIRS > __global__ __launch_bounds__ (64, PM_BAND_WAVES_PER_EU) v
           E2[c] = ex ? pm_max (0.0 - PM_GO, -PM_GO - PM_GE) : PM_NEGBIG;
         }
       double bst = pm_border (mm > 0 ? mm : 1);        // S[0][0][mm], pemapper.c:1701-1703
-      int k_b = 0, i_b = 0;
+      int k_b = 0, i_b = 0;             // (k_b: the plane in bits 0-1, bit 2 = the start cell's diagonal never leaves plane 0: see the head)
+      uint32_t dw_or = 0u;              // OR of this lane's direction dwords over its columns
       double U_last = PM_NEGBIG;        // S1 below this lane's last cell of the column it finished last
       const int mm_max = pm_wave_max (mm);
       // (columns 4 g .. 4 g + 3 of a problem's slab = one 64-byte line: lane q stores column 4 g + q.  A problem whose read ended
@@ -235,6 +252,8 @@ template < bool DIRS > __global__ __launch_bounds__ (64, PM_BAND_WAVES_PER_EU) v
                 }
               cell (7, q == 3 ? PM_NEGBIG : e2_in);
               U_last = U;
+              if (DIRS)
+                dw_or |= dw;
               if (j == mm)
                 {
                   // The scan of the last column (pemapper.c:1724-1741: rows ascending, planes 0, 1, 2, strict '>'), continued from
@@ -260,6 +279,8 @@ template < bool DIRS > __global__ __launch_bounds__ (64, PM_BAND_WAVES_PER_EU) v
                     {
                       const uint32_t nib = (dw >> (4 * (7 - c_w))) & 0xFu;
                       k_b = (nib & 2u) ? 2 : (int) (nib & 1u);
+                      if (DIRS && ((dw_or >> (4 * (7 - c_w))) & 3u) == 0u)
+                        k_b = 4;
                       i_b = j + 8 * q + c_w - K;
                     }
                 }
@@ -281,7 +302,7 @@ template < bool DIRS > __global__ __launch_bounds__ (64, PM_BAND_WAVES_PER_EU) v
       if (valid && q == 3)
         {
           h.score[o] = bst;
-          h.stk[o] = (uint8_t) (k_b | PM_BANDED);
+          h.stk[o] = (uint8_t) ((k_b & 3) | PM_BANDED | (((k_b & 4) && i_b >= mm) ? PM_GAPLESS : 0));
           h.sti[o] = (int16_t) i_b;
         }
       unsigned long long cells = (valid && q == 0) ? (unsigned long long) mm * PM_BAND_W : 0ull;

@@ -53,6 +53,7 @@ struct PmChunkSet
 {
   PmHits hits = {};
   uint32_t *wins = nullptr, *dirbuf = nullptr;
+  uint32_t *walks = nullptr;    // places in `wins` of the alignments pm_walk_kernel follows
   uint32_t *tasks_s = nullptr, *tasks_m = nullptr;      // each in thirds: all problems, those left to the DP, those left to the banded DP
   unsigned long long *path = nullptr;   // recorded traceback steps per winning alignment
   uint16_t *nsteps = nullptr;
@@ -374,6 +375,7 @@ static void free_work (pemap_dev * d)
     {
       free_hits (s.hits);
       dev_free (s.wins);
+      dev_free (s.walks);
       dev_free (s.tasks_s);
       dev_free (s.tasks_m);
     }
@@ -866,6 +868,7 @@ static int ensure_work (pemap_dev * d, int n_ends)
         {
           TRY (alloc_hits (d, s.hits, n_ends));
           TRY (dev_alloc (d, &s.wins, (size_t) n_ends));
+          TRY (dev_alloc (d, &s.walks, (size_t) n_ends));
           TRY (dev_alloc (d, &s.tasks_s, (size_t) n_ends * 3));       // second third: the problems left to the DP, last third: to the banded DP
           TRY (dev_alloc (d, &s.tasks_m, nh * 3));
         }
@@ -1252,8 +1255,8 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
     hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, false >), dim3 (d->sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H,
                         tasks_m, &ctr->n_tasks_m, ctr, dirbuf, dump_slab, c.tstride, c.L, swprio, &ctr->sw_next[1]);
   hipEventRecord (ev[5], d->stream);
-  hipLaunchKernelGGL (pm_select_kernel, dim3 ((c.b.n + 63) / 64), dim3 (64), 0, d->stream, c.b, c.prm, H, d->d_redo, wins, ctr,
-                      m1, m2, mt);
+  hipLaunchKernelGGL (pm_select_kernel, dim3 ((c.b.n + 63) / 64), dim3 (64), 0, d->stream, c.b, c.prm, H, d->d_redo, wins, S.walks,
+                      ctr, m1, m2, mt);
   hipEventRecord (ev[6], d->stream);
   hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, true >), dim3 (d->sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H,
                       d->d_redo, &ctr->n_redo, ctr, dirbuf, dump_slab, c.tstride, c.L, swprio, &ctr->sw_next[2]);
@@ -1270,7 +1273,7 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
   hipStream_t ws = d->stream;
   unsigned long long *path = S.path;
   uint16_t *nsteps = S.nsteps;
-  hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_walk_kernel < W, LPA >), dim3 (wgrid), dim3 (64), 0, ws, c.b, H, wins, ctr, d->d_cur,
+  hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_walk_kernel < W, LPA >), dim3 (wgrid), dim3 (64), 0, ws, c.b, H, wins, S.walks, ctr, d->d_cur,
                       dirbuf, c.tstride, pile_of (d), d->d_ins_log, d->ins_cap, path, d->path_words, nsteps);
   {
     // one wave per winning alignment applies the recorded steps to the pileup
@@ -1329,6 +1332,7 @@ static int absorb_run (pemap_dev * d)
       t.n_slots += c.n_slots;
       t.n_redo += c.n_redo;
       t.n_wins += c.n_wins;
+      t.n_walks += c.n_walks;
       t.positions += c.positions + hc[k].positions;
       t.cells_score += c.cells_score;
       t.cells_dirs += c.cells_dirs;
@@ -2070,6 +2074,7 @@ extern "C" int pemap_dev_run_stats (pemap_dev * d, uint64_t * s, float *t)
       s[13] = (uint64_t) c.n_band[0] + c.n_band[1];
       s[14] = c.cells_band;
       s[15] = d->last_big2;
+      s[16] = c.n_walks;
     }
   if (t)
     memcpy (t, d->last_ms, sizeof (d->last_ms));

@@ -109,6 +109,7 @@ struct PmCounters
   unsigned int n_band[2];          // problems left to the banded DP (pm_band_kernel): single-hit ends, multi-hit ends
   unsigned int band_next[2];       // their work counters
   unsigned long long cells_band;   // band cells computed
+  unsigned int n_walks;            // of n_wins, the alignments pm_walk_kernel follows (the others are known to be plain diagonals)
 };
 
 // insertion log cursor: survives runs until the host drains the log

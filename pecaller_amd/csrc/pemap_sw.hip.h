@@ -942,8 +942,8 @@ __device__ int pm_single_select (const double *sc, int n, int len, double min_al
   return 7;                     // NON_NO
 }
 
-__global__ __launch_bounds__ (64) void pm_select_kernel (PmBatch b, PmParams prm, PmHits h, uint32_t * redo, uint32_t * wins, PmCounters * ctr, uint32_t * m1,
-                                  uint32_t * m2, int *mtype)
+__global__ __launch_bounds__ (64) void pm_select_kernel (PmBatch b, PmParams prm, PmHits h, uint32_t * redo, uint32_t * wins, uint32_t * walks,
+                                  PmCounters * ctr, uint32_t * m1, uint32_t * m2, int *mtype)
 {
   int it = blockIdx.x * blockDim.x + threadIdx.x;
   if (it >= b.n)
@@ -1084,14 +1084,19 @@ __global__ __launch_bounds__ (64) void pm_select_kernel (PmBatch b, PmParams prm
         r2 = r;
       else
         r1 = r;
-      if (h.slot[e] < 0 && !(h.stk[o] & PM_GAPLESS))
+      const bool gapless = (h.stk[o] & PM_GAPLESS) != 0;
+      if (h.slot[e] < 0 && !gapless)
         {
           // winner of a multi-hit end (not decided by the gapless rule, whose traceback needs no nibbles): give it a slab
           // and have it scored again with direction nibbles
           h.slot[e] = (int) atomicAdd (&ctr->n_slots, 1u);
           redo[atomicAdd (&ctr->n_redo, 1u)] = (uint32_t) o;
         }
-      wins[atomicAdd (&ctr->n_wins, 1u)] = (uint32_t) o;
+      const unsigned w = atomicAdd (&ctr->n_wins, 1u);
+      wins[w] = (uint32_t) o;
+      // the winners pm_walk_kernel has to follow cell by cell (the ones sent to redo among them): the rest are mm diagonal steps
+      if (!gapless)
+        walks[atomicAdd (&ctr->n_walks, 1u)] = w;
     }
   m1[it] = r1;
   if (m2)
@@ -1100,8 +1105,9 @@ __global__ __launch_bounds__ (64) void pm_select_kernel (PmBatch b, PmParams prm
 }
 
 // ============================================================================================================
-// K5: traceback + pileup (smith_waterman_backtrack, pemapper.c:1752-1965).  One lane per winning alignment walks the
-// nibbles of its slab from the start cell to the first row or column.  Pileup counters are u32 in HBM updated with
+// K5: traceback + pileup (smith_waterman_backtrack, pemapper.c:1752-1965).  One lane per winning alignment that is not known
+// to be a plain diagonal (pm_select_kernel's list `walks`) walks the nibbles of its slab from the start cell to the first row
+// or column.  Pileup counters are u32 in HBM updated with
 // no-return atomics (the reference's u16 counters wrap; the fetch truncates, which is the same arithmetic).
 // Insertions go to a byte log through an atomic cursor.
 // ============================================================================================================
@@ -1131,17 +1137,21 @@ __device__ __forceinline__ void pm_log_insertion (uint8_t * ins_log, unsigned in
 // they did not fit, every step refetched its lines and the kernel ran at the HBM limit for random 64-byte lines.
 #define PM_PATH_WORDS(L) ((((2 * (L) + 21 + 31) / 32) + 1) & ~1)
 
-template < int W, int PM_LPA > __global__ __launch_bounds__ (64) void pm_walk_kernel (PmBatch b, PmHits h, const uint32_t * wins, PmCounters * ctr,
+template < int W, int PM_LPA > __global__ __launch_bounds__ (64) void pm_walk_kernel (PmBatch b, PmHits h, const uint32_t * wins, const uint32_t * walks, PmCounters * ctr,
                                                                            PmInsCursor * cur, const uint32_t * dirbuf, int tstride,
                                                                            PmPile counts, uint8_t * ins_log, unsigned ins_cap,
                                                                            unsigned long long *path, int path_words, uint16_t * n_steps)
 {
   constexpr int DW = PmSwGeom < W >::DW;
-  const unsigned n_wins = ctr->n_wins;
+  const unsigned n_walks = ctr->n_walks;
   const size_t slab_dwords = (size_t) PM_LPA * tstride * DW;
   unsigned long long incs = 0, nins = 0;
-  for (unsigned w = blockIdx.x * blockDim.x + threadIdx.x; w < n_wins; w += gridDim.x * blockDim.x)
+  // (the list holds only winners without PM_GAPLESS -- decided by pm_gapless_kernel, or flagged by pm_band_kernel: mm diagonal steps
+  // from (plane 0, row i, column mm), which pm_pile_kernel knows -- so the walkers are dense in their waves; path and n_steps stay
+  // indexed by the winner's place w in `wins`)
+  for (unsigned x = blockIdx.x * blockDim.x + threadIdx.x; x < n_walks; x += gridDim.x * blockDim.x)
     {
+      const unsigned w = walks[x];
       const size_t o = wins[w];
       const int end = (int) (o / PM_MAX_HITS);
       int mm;
@@ -1152,12 +1162,9 @@ template < int W, int PM_LPA > __global__ __launch_bounds__ (64) void pm_walk_ke
       const int pad = PM_LPA * W - mm;
       int k = h.stk[o], i = h.sti[o], j = mm;
       const bool banded = (k & 8) != 0;          // PM_BANDED: the slab holds pm_band_kernel's column-major nibbles
-      if (banded)
-        k &= 3;
+      k &= 3;
       int i1 = 0, ins_len = 0;
       unsigned long long *pw = path + (size_t) w * path_words;
-      if (k & PM_GAPLESS)
-        continue;               // decided by pm_gapless_kernel: mm diagonal steps from (plane 0, row i, column mm), which pm_pile_kernel knows
       unsigned long long acc = 0;
       int ns = 0;
       while (i > 0 && j > 0)

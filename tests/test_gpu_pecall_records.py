@@ -199,10 +199,16 @@ def dense(n, indiv, sparse):
     return p
 
 
-@pytest.mark.parametrize("tag", ["pecall_sites", "pecall_wide", "pecall_ped"])
-@pytest.mark.parametrize("split", [None, 1024])
-def test_call_records_end_to_end(tag, split):
+# (the last case: chunks of 256 columns, the lower clamp, so that the resident seam runs the fixture's columns as 24 chunks)
+E2E = [pytest.param(tag, split, None, id="%s-%s" % (split, tag)) for split in (None, 1024) for tag in ("pecall_sites", "pecall_wide", "pecall_ped")]
+E2E.append(pytest.param("pecall_sites", None, 8, id="None-pecall_sites-chunks_of_256"))
+
+
+@pytest.mark.parametrize("tag,split,chunk_log2", E2E)
+def test_call_records_end_to_end(tag, split, chunk_log2, monkeypatch):
     from pecaller_amd.pecall import PecallDev
+    if chunk_log2 is not None:
+        monkeypatch.setenv("PECALL_CHUNK_LOG2", str(chunk_log2))
     f = fx.load(tag)
     _, seqs = refio.read_fasta(os.path.join(fx.GOLD, "g1.fa.gz"))
     seq = np.concatenate(seqs)

@@ -405,3 +405,115 @@ def test_gpu_site_caller_sparse_posteriors():
     # and the object still works
     check(f["reads"][:500], f["dom"][:500])
     dev.close()
+
+
+def _chunked_columns(n, n_sites, seed, deep_ranges):
+    """test_gpu_site_caller_deep_columns's columns with samples 0 and 1 at Poisson(4) depth, 15 % variant columns and the deep samples
+    (1,500 to 12,000 reads, one in ten) only in the columns of deep_ranges"""
+    rng = np.random.default_rng(seed)
+    dom = rng.integers(0, 4, n_sites).astype(np.uint8)
+    deep_ok = np.zeros(n_sites, bool)
+    for a, b in deep_ranges:
+        deep_ok[a:b] = True
+    lam = np.full(n, 30.0)
+    lam[:2] = 4.0
+    depth = np.where((rng.random((n_sites, n)) < 0.1) & deep_ok[:, None], rng.integers(1500, 12000, (n_sites, n)), rng.poisson(lam, (n_sites, n)))
+    err = rng.binomial(depth, 0.004)
+    reads = np.zeros((n_sites, n, 6), np.int64)
+    idx = np.arange(n_sites)
+    is_var = rng.random(n_sites) < 0.15
+    alt = (dom + rng.integers(1, 4, n_sites)) % 4
+    for i in range(n):
+        dose = np.where(is_var, rng.binomial(2, 0.3, n_sites), 0)
+        good = depth[:, i] - err[:, i]
+        ar = rng.binomial(good, dose / 2.0)
+        reads[idx, i, dom] += good - ar
+        reads[idx, i, alt] += ar
+        reads[idx, i, rng.integers(0, 4, n_sites)] += err[:, i]
+    return np.minimum(reads, 65535).astype(np.uint16), dom
+
+
+def _chunk_coverage(reads, dom, post, chunk, heavy_min):
+    """per chunk of `chunk` columns: columns with a sample too deep for the head of the ln n! table (pcs_fast_kernel: all six counts
+    + 601 >= 2048) that the early pass does not take, columns with a posterior that is not 1, columns the early pass lists
+    (pcs_heavy_kernel: heavy_min or more samples with three or more reads off the reference base that are an eighth of their depth)"""
+    r = reads.astype(np.int64)
+    tot = r.sum(2)
+    ref = r[np.arange(len(dom))[:, None], np.arange(r.shape[1])[None, :], np.minimum(dom, 3)[:, None]]
+    early = (((tot - ref >= 3) & (8 * (tot - ref) >= tot)).sum(1) >= heavy_min) & (dom < 4)
+    deep = (tot + 601 >= 2048).any(1) & (dom < 4)
+    ck = np.arange(len(dom)) // chunk
+    nck = int(ck.max()) + 1
+    return (set(ck[deep].tolist()), set(ck[deep & ~early].tolist()), np.bincount(ck[(post != 1.0).any(1)], minlength=nck),
+            np.bincount(ck[early], minlength=nck))
+
+
+@pytest.mark.gpu
+def test_gpu_site_caller_seam_in_many_chunks(monkeypatch):
+    """PECALL_CHUNK_LOG2=8 (the lower clamp: 256 columns a chunk), so that a few thousand columns are what 2 M are to a run: the staging
+    slots are reused (12 chunks, 3 slots), the chunks' beam searches alternate on their four streams, chunks 2 and 11 alone hold columns
+    too deep for the table's head and get the second pass, the last chunk is short (184 columns), every chunk appends to the sparse
+    list.  Dense and sparse at the seam from pageable and from pinned arrays, and resident, on one object against the oracle; then
+    150 samples in three chunks (pcs_fast_kernel<., 4>, the wide early-list threshold, no second pass)."""
+    from pecaller_amd.pecall import PecallDev
+    monkeypatch.setenv("PECALL_CHUNK_LOG2", "8")
+    dev = PecallDev(0)
+
+    def same(got, exp):
+        assert np.array_equal(got[0], exp[0])
+        assert np.max(np.abs(got[1] - exp[1])) <= 1e-6
+        for a, b in zip(got[2:], exp[2:]):
+            assert np.array_equal(a, b)
+
+    def same_sparse(got, dense):
+        call, (site, rows), typ, ac, npass = got
+        assert np.array_equal(call, dense[0]) and np.array_equal(typ, dense[2]) and np.array_equal(ac, dense[3]) and np.array_equal(npass, dense[4])
+        want = np.nonzero((dense[1] != 1.0).any(axis=1))[0]
+        assert np.array_equal(site, want.astype(np.uint32)), (len(site), len(want))
+        assert np.array_equal(rows, dense[1][want])
+
+    reads, dom = _chunked_columns(24, 3000, 21, [(600, 700), (2900, 3000)])
+    exp = oracle_py.call_sites(reads, dom)
+    deep, deep_left, not1, early = _chunk_coverage(reads, dom, exp[1], 256, 1)
+    # what the case is for, from the input and the oracle's output, so that a changed generator cannot quietly lose it: the second pass on
+    # chunks 2 and 11 alone; rows for the sparse list from every chunk (8 to 21 of them, 172 in all); an early list in every chunk (27 to 43
+    # columns).  The figures are this seed's, bounded as they are.
+    assert deep == {2, 11} and deep_left == {2, 11}
+    assert len(not1) == 12 and not1.min() == 8 and not1.max() == 21 and not1.sum() == 172, not1
+    assert early.min() == 27 and early.max() == 43, early
+    assert exp[4].max() >= 2
+    # pageable arrays: staging slots reused, finish (k - PCS_SLOTS), the second pass on chunks 2 and 11 only
+    dense = [a.copy() for a in dev.call_sites(reads, dom)]
+    same(dense, exp)
+    same_sparse(dev.call_sites_sparse(reads, dom), dense)
+    # inputs and results pinned: copied from and to directly
+    out = dev.out_arrays(len(dom), 24)
+    site, rows = np.zeros(1024, np.uint32), np.zeros((1024, 24))
+    pinned = (reads, dom, site, rows) + out
+    for a in pinned:
+        dev.pin_host(a)
+    got = dev.call_sites(reads, dom, out=out)
+    same(got, exp)
+    assert all(np.array_equal(a, b) for a, b in zip(got, dense))
+    same_sparse(dev.call_sites_sparse(reads, dom, out=out, sparse_out=(site, rows)), dense)
+    for a in pinned:
+        dev.unpin_host(a)
+    # resident: the whole run's early list, sites_run's second pass
+    dev.sites_stage(reads, dom)
+    dev.sites_run()
+    res = dev.sites_collect()
+    same(res, exp)
+    assert all(np.array_equal(a, b) for a, b in zip(res, dense))
+
+    reads, dom = _chunked_columns(150, 700, 21, [])
+    exp = oracle_py.call_sites(reads, dom)
+    deep, _, not1, early = _chunk_coverage(reads, dom, exp[1], 256, 3)
+    # (no second pass; every chunk has rows for the sparse list and an early list at the wide threshold: this seed's figures)
+    assert not deep and not1.tolist() == [11, 13, 9] and early.tolist() == [32, 34, 26], (not1, early)
+    dense = [a.copy() for a in dev.call_sites(reads, dom)]
+    same(dense, exp)
+    same_sparse(dev.call_sites_sparse(reads, dom), dense)
+    dev.sites_stage(reads, dom)
+    dev.sites_run()
+    same(dev.sites_collect(), exp)
+    dev.close()

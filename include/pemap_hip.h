@@ -19,11 +19,18 @@
  *   pemap_dev_stage_reads/_run/_collect   the same call split in three, so that a caller can time the device part
  *   pemap_dev_fetch_pileup           the final genome walk that feeds the pileup / indel writers, pemapper.c:819-866
  *   pemap_dev_summary                total_reads/total_bases/total_dist/no_dists/mate_counts, pemapper.c:144-149, 1238-1265
+ *   pemap_dev_index_share            nothing: the reference's threads share one index in host memory (pemapper.c:411-494); here every
+ *                                    object (one per GPU) holds its own copy, made device to device from the object that loaded or built it
+ *   pemap_dev_absorb                 the reference's ONE all_base_list that every thread increments (pemapper.c:53-58, 156) and its one
+ *                                    set of totals: the objects' counters, insertion lists and summaries summed into one of them
  *   pecall_dev_*                     fill_sample_like and its callers, pecaller.c:2448-2507 (see below)
  *
  * Threading: calls on different pemap_dev objects may run concurrently from different host threads; calls on one
  * object must be serialised by the caller (the reference serialises a batch behind its own mutex, pemapper.c:661),
  * except pemap_dev_submit_batch / _wait_batch / _map_batch, which several host threads may call on one object.
+ * pemap_dev_index_share and pemap_dev_absorb are calls on BOTH their objects, with one relaxation: index_share only reads its
+ * source, so several index_share calls from one source to different destinations may run side by side.  Calls on disjoint
+ * pairs of objects may run concurrently.
  * Ownership: the caller owns every host buffer and may reuse it as soon as a call returns; the object owns all
  * device memory.
  */
@@ -78,6 +85,13 @@ int pemap_dev_build_index_resident (pemap_dev * dev, const void *d_genome, uint6
  * from the rank that loaded or built the index) can fill them, then pemap_dev_index_commit(). */
 int pemap_dev_index_alloc (pemap_dev * dev, uint64_t n_mers, uint64_t genome_size, int n_contigs, int idepth);
 int pemap_dev_index_commit (pemap_dev * dev);
+
+/* Several objects in one process (one per GPU, or several on one GPU as a rehearsal): dst receives a copy of src's committed
+ * index -- pemap_dev_index_alloc with src's sizes, buffers 0..3 (pemap_dev_buffer) copied device to device on dst's stream in
+ * pieces of at most 1 GiB (hipMemcpyPeerAsync: no peer access needs enabling; a plain device copy when both sit on one GPU), then
+ * pemap_dev_index_commit, so dst builds its look-up replicas or not by its own setting.  src is only read.  Fails when src has no
+ * committed index or dst == src. */
+int pemap_dev_index_share (pemap_dev * dst, pemap_dev * src);
 
 /* Look-up replicas -- an MI355X-side layout with no counterpart in the reference.  The look-ups of a read-end
  * (2 x segments x 49 buckets, fill_mers / get_mers, pemapper.c:1969-2003, 2158-2165) cost one 64-byte HBM request each
@@ -166,6 +180,15 @@ int pemap_dev_fetch_pileup (pemap_dev * dev, uint16_t * counts, pemap_ins_cb cb,
 int pemap_dev_fetch_records (pemap_dev * dev, uint64_t first, uint64_t count, void *out, uint64_t out_capacity,
                              uint64_t * n_records);
 int pemap_dev_reset_pileup (pemap_dev * dev);
+/* The end of a run on several objects: afterwards dst is what it would be had it mapped src's batches as well, and src is as
+ * after pemap_dev_reset_pileup.  Every 16-bit counter of buffer 4 becomes (dst + src) mod 2^16 -- the arithmetic of the reference's
+ * one shared unsigned short array -- on the device (pm_pile_add_kernel); src's insertion log is appended to dst's; the 13 summary
+ * numbers are added.  Both objects on one device: the kernel reads src's planes in place.  Different devices (or
+ * PEMAP_ABSORB_STAGED=1): src's planes arrive in pieces of PEMAP_ABSORB_CHUNK KiB (default 262144) in two staging buffers on
+ * dst's device, the copy of a piece under the add of the piece before.
+ * Fails, changing nothing, when dst == src, when either object has no index, when the two hold genomes of different size, contig
+ * count or plane size, or when either has a submitted batch that was not waited for. */
+int pemap_dev_absorb (pemap_dev * dst, pemap_dev * src);
 
 /* out13: total_reads, total_bases, total_dist, no_dists, mate_counts[0..8] */
 int pemap_dev_summary (pemap_dev * dev, long *out13);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "pemap_pile_add.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // Index build.  index_genome_whole.c:206-299: a rolling 32-bit 2-bit-per-base register over each contig; 'N' resets
@@ -526,6 +527,26 @@ __global__ __launch_bounds__ (PR_BLOCK) void pile_emit_kernel (PmPile counts, ui
             r.c[k] = c[k];
           out[at] = r;
         }
+    }
+}
+
+// dst[i] = dst[i] + src[i] over n_vec 16-byte vectors of pileup words, every 16-bit counter on its own (pm_add_u16x2): what the
+// reference's one shared unsigned short array would hold had it seen both objects' increments (pemapper.c:53-58, 156).  A stream:
+// two 16-byte loads and one 16-byte store per lane and turn, consecutive lanes on consecutive vectors, grid-stride.  dst and src
+// are 16-byte aligned and do not overlap (two objects' planes, or a staging buffer).
+#define PA_BLOCK 256
+__global__ __launch_bounds__ (PA_BLOCK) void pm_pile_add_kernel (uint4 * __restrict__ dst, const uint4 * __restrict__ src, uint64_t n_vec)
+{
+  const uint64_t step = (uint64_t) gridDim.x * PA_BLOCK;
+  for (uint64_t i = (uint64_t) blockIdx.x * PA_BLOCK + threadIdx.x; i < n_vec; i += step)
+    {
+      const uint4 a = dst[i], b = src[i];
+      uint4 r;
+      r.x = pm_add_u16x2 (a.x, b.x);
+      r.y = pm_add_u16x2 (a.y, b.y);
+      r.z = pm_add_u16x2 (a.z, b.z);
+      r.w = pm_add_u16x2 (a.w, b.w);
+      dst[i] = r;
     }
 }
 

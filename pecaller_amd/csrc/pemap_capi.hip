@@ -95,6 +95,8 @@ struct PmKnobs
   int gapless_blocks_per_cu;
   int band, band_waves_per_cu;  // the banded DP (pm_band_kernel) for the problems it is exact for; its waves per CU
   int tier2_waves;              // persistent waves per CU of the fused seed kernel's second tier (the first tier's big-end list)
+  int absorb_staged;            // pemap_dev_absorb: 1 = through the staging buffers even when both objects sit on one device
+  size_t absorb_chunk;          // bytes of a staging piece (PEMAP_ABSORB_CHUNK is in KiB): a multiple of 256, at least 256
 };
 
 static int env_int (const char *name, int dflt)
@@ -132,6 +134,10 @@ static void read_knobs (PmKnobs & k)
   if (k.gapless_blocks_per_cu == 0) k.gapless_blocks_per_cu = 1;
   k.band_waves_per_cu = env_int ("PEMAP_BAND_WAVES_PER_CU", 16);
   if (k.band_waves_per_cu < 1) k.band_waves_per_cu = 1;
+  k.absorb_staged = env_int ("PEMAP_ABSORB_STAGED", 0) ? 1 : 0;
+  const int kib = env_int ("PEMAP_ABSORB_CHUNK", 262144);
+  k.absorb_chunk = kib > 0 ? ((size_t) kib * 1024) & ~(size_t) 255 : 0;
+  if (k.absorb_chunk < 256) k.absorb_chunk = 256;
 }
 
 struct pemap_dev
@@ -1718,6 +1724,8 @@ bool pm_host_pin_range (const void *p, size_t bytes, hipStream_t copy_stream)
       }
     else
       i++;
+  // (hipHostRegisterDefault is "mapped and portable" in HIP: the range serves the copies of every device's objects, not only the
+  // registering one's)
   if (hipHostRegister (lo, (size_t) (hi - lo), hipHostRegisterDefault) != hipSuccess)
     {
       (void) hipGetLastError ();
@@ -2137,6 +2145,132 @@ extern "C" int pemap_dev_reset_pileup (pemap_dev * d)
   HIPCHK (d, hipMemset (d->d_cur, 0, sizeof (PmInsCursor)));
   d->h_ins.clear ();
   memset (d->summary, 0, sizeof (d->summary));
+  return 0;
+}
+
+// ---- several objects in one process: the index handed on, the pileups summed -----------------------------------------------
+// dst receives a copy of src's committed index: index_alloc with src's sizes, the four arrays device to device on dst's stream,
+// index_commit (dst builds its look-up replicas, or not, by its own setting).  src is only read.
+extern "C" int pemap_dev_index_share (pemap_dev * dst, pemap_dev * src)
+{
+  if (!dst || !src || dst == src)
+    return fail (dst, "index_share: the source and the destination are the same object");
+  if (!src->index_ready)
+    return fail (dst, "index_share: the source object has no committed index");
+  TRY (pemap_dev_index_alloc (dst, src->n_mers, src->gsize, src->n_contigs, src->idepth));
+  const size_t piece = (size_t) 1 << 30;
+  for (int which = 0; which < 4; which++)
+    {
+      void *to = nullptr, *from = nullptr;
+      uint64_t nb = 0, nb_src = 0;
+      TRY (pemap_dev_buffer (dst, which, &to, &nb));
+      if (pemap_dev_buffer (src, which, &from, &nb_src) || nb_src != nb)
+        return fail (dst, "index_share: buffer %d of the source does not match", which);
+      // (hipMemcpyPeerAsync needs no peer access enabled, and is a plain device copy when both objects sit on one GPU)
+      for (uint64_t o = 0; o < nb; o += piece)
+        HIPCHK (dst, hipMemcpyPeerAsync ((char *) to + o, dst->device, (const char *) from + o, src->device, nb - o < piece ? nb - o : piece, dst->stream));
+    }
+  HIPCHK (dst, hipStreamSynchronize (dst->stream));
+  return pemap_dev_index_commit (dst);
+}
+
+static bool ring_busy (pemap_dev * d)
+{
+  std::lock_guard < std::mutex > lk (d->mu);
+  for (int i = 0; i < PM_RING; i++)
+    if (d->ring[i].active)
+      return true;
+  return false;
+}
+
+// the staged way's temporaries (on dst's device), released on every return
+struct PmAbsorbStage
+{
+  uint32_t *buf[2] = {};
+  hipStream_t copy = nullptr;
+  hipEvent_t ev_copied[2] = {}, ev_added[2] = {};
+  ~PmAbsorbStage ()
+  {
+    for (int b = 0; b < 2; b++)
+      {
+        hipFree (buf[b]);
+        if (ev_copied[b])
+          hipEventDestroy (ev_copied[b]);
+        if (ev_added[b])
+          hipEventDestroy (ev_added[b]);
+      }
+    if (copy)
+      hipStreamDestroy (copy);
+  }
+};
+
+static void launch_pile_add (pemap_dev * d, uint32_t * to, const uint32_t * from, size_t bytes)
+{
+  const uint64_t n_vec = bytes / 16;
+  uint64_t grid = (n_vec + PA_BLOCK - 1) / PA_BLOCK;
+  if (grid > (uint64_t) d->n_cus * 8)
+    grid = (uint64_t) d->n_cus * 8;
+  hipLaunchKernelGGL (pm_pile_add_kernel, dim3 ((unsigned) grid), dim3 (PA_BLOCK), 0, d->stream, (uint4 *) to, (const uint4 *) from, n_vec);
+}
+
+// Afterwards dst is what it would be had it mapped src's batches as well, and src is as after pemap_dev_reset_pileup.
+extern "C" int pemap_dev_absorb (pemap_dev * dst, pemap_dev * src)
+{
+  if (!dst || !src || dst == src)
+    return fail (dst, "absorb: the source and the destination are the same object");
+  if (!dst->index_ready || !src->index_ready)
+    return fail (dst, "absorb: %s object has no index", dst->index_ready ? "the source" : "the destination");
+  if (dst->gsize != src->gsize || dst->n_contigs != src->n_contigs || dst->pile_plane_words != src->pile_plane_words)
+    return fail (dst, "absorb: the objects hold different genomes (%llu letters in %d contigs against %llu in %d)", (unsigned long long) dst->gsize,
+                 dst->n_contigs, (unsigned long long) src->gsize, src->n_contigs);
+  if (ring_busy (dst) || ring_busy (src))
+    return fail (dst, "absorb: %s object has a submitted batch that was not waited for", ring_busy (dst) ? "the destination" : "the source");
+  if (pemap_dev_sync (src) || (hipSetDevice (src->device) != hipSuccess) || drain_ins (src))
+    return fail (dst, "absorb: the source object: %.400s", src->err);
+  TRY (pemap_dev_sync (dst));   // (leaves dst's device current)
+  // ---- counters: every 16-bit counter of the planes becomes (dst + src) mod 2^16, padding included
+  const size_t bytes = 6 * dst->pile_plane_words * sizeof (uint32_t);
+  // (a plane is a whole number of 256-byte blocks, index_alloc: whole 16-byte vectors, no tail)
+  if (dst->pile_plane_words % 64 != 0)
+    return fail (dst, "internal: a pileup plane of %zu words is not a whole number of 256-byte blocks", dst->pile_plane_words);
+  if (dst->device == src->device && !dst->kn.absorb_staged)
+    launch_pile_add (dst, dst->d_counts, src->d_counts, bytes);
+  else
+    {
+      // two staging buffers on dst's device: the copy of piece k + 1 runs under the add of piece k
+      PmAbsorbStage S;
+      const size_t chunk = dst->kn.absorb_chunk < bytes ? dst->kn.absorb_chunk : bytes;
+      HIPCHK (dst, hipStreamCreateWithFlags (&S.copy, hipStreamNonBlocking));
+      for (int b = 0; b < 2; b++)
+        {
+          HIPCHK (dst, hipMalloc ((void **) &S.buf[b], chunk));
+          HIPCHK (dst, hipEventCreateWithFlags (&S.ev_copied[b], hipEventDisableTiming));
+          HIPCHK (dst, hipEventCreateWithFlags (&S.ev_added[b], hipEventDisableTiming));
+        }
+      size_t k = 0;
+      for (size_t o = 0; o < bytes; o += chunk, k++)
+        {
+          const int b = (int) (k & 1);
+          const size_t m = bytes - o < chunk ? bytes - o : chunk;
+          if (k >= 2)
+            HIPCHK (dst, hipStreamWaitEvent (S.copy, S.ev_added[b], 0));        // the add of piece k - 2 has read the buffer
+          HIPCHK (dst, hipMemcpyPeerAsync (S.buf[b], dst->device, (const char *) src->d_counts + o, src->device, m, S.copy));
+          HIPCHK (dst, hipEventRecord (S.ev_copied[b], S.copy));
+          HIPCHK (dst, hipStreamWaitEvent (dst->stream, S.ev_copied[b], 0));
+          launch_pile_add (dst, dst->d_counts + o / sizeof (uint32_t), S.buf[b], m);
+          HIPCHK (dst, hipEventRecord (S.ev_added[b], dst->stream));
+        }
+      HIPCHK (dst, hipStreamSynchronize (S.copy));
+      HIPCHK (dst, hipStreamSynchronize (dst->stream));
+    }
+  HIPCHK (dst, hipStreamSynchronize (dst->stream));
+  HIPCHK (dst, hipGetLastError ());
+  // ---- insertion log (drained above) and summary
+  dst->h_ins.insert (dst->h_ins.end (), src->h_ins.begin (), src->h_ins.end ());
+  for (int i = 0; i < 13; i++)
+    dst->summary[i] += src->summary[i];
+  if (pemap_dev_reset_pileup (src))
+    return fail (dst, "absorb: the source object: %.400s", src->err);
   return 0;
 }
 

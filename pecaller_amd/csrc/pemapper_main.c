@@ -16,6 +16,9 @@
  * GPU maps; <out>.pileup.gz is a sequence of gzip members (it inflates to the reference's bytes); the index arrays are rebuilt on the GPU from <sdx>.seq instead of inflating the 16 GiB <sdx>.idx (the device
  * builder is verified to produce the reference builder's arrays; set PEMAP_INDEX_FROM_FILES=1 to load .idx/.mdx);
  * reads longer than PEMAP_MAX_READ or shorter than PEMAP_MIN_READ are an error instead of undefined behaviour.
+ * PEMAP_DEVICES=a,b,... (1 to 16 device ids; unset: one object on PEMAP_DEVICE, as ever) maps on several device objects: the first
+ * builds the index and hands it on (pemap_dev_index_share), the batches are dealt round robin, and before an output set is written
+ * the objects' pileups are summed into the first (pemap_dev_absorb).  An id may repeat: several objects on one GPU, a rehearsal.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -32,6 +35,8 @@
 #define MAX_FILES 2000
 #define BATCH_PAIRS (1 << 20)
 #define ROW_STRIDE 288
+#define MAX_DEVS 16
+#define MAX_SETS 5              /* batch-buffer sets a file worker owns at most */
 
 static void
 die (const char *msg, const char *arg)
@@ -514,10 +519,16 @@ read_name_list (const char *path, char **names, char **outs)
         the device maps thirty times that.  A worker owns two sets of batch buffers -- one is filled from its file's streams while
         the GPU maps the other (the reference's reader thread fills a free PTHREAD_DATA_NODE while its workers map the others,
         pemapper.c:663-703), pinned once like pd_node_alloc -- and hands its batches to the ONE device object (submit / wait are
-        made for several threads); every file's coordinates go to its own .mfile, pileup counters and summary are sums. */
+        made for several threads); every file's coordinates go to its own .mfile, pileup counters and summary are sums.
+        With several device objects (PEMAP_DEVICES) batch b of the pool goes to object b mod R, and a worker owns min (R + 1, 5) sets:
+        a set is refilled only when its own batch is back, so one file pair keeps several devices busy.  .mfile entries are indexed
+        by read number: which object mapped a batch does not show. */
 typedef struct
 {
-  pemap_dev *dev;
+  pemap_dev *dev;               /* devs[0] */
+  pemap_dev **devs;
+  int n_devs, n_sets;
+  unsigned long n_batches;      /* batches dealt so far (under mu) */
   int paired, trim_s, trim_e, batch_pairs;
   long max_reads;
   char **names1, **names2;
@@ -529,15 +540,27 @@ typedef struct
 typedef struct
 {
   file_pool *P;
-  char *r1s[2], *r2s[2];
-  int *l1s[2], *l2s[2], *mts[2];
+  char *r1s[MAX_SETS], *r2s[MAX_SETS];
+  int *l1s[MAX_SETS], *l2s[MAX_SETS], *mts[MAX_SETS];
 } file_worker;
+
+/* the object the pool's next batch goes to */
+static pemap_dev *
+deal_dev (file_pool * P)
+{
+  if (P->n_devs == 1)
+    return P->dev;
+  pthread_mutex_lock (&P->mu);
+  pemap_dev *d = P->devs[P->n_batches++ % (unsigned long) P->n_devs];
+  pthread_mutex_unlock (&P->mu);
+  return d;
+}
 
 static void
 worker_alloc (file_worker * w, file_pool * P)
 {
   w->P = P;
-  for (int k = 0; k < 2; k++)
+  for (int k = 0; k < P->n_sets; k++)
     {
       w->r1s[k] = (char *) malloc ((size_t) P->batch_pairs * ROW_STRIDE);
       w->r2s[k] = P->paired ? (char *) malloc ((size_t) P->batch_pairs * ROW_STRIDE) : NULL;
@@ -556,11 +579,12 @@ static void
 map_one_file (file_worker * w, int iter)
 {
   file_pool *P = w->P;
-  pemap_dev *dev = P->dev;
-  const int paired = P->paired;
+  const int paired = P->paired, n_sets = P->n_sets;
   char path[4200];
-  int cur_set = 0, have_pending = 0;
-  uint64_t pending = 0;
+  /* per set: the batch in flight from it, if any -- its object and ticket */
+  int cur_set = 0, have_pending[MAX_SETS] = { 0 };
+  uint64_t pending[MAX_SETS] = { 0 };
+  pemap_dev *pending_dev[MAX_SETS] = { NULL };
   char *r1 = w->r1s[0], *r2 = w->r2s[0];
   int *l1 = w->l1s[0], *l2 = w->l2s[0], *mt = w->mts[0];
   char **r1s = w->r1s, **r2s = w->r2s;
@@ -633,10 +657,14 @@ map_one_file (file_worker * w, int iter)
           {
             if (current_read > cap)
               {
-                /* the batch in flight writes into the arrays about to move */
-                if (have_pending)
-                  ck (dev, pemap_dev_wait_batch (dev, pending));
-                have_pending = 0;
+                /* the batches in flight write into the arrays about to move: all of them, oldest first */
+                for (int k = 0; k < n_sets; k++)
+                  {
+                    const int s = (cur_set + k) % n_sets;
+                    if (have_pending[s])
+                      ck (pending_dev[s], pemap_dev_wait_batch (pending_dev[s], pending[s]));
+                    have_pending[s] = 0;
+                  }
                 size_t ncap = cap;
                 while (ncap < current_read)
                   ncap *= 2;
@@ -646,14 +674,17 @@ map_one_file (file_worker * w, int iter)
                 cap = ncap;
               }
             uint64_t ticket = 0;
+            pemap_dev *dev = deal_dev (P);
             ck (dev, pemap_dev_submit_batch (dev, r1, l1, r2, l2, nb, ROW_STRIDE, maps1 + (current_read - (size_t) nb),
                                              paired ? maps2 + (current_read - (size_t) nb) : NULL, mt, &ticket));
-            /* the other set's batch must be back before that set is filled again */
-            if (have_pending)
-              ck (dev, pemap_dev_wait_batch (dev, pending));
-            pending = ticket;
-            have_pending = 1;
-            cur_set ^= 1;
+            pending[cur_set] = ticket;
+            pending_dev[cur_set] = dev;
+            have_pending[cur_set] = 1;
+            /* the next set's own batch must be back before that set is filled again */
+            cur_set = (cur_set + 1) % n_sets;
+            if (have_pending[cur_set])
+              ck (pending_dev[cur_set], pemap_dev_wait_batch (pending_dev[cur_set], pending[cur_set]));
+            have_pending[cur_set] = 0;
             r1 = r1s[cur_set];
             r2 = r2s[cur_set];
             l1 = l1s[cur_set];
@@ -663,11 +694,16 @@ map_one_file (file_worker * w, int iter)
             nb = 0;
           }
       }
-    if (have_pending)
-      ck (dev, pemap_dev_wait_batch (dev, pending));
-    have_pending = 0;
+    for (int k = 0; k < n_sets; k++)
+      {
+        const int s = (cur_set + k) % n_sets;
+        if (have_pending[s])
+          ck (pending_dev[s], pemap_dev_wait_batch (pending_dev[s], pending[s]));
+        have_pending[s] = 0;
+      }
     if (nb > 0)               /* loop left through the length test */
       {
+        pemap_dev *dev = deal_dev (P);
         if (current_read > cap)
           {
             maps1 = (uint32_t *) realloc (maps1, current_read * sizeof (uint32_t));
@@ -724,6 +760,119 @@ file_worker_main (void *arg)
     }
 }
 
+/* ---- several device objects (PEMAP_DEVICES): the index goes out, and the pileups come back, along a binary tree of pairs, a host
+        thread per pair (calls on disjoint pairs of objects may run side by side; index_share only reads its source) */
+typedef struct
+{
+  pemap_dev *dst, *src;
+  int absorb;                   /* 0 pemap_dev_index_share, 1 pemap_dev_absorb */
+} pair_job;
+
+static void *
+pair_main (void *arg)
+{
+  pair_job *j = (pair_job *) arg;
+  ck (j->dst, j->absorb ? pemap_dev_absorb (j->dst, j->src) : pemap_dev_index_share (j->dst, j->src));
+  return NULL;
+}
+
+static void
+run_pairs (pair_job * jobs, int n)
+{
+  pthread_t th[MAX_DEVS];
+  int threaded[MAX_DEVS];
+  for (int k = 1; k < n; k++)
+    threaded[k] = pthread_create (&th[k], NULL, pair_main, &jobs[k]) == 0;
+  if (n > 0)
+    pair_main (&jobs[0]);
+  for (int k = 1; k < n; k++)
+    if (threaded[k])
+      pthread_join (th[k], NULL);
+    else
+      pair_main (&jobs[k]);
+}
+
+static double
+seconds_since (const struct timespec *t0)
+{
+  struct timespec t1;
+  clock_gettime (CLOCK_MONOTONIC, &t1);
+  return (double) (t1.tv_sec - t0->tv_sec) + 1e-9 * (double) (t1.tv_nsec - t0->tv_nsec);
+}
+
+/* doubling rounds: in round r the objects [0, 2^r) each serve one of [2^r, 2^(r+1)) */
+static void
+share_index (pemap_dev ** devs, int R)
+{
+  for (int have = 1; have < R; have *= 2)
+    {
+      pair_job jobs[MAX_DEVS];
+      int n = 0;
+      for (int i = 0; i < have && have + i < R; i++, n++)
+        {
+          jobs[n].dst = devs[have + i];
+          jobs[n].src = devs[i];
+          jobs[n].absorb = 0;
+        }
+      run_pairs (jobs, n);
+    }
+}
+
+/* halving rounds: absorb (devs[i], devs[i + h]) for i < h; afterwards devs[0] holds everything and the others are empty */
+static void
+merge_pileups (pemap_dev ** devs, int R)
+{
+  int h = 1;
+  while (2 * h < R)
+    h *= 2;
+  for (; h >= 1; h /= 2)
+    {
+      pair_job jobs[MAX_DEVS];
+      int n = 0;
+      for (int i = 0; i < h && i + h < R; i++, n++)
+        {
+          jobs[n].dst = devs[i];
+          jobs[n].src = devs[i + h];
+          jobs[n].absorb = 1;
+        }
+      run_pairs (jobs, n);
+      R = R < h ? R : h;
+    }
+}
+
+/* before an output set is written */
+static void
+merge_devices (int on, pemap_dev ** devs, int R)
+{
+  if (!on)
+    return;
+  struct timespec t0;
+  clock_gettime (CLOCK_MONOTONIC, &t0);
+  merge_pileups (devs, R);
+  printf ("\n pemapper_hip: pileups of %d devices merged in %.3f s \n", R, seconds_since (&t0));
+}
+
+/* PEMAP_DEVICES: 1 to MAX_DEVS comma-separated device ids -> their number; anything else is fatal */
+static int
+parse_devices (const char *list, int *ids)
+{
+  int n = 0;
+  const char *p = list;
+  for (;;)
+    {
+      char *end = NULL;
+      const long v = strtol (p, &end, 10);
+      if (end == p || !isdigit ((unsigned char) *p) || v > 1000000 || (*end != ',' && *end != '\0'))
+        die ("\n PEMAP_DEVICES=%s: expected 1 to 16 device ids separated by commas", list);
+      if (n == MAX_DEVS)
+        die ("\n PEMAP_DEVICES=%s: more than 16 entries", list);
+      ids[n++] = (int) v;
+      if (*end == '\0')
+        return n;
+      p = end + 1;
+    }
+}
+
 int
 main (int argc, char *argv[])
 {
@@ -777,6 +926,10 @@ main (int argc, char *argv[])
       printf ("\n Max_threads is not a sensible number (2,10000).  You gave %d \n", max_threads);
       exit (1);
     }
+  int dev_ids[MAX_DEVS], n_devs = 1;
+  const char *dev_list = getenv ("PEMAP_DEVICES");
+  if (dev_list)
+    n_devs = parse_devices (dev_list, dev_ids);
   char **names1 = (char **) calloc (MAX_FILES + 1, sizeof (char *));
   char **names2 = (char **) calloc (MAX_FILES + 1, sizeof (char *));
   char **outs = (char **) calloc (MAX_FILES + 1, sizeof (char *));
@@ -861,13 +1014,27 @@ main (int argc, char *argv[])
   gzclose (reffile);
   c.genome = genome;
 
-  pemap_dev *dev = NULL;
-  const char *devs = getenv ("PEMAP_DEVICE");
-  if (pemap_dev_create (&dev, devs ? atoi (devs) : 0))
+  pemap_dev *devs[MAX_DEVS] = { NULL };
+  if (!dev_list)
     {
-      printf ("\n pemap_hip: %s\n", pemap_dev_last_error (NULL));
-      exit (1);
+      const char *one = getenv ("PEMAP_DEVICE");
+      dev_ids[0] = one ? atoi (one) : 0;
     }
+  for (int k = 0; k < n_devs; k++)
+    {
+      if (pemap_dev_create (&devs[k], dev_ids[k]))
+        {
+          printf ("\n pemap_hip: %s\n", pemap_dev_last_error (NULL));
+          exit (1);
+        }
+      /* the 128 GiB of look-up replicas do not fit twice on one GPU */
+      int twice = 0;
+      for (int j = 0; j < n_devs; j++)
+        twice |= (j != k && dev_ids[j] == dev_ids[k]);
+      if (twice)
+        ck (devs[k], pemap_dev_set_lookup_replicas (devs[k], 0));
+    }
+  pemap_dev *dev = devs[0];
   c.dev = dev;
   {
     long ncpu = sysconf (_SC_NPROCESSORS_ONLN);
@@ -911,7 +1078,18 @@ main (int argc, char *argv[])
     }
   else
     ck (dev, pemap_dev_build_index (dev, genome, c.gsize, contig_len, n_contigs, bis));
-  ck (dev, pemap_dev_set_params (dev, paired, min_dist, max_dist, min_align, bis));
+  if (dev_list)
+    {
+      struct timespec t0;
+      clock_gettime (CLOCK_MONOTONIC, &t0);
+      share_index (devs, n_devs);
+      printf ("\n pemapper_hip: %d devices (ids", n_devs);
+      for (int k = 0; k < n_devs; k++)
+        printf ("%s%d", k ? "," : " ", dev_ids[k]);
+      printf ("): index shared in %.3f s \n", seconds_since (&t0));
+    }
+  for (int k = 0; k < n_devs; k++)
+    ck (devs[k], pemap_dev_set_params (devs[k], paired, min_dist, max_dist, min_align, bis));
 
   if (paired)
     {
@@ -948,6 +1126,9 @@ main (int argc, char *argv[])
   file_pool pool;
   memset (&pool, 0, sizeof pool);
   pool.dev = dev;
+  pool.devs = devs;
+  pool.n_devs = n_devs;
+  pool.n_sets = n_devs > 1 ? (n_devs + 1 < MAX_SETS ? n_devs + 1 : MAX_SETS) : 2;
   pool.paired = paired;
   pool.trim_s = trim_s;
   pool.trim_e = trim_e;
@@ -956,6 +1137,12 @@ main (int argc, char *argv[])
   pool.names2 = names2;
   /* one file at a time: batches of 2^20 pairs; several: 2^18, the device pipeline's own chunk (three batches are in flight at most) */
   pool.batch_pairs = n_workers > 1 ? BATCH_PAIRS / 4 : BATCH_PAIRS;
+  {
+    /* PEMAPPER_BATCH_PAIRS: smaller batches (tests: a small file then spans several batches, buffer sets and device objects) */
+    const char *e = getenv ("PEMAPPER_BATCH_PAIRS");
+    if (e && atoi (e) >= 1 && atoi (e) <= BATCH_PAIRS)
+      pool.batch_pairs = atoi (e);
+  }
   pthread_mutex_init (&pool.mu, NULL);
   file_worker *workers = (file_worker *) calloc ((size_t) n_workers, sizeof (file_worker));
   for (int k = 0; k < n_workers; k++)
@@ -969,6 +1156,7 @@ main (int argc, char *argv[])
         {
           if (iter > 0)
             {
+              merge_devices (dev_list != NULL, devs, n_devs);
               dump_output (&c, basename, pool.tot_pairs);
               pool.tot_pairs = 0;
             }
@@ -1005,7 +1193,9 @@ main (int argc, char *argv[])
         }
       iter = last;
     }
+  merge_devices (dev_list != NULL, devs, n_devs);
   dump_output (&c, basename, pool.tot_pairs);
-  pemap_dev_destroy (dev);
+  for (int k = 0; k < n_devs; k++)
+    pemap_dev_destroy (devs[k]);
   return 0;
 }

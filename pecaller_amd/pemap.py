@@ -22,7 +22,7 @@ SYMBOLS = [
     "pemap_dev_stage_reads", "pemap_dev_run", "pemap_dev_run_slice", "pemap_dev_collect", "pemap_dev_sync",
     "pemap_dev_synth_genome", "pemap_dev_synth_reads", "pemap_dev_synth_reads_indel", "pemap_dev_staged_reads", "pemap_dev_staged_info",
     "pemap_dev_free", "pemap_dev_fetch_pileup", "pemap_dev_fetch_records", "pemap_dev_reset_pileup", "pemap_dev_summary",
-    "pemap_dev_run_stats", "pemap_dev_debug_hits",
+    "pemap_dev_run_stats", "pemap_dev_debug_hits", "pemap_dev_index_share", "pemap_dev_absorb",
     "pecall_dev_create", "pecall_dev_destroy", "pecall_dev_last_error", "pecall_dev_site_like", "pecall_dev_stage",
     "pecall_dev_run", "pecall_dev_collect", "pecall_dev_call_sites", "pecall_dev_call_sites_sparse", "pecall_dev_set_pedigree",
     "pecall_dev_sites_stage", "pecall_dev_sites_run", "pecall_dev_sites_collect", "pecall_dev_pin_host", "pecall_dev_unpin_host",
@@ -85,6 +85,8 @@ def load_library():
         L.pemap_dev_summary.argtypes = [vp, vp]
         L.pemap_dev_run_stats.argtypes = [vp, vp, vp]
         L.pemap_dev_debug_hits.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.pemap_dev_index_share.argtypes = [vp, vp]
+        L.pemap_dev_absorb.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -144,6 +146,11 @@ class PemapDev:
 
     def index_commit(self):
         self._ck(self.L.pemap_dev_index_commit(self.h))
+
+    def index_share(self, src):
+        """this object receives a copy of src's committed index, device to device"""
+        self._ck(self.L.pemap_dev_index_share(self.h, src.h))
+        self.gsize = src.gsize
 
     def set_lookup_replicas(self, n):
         """-1 = when the memory is there (default), 0 = the reference's table only, 8 = required."""
@@ -289,6 +296,10 @@ class PemapDev:
 
     def reset_pileup(self):
         self._ck(self.L.pemap_dev_reset_pileup(self.h))
+
+    def absorb(self, src):
+        """add src's counters (every u16 counter modulo 2^16), insertion list and summary to this object's; src is left reset"""
+        self._ck(self.L.pemap_dev_absorb(self.h, src.h))
 
     def summary(self):
         out = np.zeros(13, np.int64)

@@ -325,6 +325,30 @@ int pecall_dev_call_records (pecall_dev * dev, const void *const *recs, const ui
                              int haploid, double threshold, double theta, int8_t * call, uint32_t * post_site, double *post_rows,
                              uint64_t post_cap, uint64_t * n_post, int8_t * site_type, int32_t * allele_count, int8_t * n_pass,
                              int32_t * denovo);
+/* ---- PECaller: the rows of <outfile>.base.gz made on the device ----
+ * What the host otherwise does behind a call: the per-sample text of every column (emit_rows of pecaller_main.c; in the reference
+ * the gzprintf loop of pecaller.c:1760-1775).  Valid after pecall_dev_call_sites, _call_sites_sparse, _call_records or
+ * pecall_dev_sites_run, for the columns of that call, until the next stage or call: it reads the calls, site types and posteriors
+ * the call left on the device.  A column whose samples all have posterior exactly 1 is the template
+ * "\n<contig>\t<pos>\t<ref>" + "\t<call>\t1" per sample (a call of 14 or more prints 'N'), and comes back as text; a column the
+ * caller skipped (site_type < 0) has no row; a column with some posterior that is not exactly 1 -- the columns
+ * pecall_dev_call_sites_sparse lists -- is a hole: the host formats its row (%g) and inserts it.
+ *   names, name_off[n_contigs + 1]   the contig names one behind the other: name c = names[name_off[c] .. name_off[c + 1]),
+ *                                    at most 1024 bytes each
+ *   contig[], pos[], ref_char[]      per column of the last call: its contig (0 .. n_contigs - 1), the position and the reference
+ *                                    letter its row prints.  9 bytes per column go up (directly from page-locked arrays).
+ *   text[text_cap], *n_text          in column order the rows of every column that is neither skipped nor a hole; each row begins
+ *                                    with '\n' and has no trailing newline (the bytes emit_rows appends).  It arrives in pieces of
+ *                                    16 MB, directly where pecall_dev_pin_host page-locked it, else through a page-locked block.
+ *   hole_site[hole_cap], hole_at[], *n_holes   ascending: the host's row of column hole_site[k] belongs at byte hole_at[k] of text
+ *   kernel_ms3 (may be NULL)         HIP-event durations in ms: length, scan, fill
+ * Fails (non-zero, pecall_dev_last_error says why) when no call's results are resident, for a contig outside [0, n_contigs), for
+ * a position above 2^31 - 1 (the rows print (int) pos as the reference does: no parity is claimed beyond that), and when text_cap
+ * or hole_cap is too small -- then *n_text and *n_holes say what is needed, as pecall_dev_call_sites_sparse does with *n_post. */
+int pecall_dev_sites_base_text (pecall_dev * dev, const char *names, const uint32_t * name_off /* [n_contigs + 1] */ , int n_contigs,
+                                const int32_t * contig, const uint32_t * pos, const char *ref_char /* [columns of the last call] */ ,
+                                char *text, uint64_t text_cap, uint64_t * n_text, uint32_t * hole_site, uint64_t * hole_at,
+                                uint64_t hole_cap, uint64_t * n_holes, float *kernel_ms3 /* may be NULL: length, scan, fill */ );
 /* use_pedfile = y (pecaller.c:376-392, 561-604): parents as sample indices (-1 = not sampled), sex (1 male, 2 female), and each
  * sample's kids in ped-file order: kids of i = kid_list[kid_off[i] .. kid_off[i + 1]).  denovo_rate = argv[11] (<= theta).
  * The configuration prior then carries no_denovo * ln(denovo_rate) (add_denovo, 2396-2445, tables of main 312-374).

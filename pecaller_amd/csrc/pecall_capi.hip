@@ -12,6 +12,7 @@
 #include "pecall_kernels.hip.h"
 #include "pecall_site.hip.h"
 #include "pecall_merge.hip.h"
+#include "pecall_rows.hip.h"
 
 static char g_pc_err[512] = "";
 #define PCS_SLOTS 3             // staging buffers of the seam's pipeline (chunks in flight between the two host copies)
@@ -186,6 +187,35 @@ static void pcm_free (PcmState & g)
       e = nullptr;
 }
 
+// pecall_dev_sites_base_text (pecall_rows.hip.h): the columns' heads and the contig names as they went up; per padded column its length
+// word and its byte offset; the blocks' sums of the scan; the holes; the text; and the page-locked blocks things travel through
+#define PCR_PIECE ((size_t) 16 << 20)   // bytes of text per device-to-host copy
+struct PcrState
+{
+  int32_t *d_contig = nullptr;
+  uint32_t *d_pos = nullptr, *d_name_off = nullptr, *d_hole_site = nullptr;
+  char *d_ref = nullptr, *d_names = nullptr, *d_text = nullptr;
+  unsigned *d_len = nullptr, *d_bsum_holes = nullptr;
+  unsigned long long *d_off = nullptr, *d_bsum_bytes = nullptr, *d_hole_at = nullptr;
+  PcrCtl *d_ctl = nullptr;
+  size_t cap_cols = 0, cap_names = 0, cap_contigs = 0, cap_text = 0;       // cap_cols: padded columns
+  char *h_stage = nullptr;      // [PcrCtl][contig][pos][ref][name offsets][names][hole columns][hole offsets]
+  size_t h_stage_bytes = 0;
+  char *h_text[2] = { };        // PCR_PIECE each: the text's pieces on their way to a target that is not page-locked
+  hipEvent_t ev_piece[2] = { };
+  hipEvent_t ev[6] = { };       // around the length kernel, the scan's first two kernels, its third, the fill kernel
+};
+
+static void pcr_free (PcrState & w)
+{
+  pc_free (w.d_contig, w.d_pos, w.d_name_off, w.d_hole_site, w.d_ref, w.d_names, w.d_text, w.d_len, w.d_bsum_holes, w.d_off, w.d_bsum_bytes, w.d_hole_at, w.d_ctl);
+  pc_host_free (w.h_stage, w.h_text[0], w.h_text[1]);
+  w.cap_cols = w.cap_names = w.cap_contigs = w.cap_text = w.h_stage_bytes = 0;
+  for (hipEvent_t * e : { &w.ev[0], &w.ev[1], &w.ev[2], &w.ev[3], &w.ev[4], &w.ev[5], &w.ev_piece[0], &w.ev_piece[1] })
+    if (*e && hipEventDestroy (*e) == hipSuccess)
+      *e = nullptr;
+}
+
 struct PcsChunk
 {
   hipEvent_t h2d, fast, call, d2h, heavy;       // a chunk's columns in, shortcut kernel done, beam search and what follows it done, results out, early beam search done
@@ -204,6 +234,7 @@ struct pecall_dev
   PcsScratch scratch;
   PcsSparse sp;
   PcmState mg;
+  PcrState rows;
   // pedigree
   int ped_indiv = 0, ped_haploid = 0;
   double denovo_rate = 0;
@@ -212,6 +243,7 @@ struct pecall_dev
   uint16_t h_kid_off[PCS_MAXN + 1] = { }, h_kid_list[2 * PCS_MAXN] = { };
   long staged_sites = 0;
   int staged_indiv = 0;
+  long result_sites = 0;        // columns whose results lie in `cols` (the last call's or run's; 0 once something new is staged)
   // the caller in chunks of chunk_sites columns (pcs_chunk_kernels): the shortcut kernel of chunk k + 1 runs beside the beam search of
   // chunk k, and at the seam (pecall_dev_call_sites) beside the copies of the chunks around them.  Streams and events are made by the
   // first call that needs chunks (pcs_ensure_chunks).
@@ -336,6 +368,7 @@ extern "C" void pecall_dev_destroy (pecall_dev * d)
   pcs_scratch_free (d->scratch);
   pcs_sparse_free (d->sp);
   pcm_free (d->mg);
+  pcr_free (d->rows);
   pc_free (d->d_chunk_ctr, d->d_heavy_ctr);
   pc_host_free (d->h_ctrs);
   for (int i = 0; i < PCS_SLOTS; i++)
@@ -667,6 +700,7 @@ extern "C" int pecall_dev_sites_stage (pecall_dev * d, const uint16_t * reads, c
   PCCHK (d, hipSetDevice (d->device));
   if (n_sites <= 0 || indiv <= 0 || indiv > PCS_MAXN)
     return pc_fail (d, "call_sites: n_sites %ld, indiv %d (1..%d samples per call)", n_sites, indiv, PCS_MAXN);
+  d->result_sites = 0;
   PCTRY (pcs_ensure (d, n_sites, indiv));
   long items = n_sites * indiv;
   PCCHK (d, hipMemcpyAsync (d->cols.d_sreads, reads, items * PCS_NA * sizeof (uint16_t), hipMemcpyHostToDevice, d->stream));
@@ -963,6 +997,7 @@ extern "C" int pecall_dev_sites_run (pecall_dev * d, int haploid, double thresho
   const int indiv = d->staged_indiv;
   if (d->staged_sites <= 0)
     return pc_fail (d, "sites_run: nothing staged");
+  d->result_sites = 0;
   PcsParams P;
   PCTRY (pcs_params (d, indiv, haploid, threshold, theta, P));
   PCTRY (pcs_ensure_chunks (d, d->staged_sites));
@@ -993,6 +1028,7 @@ extern "C" int pecall_dev_sites_run (pecall_dev * d, int haploid, double thresho
     PCCHK (d, hipEventElapsedTime (kernel_ms, d->ev_site[0], d->ev_site[1]));
   if (getenv ("PECALL_LIST_STATS"))
     pcs_list_stats (d, nch, heavy);
+  d->result_sites = d->staged_sites;
   return 0;
 }
 
@@ -1241,6 +1277,7 @@ static int pcs_call_sites_impl (pecall_dev * d, PcsIo io, long n_sites, int indi
     return pc_fail (d, "call_sites: a required pointer is NULL");
   if (io.sparse && (!io.post_site || !io.post_rows || !io.n_post || io.post_cap == 0))
     return pc_fail (d, "call_sites_sparse: the list of posteriors needs post_site, post_rows, a capacity and n_post");
+  d->result_sites = 0;
   if (io.sparse)
     {
       *io.n_post = 0;
@@ -1302,6 +1339,7 @@ static int pcs_call_sites_impl (pecall_dev * d, PcsIo io, long n_sites, int indi
   PCCHK (d, hipStreamSynchronize (d->stream));
   for (int i = 0; i < PCS_CALL_STREAMS; i++)
     PCCHK (d, hipStreamSynchronize (d->stream_call[i]));
+  d->result_sites = n_sites;    // (also where the list below turns out too short: the columns' results are whole)
   if (io.sparse)
     PCTRY (pcs_collect_sparse (d, io, N));
   if (trace)
@@ -1385,7 +1423,7 @@ extern "C" int pecall_dev_sites_stage_records (pecall_dev * d, const void *const
       if (n && !pm_host_pin_lookup (recs[i], (size_t) n * 16))
         staged_bytes += (size_t) n * 16;
     }
-  d->staged_sites = 0;
+  d->staged_sites = d->result_sites = 0;
   const size_t total = (size_t) off[indiv];
   if (total == 0)
     return 0;
@@ -1548,6 +1586,236 @@ extern "C" int pecall_dev_sites_gather (pecall_dev * d, const uint32_t * cols, u
       if (chrom_out)
         memcpy (chrom_out + at, d->mg.h_gather + o_chr, m);
     }
+  return 0;
+}
+
+// ---- the rows of <outfile>.base.gz (pecall_rows.hip.h)
+
+static int pcr_ensure (pecall_dev * d, size_t pad, size_t n_contigs, size_t names_bytes, size_t stage_bytes)
+{
+  PcrState & w = d->rows;
+  if (!w.d_ctl)
+    {
+      for (hipEvent_t & e : w.ev)
+        if (!e)
+          PCCHK (d, hipEventCreate (&e));
+      for (hipEvent_t & e : w.ev_piece)
+        if (!e)
+          PCCHK (d, hipEventCreateWithFlags (&e, hipEventDisableTiming));
+      PCCHK (d, hipMalloc ((void **) &w.d_ctl, sizeof (PcrCtl)));
+    }
+  if (pad > w.cap_cols)
+    {
+      pc_free (w.d_contig, w.d_pos, w.d_ref, w.d_len, w.d_off, w.d_hole_site, w.d_hole_at, w.d_bsum_bytes, w.d_bsum_holes);
+      w.cap_cols = 0;
+      PCCHK (d, hipMalloc ((void **) &w.d_contig, pad * sizeof (int32_t)));
+      PCCHK (d, hipMalloc ((void **) &w.d_pos, pad * sizeof (uint32_t)));
+      PCCHK (d, hipMalloc ((void **) &w.d_ref, pad));
+      PCCHK (d, hipMalloc ((void **) &w.d_len, pad * sizeof (unsigned)));
+      PCCHK (d, hipMalloc ((void **) &w.d_off, pad * sizeof (unsigned long long)));
+      PCCHK (d, hipMalloc ((void **) &w.d_hole_site, pad * sizeof (uint32_t)));
+      PCCHK (d, hipMalloc ((void **) &w.d_hole_at, pad * sizeof (unsigned long long)));
+      PCCHK (d, hipMalloc ((void **) &w.d_bsum_bytes, pad / PCR_SCAN_TILE * sizeof (unsigned long long)));
+      PCCHK (d, hipMalloc ((void **) &w.d_bsum_holes, pad / PCR_SCAN_TILE * sizeof (unsigned)));
+      w.cap_cols = pad;
+    }
+  if (n_contigs + 1 > w.cap_contigs)
+    {
+      pc_free (w.d_name_off);
+      w.cap_contigs = 0;
+      PCCHK (d, hipMalloc ((void **) &w.d_name_off, (n_contigs + 1) * sizeof (uint32_t)));
+      w.cap_contigs = n_contigs + 1;
+    }
+  if (names_bytes + 1 > w.cap_names)
+    {
+      pc_free (w.d_names);
+      w.cap_names = 0;
+      PCCHK (d, hipMalloc ((void **) &w.d_names, names_bytes + 1));
+      w.cap_names = names_bytes + 1;
+    }
+  if (stage_bytes > w.h_stage_bytes)
+    {
+      pc_host_free (w.h_stage);
+      w.h_stage_bytes = 0;
+      PCCHK (d, hipHostMalloc ((void **) &w.h_stage, stage_bytes + stage_bytes / 4, hipHostMallocDefault));
+      w.h_stage_bytes = stage_bytes + stage_bytes / 4;
+    }
+  return 0;
+}
+
+// `bytes` of a per-column array on their way up: from where they lie if the caller page-locked them, else through the staging block
+static int pcr_upload (pecall_dev * d, void *dev, const void *host, char *stage, size_t bytes)
+{
+  if (!pm_host_pin_lookup (host, bytes))
+    {
+      pm_par_memcpy (stage, (const char *) host, bytes);
+      host = stage;
+    }
+  PCCHK (d, hipMemcpyAsync (dev, host, bytes, hipMemcpyHostToDevice, d->stream));
+  return 0;
+}
+
+// the text back, PCR_PIECE at a time on the device-to-host stream, behind event `filled`
+static int pcr_text_back (pecall_dev * d, hipEvent_t filled, char *text, size_t total)
+{
+  PcrState & w = d->rows;
+  PCCHK (d, hipStreamWaitEvent (d->stream_d2h, filled, 0));
+  if (pm_host_pin_lookup (text, total))
+    {
+      for (size_t at = 0; at < total; at += PCR_PIECE)
+        PCCHK (d, hipMemcpyAsync (text + at, w.d_text + at, std::min (PCR_PIECE, total - at), hipMemcpyDeviceToHost, d->stream_d2h));
+      PCCHK (d, hipStreamSynchronize (d->stream_d2h));
+      return 0;
+    }
+  for (char *&h : w.h_text)
+    if (!h)
+      PCCHK (d, hipHostMalloc ((void **) &h, PCR_PIECE, hipHostMallocDefault));
+  // (piece k travels while piece k - 1 is copied out of the other block)
+  const size_t pieces = (total + PCR_PIECE - 1) / PCR_PIECE;
+  for (size_t k = 0; k <= pieces; k++)
+    {
+      if (k < pieces)
+        {
+          PCCHK (d, hipMemcpyAsync (w.h_text[k & 1], w.d_text + k * PCR_PIECE, std::min (PCR_PIECE, total - k * PCR_PIECE), hipMemcpyDeviceToHost, d->stream_d2h));
+          PCCHK (d, hipEventRecord (w.ev_piece[k & 1], d->stream_d2h));
+        }
+      if (k > 0)
+        {
+          const size_t at = (k - 1) * PCR_PIECE;
+          PCCHK (d, hipEventSynchronize (w.ev_piece[(k - 1) & 1]));
+          pm_par_memcpy (text + at, w.h_text[(k - 1) & 1], std::min (PCR_PIECE, total - at));
+        }
+    }
+  return 0;
+}
+
+// Replaces the .base half of the row formatting (emit_rows of pecaller_main.c; the per-sample gzprintf loop of pecaller.c:1760-1775)
+// for the columns whose posteriors are all exactly 1.  The host waits twice: for the text's length and the number of holes (the
+// caller's buffers are checked against them, the device text is sized by it), and for the end.
+extern "C" int pecall_dev_sites_base_text (pecall_dev * d, const char *names, const uint32_t * name_off, int n_contigs, const int32_t * contig, const uint32_t * pos,
+                                           const char *ref_char, char *text, uint64_t text_cap, uint64_t * n_text, uint32_t * hole_site, uint64_t * hole_at,
+                                           uint64_t hole_cap, uint64_t * n_holes, float *kernel_ms3)
+{
+  PCCHK (d, hipSetDevice (d->device));
+  if (n_text)
+    *n_text = 0;
+  if (n_holes)
+    *n_holes = 0;
+  if (kernel_ms3)
+    kernel_ms3[0] = kernel_ms3[1] = kernel_ms3[2] = 0.0f;
+  const long n = d->result_sites;
+  const int N = d->staged_indiv;
+  if (n <= 0)
+    return pc_fail (d, "sites_base_text: no call's results are on the device (call_sites, call_sites_sparse, call_records or sites_run first)");
+  if (!names || !name_off || n_contigs < 1 || !contig || !pos || !ref_char || !n_text || !n_holes)
+    return pc_fail (d, "sites_base_text: names, name_off, at least one contig, contig, pos, ref_char, n_text and n_holes are required");
+  if ((text_cap && !text) || (hole_cap && (!hole_site || !hole_at)))
+    return pc_fail (d, "sites_base_text: a capacity without its array");
+  // ---- the small things, before a kernel turns them into addresses
+  unsigned max_name = 0;
+  for (int c = 0; c < n_contigs; c++)
+    {
+      if (name_off[c + 1] < name_off[c] || name_off[c + 1] - name_off[c] > PCR_MAX_NAME)
+        return pc_fail (d, "sites_base_text: name_off[%d..%d] = %u, %u: the offsets ascend and a name has at most %u bytes", c, c + 1, name_off[c], name_off[c + 1], PCR_MAX_NAME);
+      max_name = std::max (max_name, name_off[c + 1] - name_off[c]);
+    }
+  for (long s = 0; s < n; s++)
+    {
+      if (contig[s] < 0 || contig[s] >= n_contigs)
+        return pc_fail (d, "sites_base_text: contig[%ld] = %d, there are %d contigs", s, contig[s], n_contigs);
+      if (pos[s] > PCR_MAX_POS)
+        return pc_fail (d, "sites_base_text: pos[%ld] = %u is beyond %u (the rows print (int) pos)", s, pos[s], PCR_MAX_POS);
+    }
+  const size_t S = (size_t) n, pad = (S + 1 + PCR_SCAN_TILE - 1) / PCR_SCAN_TILE * PCR_SCAN_TILE, names_bytes = name_off[n_contigs] - name_off[0];
+  const unsigned nb = (unsigned) (pad / PCR_SCAN_TILE);
+  const size_t at_contig = 64, at_pos = at_contig + pcm_up64 (S * 4), at_ref = at_pos + pcm_up64 (S * 4), at_noff = at_ref + pcm_up64 (S),
+    at_names = at_noff + pcm_up64 ((size_t) (n_contigs + 1) * 4), at_hsite = at_names + pcm_up64 (names_bytes + 1), at_hat = at_hsite + pcm_up64 (S * 4),
+    need = at_hat + pcm_up64 (S * 8);
+  PCTRY (pcr_ensure (d, pad, (size_t) n_contigs, names_bytes, need));
+  PcrState & w = d->rows;
+  char *st = w.h_stage;
+  PCTRY (pcr_upload (d, w.d_contig, contig, st + at_contig, S * 4));
+  PCTRY (pcr_upload (d, w.d_pos, pos, st + at_pos, S * 4));
+  PCTRY (pcr_upload (d, w.d_ref, ref_char, st + at_ref, S));
+  {
+    // (the names' offsets from 0 on: the blob that goes up begins at the first name)
+    uint32_t *o = (uint32_t *) (st + at_noff);
+    for (int c = 0; c <= n_contigs; c++)
+      o[c] = name_off[c] - name_off[0];
+    memcpy (st + at_names, names + name_off[0], names_bytes);
+    PCCHK (d, hipMemcpyAsync (w.d_name_off, o, (size_t) (n_contigs + 1) * 4, hipMemcpyHostToDevice, d->stream));
+    if (names_bytes)
+      PCCHK (d, hipMemcpyAsync (w.d_names, st + at_names, names_bytes, hipMemcpyHostToDevice, d->stream));
+  }
+  PCCHK (d, hipMemsetAsync (w.d_len + S, 0, (pad - S) * sizeof (unsigned), d->stream));
+  // ---- lengths; the scan's first half: the text's length and the number of holes
+  const long lgrid = std::min ((n + 3) / 4, (long) d->grid * 8);
+  PCCHK (d, hipEventRecord (w.ev[0], d->stream));
+  hipLaunchKernelGGL (pcr_len_kernel, dim3 ((unsigned) lgrid), dim3 (PCR_BLOCK), 0, d->stream, (const int8_t *) d->cols.d_type, (const double *) d->cols.d_post,
+                      (const int32_t *) w.d_contig, (const uint32_t *) w.d_pos, (const uint32_t *) w.d_name_off, n, N, w.d_len);
+  PCCHK (d, hipGetLastError ());
+  PCCHK (d, hipEventRecord (w.ev[1], d->stream));
+  hipLaunchKernelGGL (pcr_scan_reduce_kernel, dim3 (nb), dim3 (PCR_BLOCK), 0, d->stream, (const uint4 *) w.d_len, w.d_bsum_bytes, w.d_bsum_holes);
+  PCCHK (d, hipGetLastError ());
+  hipLaunchKernelGGL (pcr_scan_top_kernel, dim3 (1), dim3 (PCR_TOP), 0, d->stream, w.d_bsum_bytes, w.d_bsum_holes, nb, w.d_ctl);
+  PCCHK (d, hipGetLastError ());
+  PCCHK (d, hipEventRecord (w.ev[2], d->stream));
+  PCCHK (d, hipMemcpyAsync (st, w.d_ctl, sizeof (PcrCtl), hipMemcpyDeviceToHost, d->stream));
+  PCCHK (d, hipStreamSynchronize (d->stream));
+  const PcrCtl ctl = *(const PcrCtl *) st;
+  const size_t total = (size_t) ctl.n_text, holes = (size_t) ctl.n_holes;
+  *n_text = ctl.n_text;
+  *n_holes = ctl.n_holes;
+  if (ctl.n_text > text_cap || ctl.n_holes > hole_cap)
+    return pc_fail (d, "sites_base_text: the text has %llu bytes and %llu rows are left to the host, the arrays hold %llu and %llu (n_text and n_holes say what is needed)",
+                    ctl.n_text, ctl.n_holes, (unsigned long long) text_cap, (unsigned long long) hole_cap);
+  float ms[3] = { 0.0f, 0.0f, 0.0f }, a = 0.0f;
+  PCCHK (d, hipEventElapsedTime (&ms[0], w.ev[0], w.ev[1]));
+  PCCHK (d, hipEventElapsedTime (&ms[1], w.ev[1], w.ev[2]));
+  if (total || holes)
+    {
+      if (total + 16 > w.cap_text)
+        {
+          pc_free (w.d_text);
+          w.cap_text = 0;
+          PCCHK (d, hipMalloc ((void **) &w.d_text, total + total / 8 + 16));
+          w.cap_text = total + total / 8 + 16;
+        }
+      // ---- the scan's second half: the columns' offsets and the holes; the text
+      PCCHK (d, hipEventRecord (w.ev[3], d->stream));
+      hipLaunchKernelGGL (pcr_scan_apply_kernel, dim3 (nb), dim3 (PCR_BLOCK), 0, d->stream, (const uint4 *) w.d_len, (const unsigned long long *) w.d_bsum_bytes,
+                          (const unsigned *) w.d_bsum_holes, w.d_off, w.d_hole_site, w.d_hole_at);
+      PCCHK (d, hipGetLastError ());
+      PCCHK (d, hipEventRecord (w.ev[4], d->stream));
+      if (total)
+        {
+          const int R = pcr_fill_run (max_name, N);
+          const unsigned tile_bytes = pcr_fill_tile_bytes (max_name, N);
+          hipLaunchKernelGGL (pcr_fill_kernel, dim3 ((unsigned) ((n + R - 1) / R)), dim3 (PCR_BLOCK), tile_bytes + (size_t) R * 4, d->stream, (const unsigned *) w.d_len,
+                              (const unsigned long long *) w.d_off, (const int8_t *) d->cols.d_call, (const int32_t *) w.d_contig, (const uint32_t *) w.d_pos,
+                              (const char *) w.d_ref, (const char *) w.d_names, (const uint32_t *) w.d_name_off, n, N, R, tile_bytes, w.d_text);
+          PCCHK (d, hipGetLastError ());
+        }
+      PCCHK (d, hipEventRecord (w.ev[5], d->stream));
+      if (holes)
+        {
+          PCCHK (d, hipMemcpyAsync (st + at_hsite, w.d_hole_site, holes * 4, hipMemcpyDeviceToHost, d->stream));
+          PCCHK (d, hipMemcpyAsync (st + at_hat, w.d_hole_at, holes * 8, hipMemcpyDeviceToHost, d->stream));
+        }
+      if (total)
+        PCTRY (pcr_text_back (d, w.ev[5], text, total));
+      PCCHK (d, hipStreamSynchronize (d->stream));
+      if (holes)
+        {
+          memcpy (hole_site, st + at_hsite, holes * 4);
+          memcpy (hole_at, st + at_hat, holes * 8);
+        }
+      PCCHK (d, hipEventElapsedTime (&a, w.ev[3], w.ev[4]));
+      ms[1] += a;
+      PCCHK (d, hipEventElapsedTime (&ms[2], w.ev[4], w.ev[5]));
+    }
+  if (kernel_ms3)
+    memcpy (kernel_ms3, ms, sizeof ms);
   return 0;
 }
 

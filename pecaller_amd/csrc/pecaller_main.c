@@ -32,10 +32,16 @@
 #include <time.h>
 #include "../../include/pemap_hip.h"
 #include "host_io.h"
+#include "pecall_row_len.h"
+
+/* (weak: the program links against a library without this entry too -- an older build, or the tests' host-only stand-in -- and
+   PECALLER_DEVICE_ROWS=1 then ends the run with a message) */
+extern __typeof__ (pecall_dev_sites_base_text) pecall_dev_sites_base_text __attribute__ ((weak));
 
 #define MAX_SAMPLES 512         /* PCS_MAXN of the device caller */
 #define NA 6
 #define MAX_DIST 501            /* pecaller.c:222 */
+#define MAX_MT 128               /* threads of the merge and of the row formatting at most */
 
 static void
 die (const char *fmt, const char *arg)
@@ -133,6 +139,17 @@ typedef struct
   uint8_t *chrom_slot;          /* [T]: chromosome class of position p0 + slot */
   uint32_t *col_slot, *vrow, *vlist;    /* [T] */
   unsigned int p0;
+  /* PECALLER_DEVICE_ROWS=1 (dtext NULL otherwise): the rows of <outfile>.base.gz as the device made them (pecall_dev_sites_base_text)
+     -- those of the columns whose posteriors are all 1 -- and the holes: the host's row of column hole_site[k] (= post_site[k])
+     belongs at byte hole_at[k] of dtext.  The rows stage notes where its row of hole k lies (hole_off: in the formatting thread's
+     buffer; hole_src, hole_len) and how many bytes of host rows lie in front of it (hole_pre, one more entry than holes). */
+  char *dtext;
+  uint64_t dtext_cap, n_dtext;
+  int dtext_pinned;
+  uint32_t *hole_site, *hole_len;
+  uint64_t *hole_at, *hole_off, *hole_pre;
+  const char **hole_src;
+  uint64_t hole_cap, n_holes;
   /* the arrays that are page-locked (pecall_dev_pin_host took them): released before they are freed */
   const void *pinned[8];
   int n_pinned;
@@ -160,11 +177,49 @@ sb_room (sbuf * b, size_t k)
   return b->p + b->n;
 }
 
-/* rows of columns [s0, s1): <outfile>.base.gz text into ob, <outfile>.snp text into sb, <outfile>.piles.gz text into pb */
+/* the row of column s in <outfile>.base.gz, appended to ob; p: the column's posteriors, NULL: all 1 */
 static void
+emit_base_row (const tile_t * t, long s, const double *p, int indiv, const char *frag, size_t fl, sbuf * ob)
+{
+  const int8_t *call = t->call + s * indiv;
+  char *w = sb_room (ob, fl + 32 + (size_t) indiv * 32);
+  char *w0 = w;
+  *w++ = '\n';
+  memcpy (w, frag, fl);
+  w += fl;
+  *w++ = '\t';
+  w += sprintf (w, "%d", (int) t->pos[s]);
+  *w++ = '\t';
+  *w++ = t->ref_char[s];
+  for (int i = 0; i < indiv; i++)
+    {
+      *w++ = '\t';
+      if (call[i] < 14)
+        {
+          *w++ = GEN[call[i]];
+          *w++ = '\t';
+          if (!p || p[i] == 1.0)
+            *w++ = '1';
+          else
+            w += sprintf (w, "%g", p[i]);
+        }
+      else
+        {
+          *w++ = 'N';
+          *w++ = '\t';
+          *w++ = '1';
+        }
+    }
+  ob->n += (size_t) (w - w0);
+}
+
+/* rows of columns [s0, s1): <outfile>.base.gz text into ob, <outfile>.snp text into sb, <outfile>.piles.gz text into pb -> the number
+   of columns that have a row in <outfile>.base.gz.  With the device's text (t->dtext) ob takes the holes' rows only. */
+static long
 emit_rows (const tile_t * t, long s0, long s1, int indiv, char **contig_names, sbuf * ob, sbuf * sb, sbuf * pb)
 {
   char minor[80], am_count[80], tmp[64];
+  long base_rows = 0;
   /* the first listed column at or behind s0 */
   uint64_t lp = 0, hi = t->n_post;
   while (lp < hi)
@@ -186,37 +241,16 @@ emit_rows (const tile_t * t, long s0, long s1, int indiv, char **contig_names, s
       const char *frag = contig_names[t->contig[s]];
       const int8_t *call = t->call + s * indiv;
       const size_t fl = strlen (frag);
-      {
-        char *w = sb_room (ob, fl + 32 + (size_t) indiv * 32);
-        char *w0 = w;
-        *w++ = '\n';
-        memcpy (w, frag, fl);
-        w += fl;
-        *w++ = '\t';
-        w += sprintf (w, "%d", (int) t->pos[s]);
-        *w++ = '\t';
-        *w++ = t->ref_char[s];
-        for (int i = 0; i < indiv; i++)
-          {
-            *w++ = '\t';
-            if (call[i] < 14)
-              {
-                *w++ = GEN[call[i]];
-                *w++ = '\t';
-                if (!p || p[i] == 1.0)
-                  *w++ = '1';
-                else
-                  w += sprintf (w, "%g", p[i]);
-              }
-            else
-              {
-                *w++ = 'N';
-                *w++ = '\t';
-                *w++ = '1';
-              }
-          }
-        ob->n += (size_t) (w - w0);
-      }
+      base_rows++;
+      if (!t->dtext)
+        emit_base_row (t, s, p, indiv, frag, fl, ob);
+      else if (p)
+        {
+          /* a hole of the device's text: list entry lp - 1 */
+          t->hole_off[lp - 1] = ob->n;
+          emit_base_row (t, s, p, indiv, frag, fl, ob);
+          t->hole_len[lp - 1] = (uint32_t) (ob->n - t->hole_off[lp - 1]);
+        }
       if (t->type[s] == 0)
         continue;
       minor[0] = am_count[0] = '\0';
@@ -244,6 +278,7 @@ emit_rows (const tile_t * t, long s0, long s1, int indiv, char **contig_names, s
             pb->n += (size_t) sprintf (sb_room (pb, 16), "\t%d", (int) r[a]);
         }
     }
+  return base_rows;
 }
 
 /* ---- what a run is made of.  The reference, read-only once the .sdx and the .seq are loaded: the merge threads and both stages of
@@ -263,8 +298,13 @@ typedef struct
 {
   const run_t *r;
   const tile_t *t;
-  long s0, s1;
+  long s0, s1, base_rows;
   sbuf ob, sb, pb;              /* (kept from tile to tile) */
+  /* the splice of the device's text and the holes' rows: bytes [lo, hi) of the text and the holes that belong in front of them (the
+     last job: also those at the text's end), to their places in out */
+  uint64_t lo, hi;
+  int last;
+  char *out;
 } emit_job;
 
 /* a merge thread's view of the range being walked */
@@ -304,7 +344,6 @@ typedef struct
   double sec;                   /* spent on its tiles */
 } stage_t;
 
-#define MAX_MT 128
 #define RC_UNORDERED 77
 struct run_s
 {
@@ -318,6 +357,13 @@ struct run_s
      (find_lowest, pecaller.c:865-923, 1820-1833), whatever order the records come in; otherwise by the parallel walk.  device_merge
      (PECALLER_DEVICE_MERGE=1): a range's columns are made on the device from the streams' records; not with a guide file or serial_merge */
   int serial_merge, device_merge;
+  /* device_rows (PECALLER_DEVICE_ROWS=1): the rows of <outfile>.base.gz whose posteriors are all 1 are made on the device behind each
+     tile's call (pecall_dev_sites_base_text); names / name_off: the contig names as that call takes them */
+  int device_rows;
+  char *names;
+  uint32_t *name_off;
+  size_t max_name;
+  long rows_dev, rows_hole;
   /* set once (start_pipeline).  tile: columns per device call, and genome positions per range of the stream merge -- a call has a fixed
      part (two kernel launches, the transfers' latencies), so tiles are large.  mg_chunk: slots per work item of the column pass.
      guide_range_min: positions of a guide interval left from which the streams are walked in parallel.  post_cap: a tile's first list */
@@ -361,8 +407,85 @@ static void *
 emit_thread (void *arg)
 {
   emit_job *j = (emit_job *) arg;
-  emit_rows (j->t, j->s0, j->s1, j->r->indiv, j->r->ref.contig_names, &j->ob, &j->sb, &j->pb);
+  j->base_rows = emit_rows (j->t, j->s0, j->s1, j->r->indiv, j->r->ref.contig_names, &j->ob, &j->sb, &j->pb);
   return NULL;
+}
+
+/* bytes [lo, hi) of the device's text go to out, each behind the host rows that belong in front of it; the rows of the holes at
+   lo <= hole_at < hi (the last job: <= hi) go in between */
+static void *
+splice_thread (void *arg)
+{
+  const emit_job *j = (const emit_job *) arg;
+  const tile_t *t = j->t;
+  uint64_t k = 0, top = t->n_holes, cur = j->lo;
+  while (k < top)               /* the first hole at or behind lo */
+    {
+      const uint64_t mid = (k + top) / 2;
+      if (t->hole_at[mid] < j->lo)
+        k = mid + 1;
+      else
+        top = mid;
+    }
+  for (; k < t->n_holes && (t->hole_at[k] < j->hi || (j->last && t->hole_at[k] == j->hi)); k++)
+    {
+      memcpy (j->out + cur + t->hole_pre[k], t->dtext + cur, (size_t) (t->hole_at[k] - cur));
+      cur = t->hole_at[k];
+      memcpy (j->out + cur + t->hole_pre[k], t->hole_src[k], t->hole_len[k]);
+    }
+  memcpy (j->out + cur + t->hole_pre[k], t->dtext + cur, (size_t) (j->hi - cur));
+  return NULL;
+}
+
+static void
+run_jobs (void *(*fn) (void *), emit_job * jobs, int threads)
+{
+  pthread_t th[MAX_MT];
+  for (int k = 1; k < threads; k++)
+    if (pthread_create (&th[k], NULL, fn, &jobs[k]))
+      die ("\n pecaller_hip: can not start %s", "a formatting thread");
+  fn (&jobs[0]);
+  for (int k = 1; k < threads; k++)
+    pthread_join (th[k], NULL);
+}
+
+/* <outfile>.base.gz text of a tile whose template rows came from the device: the device's text with the rows the formatting threads
+   made of the holes put in at their places, appended to r->ob */
+static void
+splice_tile (run_t * r, const tile_t * t, int threads)
+{
+  emit_job *jobs = r->jobs;
+  if (t->n_holes != t->n_post)
+    die ("\n pecaller_hip: %s", "the device's text leaves other rows to the host than the call listed");
+  uint64_t pre = 0;
+  int j = 0;
+  for (uint64_t k = 0; k < t->n_holes; k++)
+    {
+      if (t->hole_site[k] != t->post_site[k])
+        die ("\n pecaller_hip: %s", "the device's text leaves other rows to the host than the call listed");
+      while (j < threads - 1 && (long) t->hole_site[k] >= jobs[j].s1)
+        j++;
+      t->hole_src[k] = jobs[j].ob.p + t->hole_off[k];
+      t->hole_pre[k] = pre;
+      pre += t->hole_len[k];
+    }
+  t->hole_pre[t->n_holes] = pre;
+  const uint64_t total = t->n_dtext + pre;
+  char *out = sb_room (&r->ob, (size_t) total);
+  for (int k = 0; k < threads; k++)
+    {
+      jobs[k].out = out;
+      jobs[k].lo = t->n_dtext * (uint64_t) k / (uint64_t) threads;
+      jobs[k].hi = t->n_dtext * (uint64_t) (k + 1) / (uint64_t) threads;
+      jobs[k].last = k == threads - 1;
+    }
+  run_jobs (splice_thread, jobs, threads);
+  r->ob.n += (size_t) total;
+  long base_rows = 0;
+  for (int k = 0; k < threads; k++)
+    base_rows += jobs[k].base_rows;
+  r->rows_hole += (long) t->n_holes;
+  r->rows_dev += base_rows - (long) t->n_holes;
 }
 
 /* the rows of a tile, formatted by the run's MT threads (contiguous runs of columns, put together in column order) */
@@ -370,7 +493,6 @@ static void
 emit_tile (run_t * r, const tile_t * t)
 {
   emit_job *jobs = r->jobs;
-  pthread_t th[MAX_MT];
   const int threads = t->n < 4096 ? 1 : r->MT;
   for (int k = 0; k < threads; k++)
     {
@@ -380,16 +502,16 @@ emit_tile (run_t * r, const tile_t * t)
       jobs[k].s1 = t->n * (k + 1) / threads;
       jobs[k].ob.n = jobs[k].sb.n = jobs[k].pb.n = 0;
     }
-  for (int k = 1; k < threads; k++)
-    if (pthread_create (&th[k], NULL, emit_thread, &jobs[k]))
-      die ("\n pecaller_hip: can not start %s", "a formatting thread");
-  emit_thread (&jobs[0]);
-  for (int k = 1; k < threads; k++)
-    pthread_join (th[k], NULL);
+  run_jobs (emit_thread, jobs, threads);
+  if (t->dtext)
+    splice_tile (r, t, threads);
   for (int k = 0; k < threads; k++)
     {
-      memcpy (sb_room (&r->ob, jobs[k].ob.n), jobs[k].ob.p, jobs[k].ob.n);
-      r->ob.n += jobs[k].ob.n;
+      if (!t->dtext)
+        {
+          memcpy (sb_room (&r->ob, jobs[k].ob.n), jobs[k].ob.p, jobs[k].ob.n);
+          r->ob.n += jobs[k].ob.n;
+        }
       if (jobs[k].sb.n)
         fwrite (jobs[k].sb.p, 1, jobs[k].sb.n, r->snpfile);
       if (jobs[k].pb.n)
@@ -705,6 +827,61 @@ device_merge_columns (run_t * r, tile_t * t)
   r->dev_ranges++;
 }
 
+/* the tile's page-locked text buffer, and its hole lists with what the rows stage notes per hole: made anew for `cap` (the arrays
+   hold nothing that is still needed when they grow) */
+static void
+tile_text_alloc (run_t * r, tile_t * t, uint64_t cap)
+{
+  if (t->dtext_pinned)
+    (void) pecall_dev_unpin_host (r->pc, t->dtext);
+  free (t->dtext);
+  t->dtext = (char *) malloc ((size_t) cap);
+  if (!t->dtext)
+    die ("\n pecaller_hip: out of memory for %s", "the device's text");
+  t->dtext_cap = cap;
+  t->dtext_pinned = pecall_dev_pin_host (r->pc, t->dtext, cap) == 0;
+}
+
+static void
+tile_holes_alloc (tile_t * t, uint64_t cap)
+{
+  void *old[] = { t->hole_site, t->hole_len, t->hole_at, t->hole_off, t->hole_pre, (void *) t->hole_src };
+  for (size_t k = 0; k < sizeof old / sizeof old[0]; k++)
+    free (old[k]);
+  t->hole_site = (uint32_t *) malloc ((size_t) cap * sizeof (uint32_t));
+  t->hole_len = (uint32_t *) malloc ((size_t) cap * sizeof (uint32_t));
+  t->hole_at = (uint64_t *) malloc ((size_t) cap * sizeof (uint64_t));
+  t->hole_off = (uint64_t *) malloc ((size_t) cap * sizeof (uint64_t));
+  t->hole_pre = (uint64_t *) malloc ((size_t) (cap + 1) * sizeof (uint64_t));
+  t->hole_src = (const char **) malloc ((size_t) cap * sizeof (const char *));
+  if (!t->hole_site || !t->hole_len || !t->hole_at || !t->hole_off || !t->hole_pre || !t->hole_src)
+    die ("\n pecaller_hip: out of memory for %s", "the list of rows left to the host");
+  t->hole_cap = cap;
+}
+
+/* behind the tile's call, its heads filled: the template rows of <outfile>.base.gz from the device.  A buffer that is too small is
+   made anew with the size the call asked for, and once more (as call_tile does with the list of posteriors) */
+static void
+device_text (run_t * r, tile_t * t)
+{
+  t->n_dtext = t->n_holes = 0;
+  if (t->n <= 0)
+    return;
+  for (int again = 0;; again++)
+    {
+      const int rc = pecall_dev_sites_base_text (r->pc, r->names, r->name_off, r->ref.no_contigs, t->contig, t->pos, t->ref_char, t->dtext, t->dtext_cap, &t->n_dtext,
+                                                 t->hole_site, t->hole_at, t->hole_cap, &t->n_holes, NULL);
+      if (!rc)
+        return;
+      if (again || (t->n_dtext <= t->dtext_cap && t->n_holes <= t->hole_cap))
+        die ("\n pecaller_hip: %s", pecall_dev_last_error (r->pc));
+      if (t->n_holes > t->hole_cap)
+        tile_holes_alloc (t, t->n_holes + t->n_holes / 8 + 1024);
+      if (t->n_dtext > t->dtext_cap)
+        tile_text_alloc (r, t, t->n_dtext + t->n_dtext / 8 + 4096);
+    }
+}
+
 static void
 call_tile (run_t * r, tile_t * t)
 {
@@ -731,6 +908,8 @@ call_tile (run_t * r, tile_t * t)
     die ("\n pecaller_hip: %s", pecall_dev_last_error (r->pc));
   else if (r->device_merge)
     device_merge_columns (r, t);
+  if (r->device_rows)
+    device_text (r, t);
 }
 
 static void
@@ -844,6 +1023,12 @@ tile_alloc (run_t * r, tile_t * t)
       tile_pin (r, t, t->ref_base, (uint64_t) T);
       tile_pin (r, t, t->chrom, (uint64_t) T);
     }
+  if (r->device_rows)
+    {
+      /* every column a row of the longest form: the longest contig name, ten digits */
+      tile_text_alloc (r, t, (uint64_t) T * pcr_row_len ((uint32_t) r->max_name, PCR_MAX_POS, (uint32_t) indiv));
+      tile_holes_alloc (t, t->post_cap);
+    }
   tile_pin (r, t, t->call, (uint64_t) T * indiv);
   tile_pin (r, t, t->type, (uint64_t) T);
   tile_pin (r, t, t->ac, (uint64_t) T * NA * sizeof (int32_t));
@@ -855,6 +1040,11 @@ tile_free (run_t * r, tile_t * t)
 {
   for (int k = 0; k < t->n_pinned; k++)
     (void) pecall_dev_unpin_host (r->pc, t->pinned[k]);
+  if (t->dtext_pinned)
+    (void) pecall_dev_unpin_host (r->pc, t->dtext);
+  void *rows[] = { t->dtext, t->hole_site, t->hole_len, t->hole_at, t->hole_off, t->hole_pre, (void *) t->hole_src };
+  for (size_t k = 0; k < sizeof rows / sizeof rows[0]; k++)
+    free (rows[k]);
   void *all[] = { t->recs, t->n_recs, t->chrom_slot, t->col_slot, t->vrow, t->vlist, t->reads, t->ref_base, t->chrom, t->denovo, t->ref_char, t->contig,
     t->pos, t->call, t->post_site, t->post_rows, t->type, t->ac };
   for (size_t k = 0; k < sizeof all / sizeof all[0]; k++)
@@ -1174,6 +1364,28 @@ start_pipeline (run_t * r)
   if ((e = getenv ("PECALLER_POST_CAP")) && atol (e) >= 1)
     r->post_cap = (uint64_t) atol (e);
   r->device_merge = !r->guide_file && !r->serial_merge && (e = getenv ("PECALLER_DEVICE_MERGE")) && atoi (e) == 1;
+  r->device_rows = (e = getenv ("PECALLER_DEVICE_ROWS")) && atoi (e) == 1;
+  if (r->device_rows && !pecall_dev_sites_base_text)
+    die ("\n pecaller_hip: PECALLER_DEVICE_ROWS=1 needs %s, which this library lacks", "pecall_dev_sites_base_text");
+  if (r->device_rows)
+    {
+      const ref_t *g = &r->ref;
+      size_t bytes = 0;
+      for (int i = 0; i < g->no_contigs; i++)
+        bytes += strlen (g->contig_names[i]);
+      r->names = (char *) malloc (bytes + 1);
+      r->name_off = (uint32_t *) calloc ((size_t) g->no_contigs + 1, sizeof (uint32_t));
+      if (!r->names || !r->name_off)
+        die ("\n pecaller_hip: out of memory for %s", "the contig names");
+      for (int i = 0; i < g->no_contigs; i++)
+        {
+          const size_t l = strlen (g->contig_names[i]);
+          memcpy (r->names + r->name_off[i], g->contig_names[i], l);
+          r->name_off[i + 1] = r->name_off[i] + (uint32_t) l;
+          if (l > r->max_name)
+            r->max_name = l;
+        }
+    }
   pthread_mutex_init (&r->pool.mu, NULL);
   pthread_cond_init (&r->pool.cv, NULL);
   for (int k = 0; k < N_TILES; k++)
@@ -1489,6 +1701,8 @@ close_outputs (run_t * r)
           r->tot_cols, r->indiv, sec, (double) r->tot_cols / (sec > 0 ? sec : 1) / 1e6, r->sec_merge, r->sec_wait, r->dev_stage.sec, r->row_stage.sec);
   if (r->device_merge && !r->unordered)
     printf (" pecaller_hip: device merge: %ld columns in %ld ranges\n", r->dev_cols, r->dev_ranges);
+  if (r->device_rows && !r->unordered)
+    printf (" pecaller_hip: device rows: %ld rows from the device, %ld holes formatted by the host\n", r->rows_dev, r->rows_hole);
 }
 
 /* everything the run holds is given back (the stages' threads ended in walk); page-locked ranges before their memory and the device */
@@ -1506,6 +1720,8 @@ teardown (run_t * r)
   for (int k = 0; k < MAX_MT; k++)
     free (r->jobs[k].ob.p), free (r->jobs[k].sb.p), free (r->jobs[k].pb.p);
   free (r->ob.p);
+  free (r->names);
+  free (r->name_off);
   free (r->sm);
   for (int i = 0; i < g->no_contigs; i++)
     free (g->contig_names[i]);

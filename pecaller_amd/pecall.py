@@ -46,6 +46,7 @@ class PecallDev:
         L.pecall_dev_sites_merge_ms.argtypes = [vp, vp]
         L.pecall_dev_call_records.argtypes = [vp, vp, vp, i, u32, u32, vp, u32, vp, C.POINTER(C.c_long), vp,
                                               i, dbl, dbl, vp, vp, vp, u64, vp, vp, vp, vp, vp]
+        L.pecall_dev_sites_base_text.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp]
         self.L = L
         h = vp()
         if L.pecall_dev_create(C.byref(h), device_id):
@@ -111,6 +112,7 @@ class PecallDev:
     def sites_run(self, threshold=0.95, theta=0.001, haploid=False):
         """the kernel on the staged columns -> its duration in ms (HIP events on the object's stream)"""
         ms = C.c_float(0)
+        self._rindiv = self._sshape[1]
         self._ck(self.L.pecall_dev_sites_run(self.h, int(haploid), float(threshold), float(theta), C.byref(ms)))
         return ms.value
 
@@ -194,6 +196,7 @@ class PecallDev:
         col_slot = np.zeros(max(int(span), 1), np.uint32)
         n_cols, n_post = C.c_long(0), C.c_uint64(0)
         self.sparse_needed = 0
+        self._rindiv = indiv
         rc = self.L.pecall_dev_call_records(self.h, C.addressof(ptrs), _p(n), indiv, int(p0), int(span), _p(letters) if letters.size else None, letters.size, _p(cy),
                                             C.byref(n_cols), _p(col_slot), int(haploid), float(threshold), float(theta), _p(call), _p(site), _p(rows), cap,
                                             C.byref(n_post), _p(typ), _p(ac), _p(npass), _p(den))
@@ -203,6 +206,43 @@ class PecallDev:
         self._sshape = (m, indiv)
         self.denovo = den[:m]
         return call[:m], (site[:n_post.value], rows[:n_post.value]), typ[:m], ac[:m], npass[:m], col_slot[:m]
+
+    def base_text(self, names, contig, pos, ref_char, text_cap=None, hole_cap=None, pin=False):
+        """the .base rows of the last call's columns from the device (pecall_dev_sites_base_text): names = the contig names (str or
+        bytes), contig / pos / ref_char per column -> (text bytes, hole_site, hole_at): the rows of the columns that are neither
+        skipped nor holes; the caller's own row of column hole_site[k] belongs at byte hole_at[k].  text_cap / hole_cap default
+        to the bound (every column a row of the longest form, every column a hole); a failure for want of room leaves what is
+        needed in self.text_needed / self.holes_needed.  pin: the text buffer is page-locked for the call.
+        self.rows_ms = the kernels' durations (length, scan, fill)"""
+        nm = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+        blob = np.frombuffer(b"".join(nm) + b"\0", np.uint8)
+        name_off = np.concatenate([[0], np.cumsum([len(x) for x in nm])]).astype(np.uint32)
+        contig = np.ascontiguousarray(contig, np.int32)
+        pos = np.ascontiguousarray(pos, np.uint32)
+        ref = np.frombuffer(ref_char.encode() if isinstance(ref_char, str) else bytes(ref_char), np.uint8) if not isinstance(ref_char, np.ndarray) else np.ascontiguousarray(ref_char).view(np.uint8)
+        n = len(contig)
+        if len(pos) != n or ref.size != n:
+            raise ValueError("contig, pos and ref_char have one entry per column")
+        indiv = getattr(self, "_rindiv", 0) or 512          # (samples of the last call)
+        if text_cap is None:
+            text_cap = n * (14 + max([len(x) for x in nm] + [0]) + 4 * indiv)
+        if hole_cap is None:
+            hole_cap = n
+        text = np.zeros(max(int(text_cap), 1), np.uint8)
+        site, at = np.zeros(max(int(hole_cap), 1), np.uint32), np.zeros(max(int(hole_cap), 1), np.uint64)
+        n_text, n_holes = C.c_uint64(0), C.c_uint64(0)
+        ms = np.zeros(3, np.float32)
+        if pin:
+            self.pin_host(text)
+        try:
+            rc = self.L.pecall_dev_sites_base_text(self.h, _p(blob), _p(name_off), len(nm), _p(contig), _p(pos), _p(ref), _p(text), int(text_cap),
+                                                   C.byref(n_text), _p(site), _p(at), int(hole_cap), C.byref(n_holes), _p(ms))
+        finally:
+            if pin:
+                self.unpin_host(text)
+        self.text_needed, self.holes_needed, self.rows_ms = int(n_text.value), int(n_holes.value), ms
+        self._ck(rc)
+        return text[:n_text.value].tobytes(), site[:n_holes.value], at[:n_holes.value]
 
     def pin_host(self, a):
         self._ck(self.L.pecall_dev_pin_host(self.h, a.ctypes.data, a.nbytes))
@@ -238,6 +278,7 @@ class PecallDev:
         n = C.c_uint64(0)
         self.denovo = den
         self.sparse_needed = 0
+        self._rindiv = indiv
         rc = self.L.pecall_dev_call_sites_sparse(self.h, _p(reads), _p(ref_base), _p(cy), n_sites, indiv, int(haploid), float(threshold),
                                                  float(theta), _p(call), _p(site), _p(rows), cap, C.byref(n), _p(typ), _p(ac), _p(npass), _p(den))
         self.sparse_needed = int(n.value)
@@ -255,6 +296,7 @@ class PecallDev:
         cy = None if chrom is None else np.ascontiguousarray(chrom, np.uint8)
         call, post, typ, ac, npass, den = out if out is not None else self.out_arrays(n_sites, indiv)
         self.denovo = den
+        self._rindiv = indiv
         self._ck(self.L.pecall_dev_call_sites(self.h, _p(reads), _p(ref_base), _p(cy), n_sites, indiv, int(haploid), float(threshold),
                                               float(theta), _p(call), _p(post), _p(typ), _p(ac), _p(npass), _p(den)))
         return call, post, typ, ac, npass

@@ -54,7 +54,7 @@ struct PmChunkSet
   PmHits hits = {};
   uint32_t *wins = nullptr, *dirbuf = nullptr;
   uint32_t *walks = nullptr;    // places in `wins` of the alignments pm_walk_kernel follows
-  uint32_t *tasks_s = nullptr, *tasks_m = nullptr;      // each in thirds: all problems, those left to the DP, those left to the banded DP
+  uint32_t *tasks_s = nullptr, *tasks_m = nullptr;      // each in quarters: all problems, those left to the DP, to the banded DP, to the gapless rule's second launch
   unsigned long long *path = nullptr;   // recorded traceback steps per winning alignment
   uint16_t *nsteps = nullptr;
   PmLists lists = {};
@@ -84,7 +84,7 @@ struct PmKnobs
 {
   int big_blocks_per_cu, sw_waves_per_cu;
   int replicas;                 // -1 unset, 0 never, 1 as the default
-  int gapless;                  // 0 off, 1 first case only, 2 both
+  int gapless;                  // 0 off, 1 first case only, 2 the first two, 3 all three
   double dir_budget_gb;
   int lookup_waves /* -1 unset */;
   int lookup_prio, vote_prio, sw_prio;
@@ -113,7 +113,7 @@ static void read_knobs (PmKnobs & k)
   if (k.big_blocks_per_cu < 1) k.big_blocks_per_cu = 1;
   if (k.sw_waves_per_cu < 1) k.sw_waves_per_cu = 1;
   k.replicas = getenv ("PEMAP_REPLICAS") ? (env_int ("PEMAP_REPLICAS", 1) ? 1 : 0) : -1;
-  k.gapless = env_int ("PEMAP_GAPLESS", 2);
+  k.gapless = env_int ("PEMAP_GAPLESS", 3);
   { const char *e = getenv ("PEMAP_DIR_BUDGET_GB"); k.dir_budget_gb = e ? atof (e) : 40.0; if (k.dir_budget_gb < 0.25) k.dir_budget_gb = 0.25; }
   k.lookup_waves = env_int ("PEMAP_LOOKUP_WAVES", -1);
   k.lookup_prio = env_int ("PEMAP_LOOKUP_PRIO", 0);
@@ -807,7 +807,8 @@ static int ensure_reads (pemap_dev * d, int n, int stride, int paired)
 // 2 x 250 bp: 111.8 against 120.5 with 8 x 32); with the rule off (PEMAP_GAPLESS=0: every problem through the DP) reads of
 // 105..152 bases take 8 x 19, which was 18 % faster there.  (8 x 26 / 32 / 38 and 12 x 13 were measured equal or slower and are gone.)
 // PEMAP_GAPLESS=0: every problem goes through the DP (the rule of pm_gapless_kernel off); 1: its first case only (diagonals
-// with at most one mismatch); default 2: both cases
+// with at most one mismatch); 2: the first two (best diagonal with two mismatches, as before case (3) existed: the A/B switch
+// inside one build); default 3: all three (best diagonal with three mismatches on a full-width window)
 static int pm_gapless_max_x (const pemap_dev * d)
 {
   return d->kn.gapless;
@@ -875,8 +876,8 @@ static int ensure_work (pemap_dev * d, int n_ends)
           TRY (alloc_hits (d, s.hits, n_ends));
           TRY (dev_alloc (d, &s.wins, (size_t) n_ends));
           TRY (dev_alloc (d, &s.walks, (size_t) n_ends));
-          TRY (dev_alloc (d, &s.tasks_s, (size_t) n_ends * 3));       // second third: the problems left to the DP, last third: to the banded DP
-          TRY (dev_alloc (d, &s.tasks_m, nh * 3));
+          TRY (dev_alloc (d, &s.tasks_s, (size_t) n_ends * 4));       // second quarter: the problems left to the DP, third: to the banded DP, last: to case (3)
+          TRY (dev_alloc (d, &s.tasks_m, nh * 4));
         }
       TRY (dev_alloc (d, &d->d_redo, (size_t) n_ends));
       d->cap_ends = n_ends;
@@ -1224,8 +1225,14 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
       const int gbp = d->kn.gapless_blocks_per_cu > 0 ? d->kn.gapless_blocks_per_cu : (seg_template (c.L) <= 10 ? 24 : 6);
       if (ggrid > d->n_cus * gbp)
         ggrid = d->n_cus * gbp;
-      hipLaunchKernelGGL (pm_gapless_kernel, dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, H, tasks_s, &ctr->n_tasks_s, tasks_dp,
-                          &ctr->n_tasks_dp, pm_gapless_max_x (d), tasks_band, &ctr->n_band[0]);
+      // case (3) in a launch of its own over the problems it may decide (one in eight; what it refuses joins the DP's lists)
+      uint32_t *tasks_c3 = pm_gapless_max_x (d) >= 3 ? tasks_s + 3 * (size_t) d->cap_ends : nullptr;
+      hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < false >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, H, tasks_s,
+                          &ctr->n_tasks_s, tasks_dp, &ctr->n_tasks_dp, pm_gapless_max_x (d), tasks_band, &ctr->n_band[0], tasks_c3, &ctr->n_c3[0]);
+      if (tasks_c3)
+        hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < true >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, H, tasks_c3,
+                            &ctr->n_c3[0], tasks_dp, &ctr->n_tasks_dp, pm_gapless_max_x (d), tasks_band, &ctr->n_band[0], (uint32_t *) nullptr,
+                            (unsigned *) nullptr);
       if (tasks_band)
         {
           // the problems the rule left open whose best diagonal has few mismatches: the DP restricted to a band of 32 diagonals,
@@ -1249,8 +1256,13 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
       // sw_next[3] counts what is left to the DP
       uint32_t *tasks_mdp = tasks_m + (size_t) d->cap_ends * PM_MAX_HITS;
       uint32_t *tasks_mband = d->kn.band ? tasks_m + 2 * (size_t) d->cap_ends * PM_MAX_HITS : nullptr;
-      hipLaunchKernelGGL (pm_gapless_kernel, dim3 (d->n_cus * 16), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, H, tasks_m, &ctr->n_tasks_m, tasks_mdp,
-                          &ctr->sw_next[3], pm_gapless_max_x (d), tasks_mband, &ctr->n_band[1]);
+      uint32_t *tasks_mc3 = pm_gapless_max_x (d) >= 3 ? tasks_m + 3 * (size_t) d->cap_ends * PM_MAX_HITS : nullptr;
+      hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < false >), dim3 (d->n_cus * 16), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, H, tasks_m,
+                          &ctr->n_tasks_m, tasks_mdp, &ctr->sw_next[3], pm_gapless_max_x (d), tasks_mband, &ctr->n_band[1], tasks_mc3, &ctr->n_c3[1]);
+      if (tasks_mc3)
+        hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < true >), dim3 (d->n_cus * 16), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, H, tasks_mc3,
+                            &ctr->n_c3[1], tasks_mdp, &ctr->sw_next[3], pm_gapless_max_x (d), tasks_mband, &ctr->n_band[1], (uint32_t *) nullptr,
+                            (unsigned *) nullptr);
       if (tasks_mband)
         hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_band_kernel < false >), dim3 (d->n_cus * d->kn.band_waves_per_cu), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H,
                             tasks_mband, &ctr->n_band[1], ctr, dirbuf, slab_dwords_for (d, c.L), &ctr->band_next[1]);

@@ -108,6 +108,7 @@ struct PmCounters
   unsigned int sw_next[4];         // work counters of the three SW launches of a chunk (single-hit, multi-hit, redo)
   unsigned int n_band[2];          // problems left to the banded DP (pm_band_kernel): single-hit ends, multi-hit ends
   unsigned int band_next[2];       // their work counters
+  unsigned int n_c3[2];            // problems the gapless rule's first launch leaves to its second (case (3)): single-hit ends, multi-hit ends
   unsigned long long cells_band;   // band cells computed
   unsigned int n_walks;            // of n_wins, the alignments pm_walk_kernel follows (the others are known to be plain diagonals)
 };

@@ -426,7 +426,28 @@ __device__ __forceinline__ double pm_add_ones (double y, int n)
 //       d1 < d2.  If none does, (1)'s statements hold for the diagonals with x = 2: a path with a gap reaches a cell of
 //       such a diagonal with more than the fold's c - 8/3 only as (perfect prefix elsewhere, deletion, perfect stretch
 //       here past both mismatches), which continued to the end IS such an alignment; the same for S1 on the diagonal.
-// In both cases the winner is the first maximum in ascending row order under strict '>' (1724-1741) among the folds,
+//   (3) xmin = 3 (full-width windows, D = nn - mm = 2 PM_SLOP + 1; clipped ones keep going to the banded DP, by choice).
+//       Against a perfect alignment a mismatch costs 4/3, a deletion of b reference bases 2 + (b-1)/36, an insertion of
+//       b read bases 2 + (b-1)/36 + b; the diagonal costs 4.  Every gapped alignment costs at least 4 + 1/36 -- ten
+//       orders above the rounding of these sums -- (one deletion with two mismatches >= 4.67, one inserted base with
+//       one mismatch 4.33, two inserted bases 4.03, two deletions of three or more bases together >= 4.03, a deletion
+//       and an insertion >= 5, three gaps >= 6) except three kinds, and where one of those exists the problem is left
+//       to the DP.  With preY[d] / sufY[d] the longest prefix / suffix of diagonal d with at most Y mismatches:
+//         (a) one deletion, at most one mismatch (<= 3.33 + (b-1)/36): pre0[d1] + suf1[d2] >= mm or
+//             pre1[d1] + suf0[d2] >= mm for some d1 < d2 in 0 .. D;
+//         (b) one inserted read base, no mismatch (3): pre0[d1] + suf0[d1 - 1] >= mm - 1 for some d1 in 0 .. D + 1.  The
+//             two edge diagonals lie inside the window without one read base: -1 holds bases 1 .. mm - 1 (reached from
+//             the top border at the price of base 0 inserted), D + 1 holds 0 .. mm - 2 (the last base inserted); their
+//             pre0 and suf0 are at most mm - 1;
+//         (c) two one-base deletions, no mismatch (exactly 4: a tie in real arithmetic, which rounding decides): for
+//             some d in 0 .. D - 2 diagonal d + 1 has no mismatch in [pre0[d], mm - suf0[d + 2]) (an empty range is (a)).
+//       If none exists, (2)'s argument holds word for word for the diagonals with x = 3: a gapped path that reaches a
+//       cell of one of them with more than the fold, continued along it to the read's end, IS one of the excluded
+//       alignments; the same for the S1 and S2 the traceback compares.  The kernel knows per diagonal the first two
+//       and the last two mismatches ((c): a lane looks at its pieces in the rare case that those four do not settle
+//       the range).  The rule errs towards the DP only.  tests/test_gapless_rule3_cpu.py restates it and shows on the
+//       full DP that each of (a), (b), (c) is needed.
+// In all cases the winner is the first maximum in ascending row order under strict '>' (1724-1741) among the folds,
 // which are reproduced addition by addition, so the score is the DP's double to the last bit.  Such a problem gets its
 // score, start cell (plane 0, row d + mm) and the PM_GAPLESS flag; the walk kernel then emits mm diagonal steps without
 // a direction slab.  Everything else is appended to tasks_dp for pm_sw_kernel.  With 1 % substitutions 81 % of the
@@ -492,15 +513,21 @@ static_assert (PM_BAND_K >= 2 && PM_BAND_K <= 5, "the band holds at most 32 diag
 // (one-wave workgroups: a wave goes wherever a SIMD has room beside the seed kernel's waves; four to a workgroup waited for room for four)
 #define PM_GL_BLOCK 64
 #define PM_GL_PER_BLOCK (PM_GL_BLOCK / 32)     // problems a workgroup works on at a time: one per half-wave
-__global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gapless_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, const uint32_t * tasks,
+// C3 = false, the launch over all problems: cases (1) and (2); a problem that case (3) may decide goes to tasks_c3 when that list is
+// given, and to the DP's lists like the rest when it is not.  C3 = true, a second launch over tasks_c3 alone: all three cases.  (Case
+// (3) inside the one launch took registers from every problem's path: the kernel was a third slower for one problem in eight.)
+template < bool C3 > __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gapless_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, const uint32_t * tasks,
                                                           const unsigned *n_tasks_p, uint32_t * tasks_dp, unsigned *n_tasks_dp, int max_x,
-                                                          uint32_t * tasks_band, unsigned *n_tasks_band)
+                                                          uint32_t * tasks_band, unsigned *n_tasks_band, uint32_t * tasks_c3, unsigned *n_tasks_c3)
 {
   __shared__ __align__ (8) uint8_t rd[PM_GL_PER_BLOCK][320];
-  __shared__ __align__ (8) uint8_t win[PM_GL_PER_BLOCK][352];         // the window: nn <= 299 bytes, read in 8-byte pieces up to 8 bytes past 8-byte boundaries
+  // the window: nn <= 299 bytes, read in 8-byte pieces up to 8 bytes past 8-byte boundaries; it starts at byte 8 of its row, so that
+  // case (3)'s diagonal -1 finds a piece (never written, its one byte never used) in front of it
+  __shared__ __align__ (8) uint8_t win[PM_GL_PER_BLOCK][360];
   __shared__ uint32_t q_band[PM_GL_BLOCK / 64][PM_GL_QUEUE], q_dp[PM_GL_BLOCK / 64][PM_GL_QUEUE];       // per wave: problems on their way to the two DP lists
+  __shared__ uint32_t q_c3[PM_GL_BLOCK / 64][C3 ? 1 : PM_GL_QUEUE];       // ... and to the second launch
   const int wv = threadIdx.x >> 6;
-  int n_qb = 0, n_qd = 0;
+  int n_qb = 0, n_qd = 0, n_q3 = 0;
   auto flush_queue = [&] (const uint32_t * q, int &n, uint32_t * dst, unsigned *counter)
   {
     if (n == 0)
@@ -604,7 +631,7 @@ __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gapless_kernel (PmIndex ix
                 *(uint64_t *) &rd[slot][8 * c] = v;
               }
             if (valid && 8 * c < nn + 16)
-              *(uint64_t *) &win[slot][8 * c] = wq[u];
+              *(uint64_t *) &win[slot][8 + 8 * c] = wq[u];
           }
       }
       __builtin_amdgcn_fence (__ATOMIC_SEQ_CST, "wavefront");
@@ -619,7 +646,7 @@ __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gapless_kernel (PmIndex ix
       {
         const uint64_t q = *(const uint64_t *) &rd[slot][8 * c];
         const int off = d + 8 * c, sh = 8 * (off & 7);
-        const uint64_t *wq = (const uint64_t *) &win[slot][off & ~7];
+        const uint64_t *wq = (const uint64_t *) &win[slot][8 + (off & ~7)];
         const uint64_t lo = wq[0], hi = wq[1];
         const uint64_t r = sh ? ((lo >> sh) | (hi << (64 - sh))) : lo;
         const int nb = mm - 8 * c < 8 ? mm - 8 * c : 8;
@@ -755,6 +782,116 @@ __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gapless_kernel (PmIndex ix
               const unsigned del = (unsigned) (__ballot (mine && pbefore + suf >= mm) >> half);
               cmask = del ? 0u : c2;
             }
+          else if (C3 && max_x >= 3 && ndiag == 2 * PM_SLOP + 2)
+            {
+              const unsigned c3 = (unsigned) (__ballot (mism == 3) >> half);
+              if (c3 != 0u)
+                {
+                  // case (3), full-width windows only (D = nn - mm = 2 PM_SLOP + 1; lanes D + 1 and D + 2 are idle).  Per diagonal: the
+                  // last two mismatches l1 > l2 beside the first two m1 < m2.  A finished diagonal knows l1, and with x = 3 also l2 = m2;
+                  // the others scan from the read's end (a finished one with x > 3 from its last mismatch on), as case (2) does for its
+                  // suffix.  Lane D + 1 scans diagonal D + 1 (read bases 0 .. mm - 2 lie inside the window) from the front for its first
+                  // mismatch, lane D + 2 diagonal -1 (read bases 1 .. mm - 1) from the end for its last.
+                  const bool e_hi = l == ndiag, e_lo = l == ndiag + 1;
+                  const int dg = e_lo ? -1 : l;
+                  int l1 = -1, l2 = -1, nf = 2, stop = 2, c = 0;
+                  unsigned keep = ~0u;
+                  if (mine)
+                    {
+                      if (finished)
+                        {
+                          l1 = mlast;
+                          if (mism == 3)
+                            l2 = m2;
+                          else
+                            {
+                              nf = 1;
+                              c = mlast >> 3;
+                              keep = (1u << (mlast & 7)) - 1u;
+                            }
+                        }
+                      else
+                        {
+                          nf = 0;
+                          c = nch - 1;
+                        }
+                    }
+                  else if (e_hi || e_lo)
+                    {
+                      nf = 0;
+                      stop = 1;
+                      c = e_lo ? nch - 1 : 0;
+                    }
+                  while (nf < stop && c >= 0 && c < nch)
+                    {
+                      unsigned mk = piece_mask (dg, c) & keep;
+                      keep = ~0u;
+                      if (dg < 0 && c == 0)
+                        mk &= ~1u;        // (read base 0 is not on diagonal -1)
+                      while (mk != 0u && nf < stop)
+                        {
+                          const int bit = e_hi ? __ffs ((int) mk) - 1 : 31 - __clz ((int) mk);
+                          mk &= ~(1u << bit);
+                          if (nf == 0)
+                            l1 = 8 * c + bit;
+                          else
+                            l2 = 8 * c + bit;
+                          nf++;
+                        }
+                      c += e_hi ? 1 : -1;
+                    }
+                  // p0 / p1: the longest prefix with no / at most one mismatch, s0 / s1 the same for suffixes; the edge diagonals
+                  // have p0 (D + 1) and s0 (-1) only, at most mm - 1
+                  const int p0 = mine ? m1 : e_hi ? (l1 < 0 ? mm - 1 : min (l1, mm - 1)) : 0, p1 = mine ? m2 : 0;
+                  const int s0 = (mine || e_lo) ? mm - 1 - max (l1, 0) : 0, s1 = mine ? mm - 1 - l2 : 0;
+                  // (a) one deletion and at most one mismatch: prefix maxima over the earlier diagonals
+                  int pm0 = p0, pm1 = p1;
+                  for (int s = 1; s < 32; s <<= 1)
+                    {
+                      const int v0 = __shfl_up (pm0, s), v1 = __shfl_up (pm1, s);
+                      if (l >= s)
+                        {
+                          pm0 = max (pm0, v0);
+                          pm1 = max (pm1, v1);
+                        }
+                    }
+                  int b0 = __shfl_up (pm0, 1), b1 = __shfl_up (pm1, 1), sprev = __shfl_up (s0, 1);
+                  const int lo = __shfl_up (p0, 1), hi = __shfl_down (l1, 1) + 1;
+                  const int s_edge = __shfl (s0, half + ndiag + 1);
+                  if (l == 0)
+                    {
+                      b0 = b1 = 0;
+                      sprev = s_edge;
+                    }
+                  bool bad = mine && (b0 + s1 >= mm || b1 + s0 >= mm);
+                  // (b) one inserted read base and no mismatch: the prefix on diagonal l, the suffix on diagonal l - 1
+                  bad |= l <= ndiag && p0 + sprev >= mm - 1;
+                  // (c) two one-base deletions and no mismatch: diagonal l between the prefix of l - 1 and the suffix of l + 1
+                  if (l >= 1 && l <= ndiag - 2)
+                    {
+                      bool dirty = false;
+                      if (lo < hi)
+                        {
+                          dirty = (m1 >= lo && m1 < hi) || (m2 >= lo && m2 < hi) || (l2 >= lo && l2 < hi) || (l1 >= lo && l1 < hi);
+                          if (!dirty && lo > m2 && hi <= l2)
+                            {
+                              // (between the second and the second-to-last mismatch, where others may lie: look)
+                              for (int cc = lo >> 3; cc <= ((hi - 1) >> 3) && !dirty; cc++)
+                                {
+                                  unsigned mk = piece_mask (l, cc);
+                                  if (lo > 8 * cc)
+                                    mk &= ~0u << (lo - 8 * cc);
+                                  if (hi < 8 * cc + 8)
+                                    mk &= (1u << (hi - 8 * cc)) - 1u;
+                                  dirty = mk != 0u;
+                                }
+                            }
+                        }
+                      bad |= !dirty;      // (an empty range is (a) already)
+                    }
+                  cmask = (unsigned) (__ballot (bad) >> half) ? 0u : c3;
+                }
+            }
         }
       // the DP's value at the end of a candidate diagonal: the left fold of the bonuses
       double sc = 0.0;
@@ -763,14 +900,15 @@ __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gapless_kernel (PmIndex ix
           if (mism >= 1)
             {
               sc = (double) m1 + miss;
-              if (mism == 2)
+              int at = m1;
+              for (int k = 1; k < mism; k++)
                 {
-                  sc = pm_add_ones (sc, m2 - m1 - 1);
+                  const int nxt = k == 1 ? m2 : mlast;      // (three mismatches: m1, m2 and the last one)
+                  sc = pm_add_ones (sc, nxt - at - 1);
                   sc = sc + miss;
-                  sc = pm_add_ones (sc, mm - m2 - 1);
+                  at = nxt;
                 }
-              else
-                sc = pm_add_ones (sc, mm - m1 - 1);
+              sc = pm_add_ones (sc, mm - at - 1);
             }
           else
             sc = (double) mm;
@@ -782,7 +920,9 @@ __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gapless_kernel (PmIndex ix
         int xmin = mism;
         for (int s = 16; s; s >>= 1)
           xmin = min (xmin, __shfl_xor (xmin, s));      // (within the half-wave)
-        const bool open = valid && cmask == 0u && l == 0;
+        // (xmin = 3 with no candidate: no diagonal has fewer)
+        const bool to_c3 = !C3 && valid && cmask == 0u && l == 0 && tasks_c3 && xmin == 3 && ndiag == 2 * PM_SLOP + 2;
+        const bool open = valid && cmask == 0u && l == 0 && !to_c3;
         const bool to_band = open && tasks_band && xmin <= PM_BAND_MAXX_, to_dp = open && !to_band;
         const unsigned long long mb = __ballot (to_band), md = __ballot (to_dp);
         if (to_band)
@@ -795,6 +935,15 @@ __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gapless_kernel (PmIndex ix
           flush_queue (q_band[wv], n_qb, tasks_band, n_tasks_band);
         if (n_qd > PM_GL_QUEUE - 2)
           flush_queue (q_dp[wv], n_qd, tasks_dp, n_tasks_dp);
+        if (!C3)
+          {
+            const unsigned long long m3 = __ballot (to_c3);
+            if (to_c3)
+              q_c3[wv][n_q3 + (int) __popcll (m3 & ((1ull << lane) - 1ull))] = (uint32_t) o;
+            n_q3 += (int) __popcll (m3);
+            if (n_q3 > PM_GL_QUEUE - 2)
+              flush_queue (q_c3[wv], n_q3, tasks_c3, n_tasks_c3);
+          }
       }
       if (valid)
         {
@@ -828,6 +977,8 @@ __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gapless_kernel (PmIndex ix
     }
   flush_queue (q_band[wv], n_qb, tasks_band, n_tasks_band);
   flush_queue (q_dp[wv], n_qd, tasks_dp, n_tasks_dp);
+  if (!C3)
+    flush_queue (q_c3[wv], n_q3, tasks_c3, n_tasks_c3);
 }
 
 __device__ __forceinline__ int pm_wave_max (int v)

@@ -11,24 +11,38 @@ SETS = {
     "r150": dict(prefix="g1", paired=True, trim=(0, 0)),
     "r100": dict(prefix="g1s", paired=False, trim=(0, 0)),
     "r250": dict(prefix="g1l", paired=True, trim=(3, 2)),      # pemapper_tsw trim_from_start=3 trim_from_end=2
+    # the genome and reads of pair_cases.py (make_golden_pair.py): one read set, two reference runs with their own parameters
+    "rpair_narrow": dict(prefix="rpair", paired=True, trim=(0, 0), genome="rpair", min_dist=150, max_dist=300, min_align=0.96),
+    "rpair_base": dict(prefix="rpair", paired=True, trim=(0, 0), genome="rpair", min_dist=0, max_dist=500, min_align=0.85),
 }
+META = {"g1": "golden.json", "rpair": "rpair.json"}
+
+
+def params(name):
+    """min_dist / max_dist / min_align of the reference run of a set"""
+    s = SETS[name]
+    return dict(min_dist=s.get("min_dist", 0), max_dist=s.get("max_dist", 500), min_align=s.get("min_align", 0.85))
+
+
+def genome_of(name):
+    return SETS[name].get("genome", "g1")
 
 
 @functools.lru_cache(maxsize=None)
-def meta():
-    with open(os.path.join(GOLD, "golden.json")) as f:
+def meta(gname="g1"):
+    with open(os.path.join(GOLD, META[gname])) as f:
         return json.load(f)
 
 
 @functools.lru_cache(maxsize=None)
-def genome():
-    names, contigs = refio.read_fasta(os.path.join(GOLD, "g1.fa.gz"))
+def genome(gname="g1"):
+    names, contigs = refio.read_fasta(os.path.join(GOLD, gname + ".fa.gz"))
     return names, contigs
 
 
 @functools.lru_cache(maxsize=None)
-def index():
-    names, contigs = genome()
+def index(gname="g1"):
+    names, contigs = genome(gname)
     mers, ukmer, ustart, cs = refio.kmer_index(contigs)
     g = np.concatenate(contigs)
     return dict(mers=mers, ukmer=ukmer, ustart=ustart, genome=g, contig_starts=cs,
@@ -91,7 +105,7 @@ def plane0_column(positions):
 
 def check_pileup_against_golden(name, counts):
     """counts: [gsize][6] u16.  Compares with the md5 / record count / column sums / sampled records of the reference run."""
-    m = meta()[name]
+    m = meta(genome_of(name))[name]
     nz = np.nonzero(counts.astype(np.int64).sum(axis=1))[0]
     rec = np.zeros(len(nz), refio.PILE_DT)
     rec["pos"] = nz

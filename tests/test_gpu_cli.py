@@ -180,3 +180,27 @@ def test_cli_maps_from_the_index_files_of_the_builder(tmp_path, monkeypatch):
     r = subprocess.run([EXE, out, str(tmp_path / "gx.sdx"), "p", f1, f2, "500", "0", "N", "0.85", "8", "200000000"], stdout=subprocess.PIPE)
     assert r.returncode == 0, r.stdout[-2000:]
     _compare("r150", out, f1, f2)
+
+
+def test_cli_distance_limits_and_threshold_from_the_command_line(tmp_path):
+    """max_dist, min_dist and min_match other than 500 0 0.85 (argv[6], argv[7], argv[9]) on the reads of pair_cases.py, which
+    put spot distances on both limits and scores on 100 * 0.96: the files of the reference's run with `300 150 N 0.96`"""
+    name = "rpair_narrow"
+    ix = fixtures.index("rpair")
+    shutil.copy(os.path.join(fixtures.GOLD, "rpair.sdx"), tmp_path / "rpair.sdx")
+    with gzip.open(tmp_path / "rpair.seq", "wb", compresslevel=1) as f:
+        f.write(ix["genome"].tobytes())
+    f1, f2 = (str(tmp_path / ("rpair_%d_.fastq.gz" % k)) for k in (1, 2))
+    for f in (f1, f2):
+        shutil.copy(os.path.join(fixtures.GOLD, os.path.basename(f)), f)
+    out = str(tmp_path / "out")
+    m = fixtures.meta("rpair")[name]
+    subprocess.check_call([EXE, out, str(tmp_path / "rpair.sdx"), "p", f1, f2, m["max_dist"], m["min_dist"], "N", m["min_match"], "8",
+                           "200000000"], stdout=subprocess.DEVNULL)
+    assert (m["max_dist"], m["min_dist"], m["min_match"]) == ("300", "150", "0.96")
+    assert np.array_equal(np.fromfile(f1 + ".mfile", dtype="<u4"), fixtures.golden_m(name, 1))
+    assert np.array_equal(np.fromfile(f2 + ".mfile", dtype="<u4"), fixtures.golden_m(name, 2))
+    pile = refio.read_pileup(out + ".pileup.gz")
+    assert len(pile) == m["pileup_records"] and refio.md5(pile) == m["pileup_md5"]
+    assert refio.read_indel(out + ".indel.txt.gz") == refio.read_indel(os.path.join(fixtures.GOLD, name + ".indel.txt.gz"))
+    assert open(out + ".summary.txt").read() == open(os.path.join(fixtures.GOLD, name + ".summary.txt")).read()

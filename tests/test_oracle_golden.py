@@ -19,12 +19,29 @@ def test_numpy_index_matches_reference_files():
     assert len(ix["genome"]) == m["seq_len"]
 
 
-@pytest.mark.parametrize("name", ["r150", "r100", "r250"])
+def test_numpy_index_matches_reference_files_pair_genome():
+    """the genome of pair_cases.py: the committed files are what the generator makes, and the numpy index is the reference's"""
+    import pair_cases
+    names, contigs = fixtures.genome("rpair")
+    g = pair_cases.genome()
+    assert names == g["names"] and all(np.array_equal(a, b) for a, b in zip(contigs, g["contigs"]))
+    for got, exp in zip(fixtures.reads("rpair_narrow"), pair_cases.reads(100)):
+        assert np.array_equal(got, exp)
+    ix = fixtures.index("rpair")
+    m = fixtures.meta("rpair")["index"]
+    assert len(ix["mers"]) == m["n_mers"] and refio.md5(ix["mers"]) == m["mdx_md5"]
+    assert refio.md5(ix["ukmer"]) == m["idx_ukmer_md5"] and refio.md5(ix["ustart"]) == m["idx_ustart_md5"]
+    lens, sdx_names, idepth = refio.read_sdx(fixtures.GOLD + "/rpair.sdx")
+    assert idepth == 16 and sdx_names == names
+    assert np.array_equal(np.cumsum([0] + lens), ix["contig_starts"]) and len(ix["genome"]) == m["seq_len"]
+
+
+@pytest.mark.parametrize("name", ["r150", "r100", "r250", "rpair_narrow", "rpair_base"])
 def test_oracle_matches_reference(name):
-    ix = fixtures.index()
+    ix = fixtures.index(fixtures.genome_of(name))
     s = fixtures.SETS[name]
     r1, l1, r2, l2 = fixtures.reads(name)
-    o = oracle_py.Oracle(ix, paired=s["paired"], min_dist=0, max_dist=500, min_align=0.85)
+    o = oracle_py.Oracle(ix, paired=s["paired"], **fixtures.params(name))
     m1, m2, mt, _, _ = o.map_batch(r1, l1, r2, l2, threads=8)
     assert np.array_equal(m1, fixtures.golden_m(name, 1))
     if s["paired"]:
@@ -43,7 +60,7 @@ def test_oracle_matches_reference(name):
     # "%g" of the averages (pemapper.c:888-890)
     assert head[3] == "%g" % (sm[1] / sm[0])
     assert head[7] == "%g" % ((sm[2] / sm[3]) if sm[3] else 0.0)
-    names, contigs = fixtures.genome()
+    names, contigs = fixtures.genome(fixtures.genome_of(name))
     gold_ins, _ = fixtures.golden_insertions(name)
     assert fixtures.ins_to_named(o.insertions(), names, contigs) == gold_ins
 

@@ -11,7 +11,13 @@ import numpy as np
 PILE_DT = np.dtype([("pos", "<u4"), ("c", "<u2", (6,))])
 
 
+_NOT_LETTER = bytes(b for b in range(256) if not (65 <= b <= 90 or 97 <= b <= 122))
+
+
 def read_fasta(path):
+    """names and upper-case letters as the reference builder takes them (index_genome_whole.c:228-252): a header is cut after its
+    last letter or digit and its white space becomes '_'; of the other lines every alphabetic character is a base, whatever else
+    stands between them (digits, '*', '-', blanks, CR) is dropped"""
     names, seqs, cur = [], [], []
     op = gzip.open if str(path).endswith(".gz") else open
     with op(path, "rb") as f:
@@ -19,10 +25,13 @@ def read_fasta(path):
             if line.startswith(b">"):
                 if names:
                     seqs.append(b"".join(cur))
-                names.append(line[1:].strip().decode())
+                head = line[1:]
+                while head and not head[-1:].isalnum():
+                    head = head[:-1]
+                names.append("".join("_" if ch.isspace() else ch for ch in head.decode()))
                 cur = []
             else:
-                cur.append(line.strip())
+                cur.append(line.translate(None, _NOT_LETTER))
     seqs.append(b"".join(cur))
     return names, [np.frombuffer(s.upper(), dtype=np.uint8) for s in seqs]
 

@@ -72,6 +72,10 @@ def test_lookup_replicas_encode_the_reference_table(dev):
     big = uk[np.nonzero((us[1:] - us[:-1]) >= 2)[0]]
     ks |= set(big[rng.integers(0, len(big), size=300)].tolist()) if len(big) else set()
     ks |= set(rng.integers(0, 1 << 32, size=100).tolist()) | {0, (1 << 32) - 1}
+    # every bucket on or over too_many_spots (one of 386 positions in this genome): the marker entries of populated buckets
+    over = uk[np.nonzero((us[1:] - us[:-1]) >= 100)[0]]
+    assert len(over) >= 1
+    ks |= set(over.tolist())
     # neighbours of a few of them: the entries the kernel reads from the same lines
     for k in list(ks)[:50]:
         for f in range(16):
@@ -96,6 +100,7 @@ def test_lookup_replicas_encode_the_reference_table(dev):
                 assert multi[o] == ln and np.array_equal(multi[o + 1:o + 1 + ln], mers[st_of[k]:st_of[k] + ln]), (k, p)
         seen[0 if ln == 0 else 1 if ln == 1 else 2 if ln < 100 else 100] += 1
     assert seen[1] > 100 and seen[2] > 100 and seen[0] > 100
+    assert seen[100] >= len(over) + 1           # (+ 1: the absent all-T k-mer, whose wrapped length is huge)
     # one whole window of replica 0 (the reference's order): emptiness agrees with the prefix table everywhere
     W = 1 << 24
     start = int(uk[len(uk) // 2]) & ~(W - 1)

@@ -54,12 +54,29 @@ struct PmChunkSet
   PmHits hits = {};
   uint32_t *wins = nullptr, *dirbuf = nullptr;
   uint32_t *walks = nullptr;    // places in `wins` of the alignments pm_walk_kernel follows
-  uint32_t *tasks_s = nullptr, *tasks_m = nullptr;      // each in quarters: all problems, those left to the DP, to the banded DP, to the gapless rule's second launch
+  uint32_t *tasks_s = nullptr, *tasks_m = nullptr;      // SW problems of the single-hit / multi-hit ends, PM_TASK_QUARTERS quarters each (task_list)
   unsigned long long *path = nullptr;   // recorded traceback steps per winning alignment
   uint16_t *nsteps = nullptr;
   PmLists lists = {};
   hipEvent_t ev_lists_ready = nullptr, ev_lists_free = nullptr, ev_walk_done = nullptr;
   uint64_t rest_id = 0;         // run serial and chunk number of the last remainder enqueued on the set (launch_rest)
+};
+
+// The timing events of a chunk (pemap_dev::evs holds PM_NEV per chunk), each recorded behind the kernel(s) it is named for, and the
+// times pemap_dev_run_stats reports (in the order of include/pemap_hip.h), each the sum over pm_intervals' rows for its slot.
+enum PmEvent
+{
+  PM_EV_LOOKUP_BEGIN, PM_EV_LOOKUP_END, PM_EV_VOTE_BEGIN, PM_EV_VOTE_END, PM_EV_SEED_END,       // the seed stage, on either stream
+  PM_EV_SW_SINGLE_END, PM_EV_SW_MULTI_END, PM_EV_SELECT_END, PM_EV_SW_REDO_END, PM_EV_WALK_END, PM_NEV       // the ALU stream
+};
+enum PmTime { PM_T_SEED, PM_T_SW_SINGLE, PM_T_SW_MULTI, PM_T_SELECT, PM_T_SW_REDO, PM_T_WALK, PM_T_LOOKUP, PM_T_VOTE, PM_NT };
+static_assert (PM_NT == 8, "pemap_dev_run_stats copies last_ms into the caller's times_ms8");
+static const struct { PmTime slot; PmEvent from, to; bool seed_too; } pm_intervals[] = {
+  // the seed stage in two rows: its look-ups (one measurement for two slots), then vote, remainder and emit (the reference layout's run on the ALU stream)
+  { PM_T_LOOKUP, PM_EV_LOOKUP_BEGIN, PM_EV_LOOKUP_END, true }, { PM_T_SEED, PM_EV_VOTE_BEGIN, PM_EV_SEED_END },
+  { PM_T_VOTE, PM_EV_VOTE_BEGIN, PM_EV_VOTE_END }, { PM_T_SW_SINGLE, PM_EV_SEED_END, PM_EV_SW_SINGLE_END },
+  { PM_T_SW_MULTI, PM_EV_SW_SINGLE_END, PM_EV_SW_MULTI_END }, { PM_T_SELECT, PM_EV_SW_MULTI_END, PM_EV_SELECT_END },
+  { PM_T_SW_REDO, PM_EV_SELECT_END, PM_EV_SW_REDO_END }, { PM_T_WALK, PM_EV_SW_REDO_END, PM_EV_WALK_END },
 };
 
 // Host ranges page-locked through pemap_dev_pin_host.  HIP's registrations are process-wide and keyed by the pointer, so the
@@ -183,7 +200,6 @@ struct pemap_dev
   uint32_t *d_m1 = nullptr, *d_m2 = nullptr;
   int *d_mtype = nullptr;
   int cap_out = 0;
-  PmCounters *d_ctr = nullptr;
   PmInsCursor *d_cur = nullptr;
   uint32_t *d_seed_scratch = nullptr;
   uint8_t *d_ins_log = nullptr;
@@ -192,9 +208,8 @@ struct pemap_dev
   // run bookkeeping
   int run_first = 0, run_n = 0;
   bool run_pending = false;     // kernels of the last run still in flight / not yet accounted
-  int run_chunks = 0, run_chunk_pairs = 0, run_L = 0;
+  int run_chunks = 0, run_L = 0;
   uint64_t run_ends = 0;
-  hipEvent_t ev[7] = {};
   // two-stream pipeline: the look-up kernel of chunk k+1 (memory stream) runs beside vote/SW/walk of chunk k
   hipStream_t stream2 = nullptr;
   int n_cus = 0;
@@ -215,7 +230,7 @@ struct pemap_dev
   int ring_cap = 0;             // rows per slot, 0 = the ring is not set up (the staged arrays hold a resident read set)
   unsigned long long ring_seq = 0;
   hipStream_t stream_h2d = nullptr;
-  float last_ms[8] = {};
+  float last_ms[PM_NT] = {};
   std::vector < uint8_t > h_ins;        // host copy of all insertion-log bytes so far
   long summary[13] = {};
 };
@@ -227,6 +242,17 @@ static inline PmPile pile_of (const pemap_dev * d)
   p.plane_words = d->pile_plane_words;
   p.genome = d->d_genome;
   return p;
+}
+
+static inline PmIndex index_of (const pemap_dev * d)   // (here and below: in the order of the struct's fields)
+{
+  return PmIndex { d->d_pos_index, d->d_mers, d->d_genome, d->d_contig_starts, d->n_mers, d->gsize, d->n_contigs, d->idepth,
+                   d->d_rep, d->d_multi, d->multi_base, d->n_rep };
+}
+
+static inline PmParams params_of (const pemap_dev * d)
+{
+  return PmParams { d->min_dist, d->max_dist, d->min_align, d->bisulfite };
 }
 
 static int fail (pemap_dev * d, const char *fmt, ...)
@@ -303,15 +329,12 @@ extern "C" int pemap_dev_create (pemap_dev ** out, int device_id)
   d->n_cus = cus;
   if (hipStreamCreateWithFlags (&d->stream, hipStreamNonBlocking) != hipSuccess)
     return fail (nullptr, "hipStreamCreate failed");
-  for (int i = 0; i < 7; i++)
-    hipEventCreate (&d->ev[i]);
   for (PmChunkSet & s : d->set)
     for (hipEvent_t * e : { &s.ev_lists_ready, &s.ev_lists_free, &s.ev_walk_done })
       if (hipEventCreateWithFlags (e, hipEventDisableTiming) != hipSuccess)
         return fail (nullptr, "hipEventCreate failed");
-  if (hipMalloc ((void **) &d->d_ctr, sizeof (PmCounters)) != hipSuccess || hipMalloc ((void **) &d->d_cur, sizeof (PmInsCursor)) != hipSuccess)
+  if (hipMalloc ((void **) &d->d_cur, sizeof (PmInsCursor)) != hipSuccess)
     return fail (nullptr, "hipMalloc failed");
-  hipMemset (d->d_ctr, 0, sizeof (PmCounters));
   hipMemset (d->d_cur, 0, sizeof (PmInsCursor));
   *out = d.release ();
   return 0;
@@ -414,7 +437,6 @@ extern "C" void pemap_dev_destroy (pemap_dev * d)
   hipFree (d->d_m1);
   hipFree (d->d_m2);
   hipFree (d->d_mtype);
-  hipFree (d->d_ctr);
   hipFree (d->d_cur);
   hipFree (d->d_seed_scratch);
   hipFree (d->d_ins_log);
@@ -433,8 +455,6 @@ extern "C" void pemap_dev_destroy (pemap_dev * d)
     }
   if (d->stream_h2d)
     hipStreamDestroy (d->stream_h2d);
-  for (int i = 0; i < 7; i++)
-    hipEventDestroy (d->ev[i]);
   for (size_t i = 0; i < d->evs.size (); i++)
     hipEventDestroy (d->evs[i]);
   hipFree (d->d_chunk_ctr);
@@ -829,6 +849,20 @@ static void pick_geom (const pemap_dev * d, int L, int *lanes, int *w)
   else { *lanes = 16; *w = 19; }
 }
 
+// f (PmInt < W > {}, PmInt < LPA > {}) for the SW geometry of reads up to L bases: one instantiation per form pick_geom can choose
+template < int N > using PmInt = std::integral_constant < int, N >;
+template < class F > static void with_sw_geom (const pemap_dev * d, int L, F f)
+{
+  int lanes, w;
+  pick_geom (d, L, &lanes, &w);
+  if (lanes == 8 && w == 13) f (PmInt < 13 > {}, PmInt < 8 > {});
+  else if (lanes == 8) f (PmInt < 19 > {}, PmInt < 8 > {});
+  else if (w == 10) f (PmInt < 10 > {}, PmInt < 16 > {});
+  else if (w == 13) f (PmInt < 13 > {}, PmInt < 16 > {});
+  else if (w == 16) f (PmInt < 16 > {}, PmInt < 16 > {});
+  else f (PmInt < 19 > {}, PmInt < 16 > {});
+}
+
 // rows of one lane's region in a direction slab: window rows + the skew steps, rounded up to the 16-step flush unit
 static int tstride_for (const pemap_dev * d, int L)
 {
@@ -848,6 +882,40 @@ static size_t slab_dwords_for (const pemap_dev * d, int L)
 static size_t dir_budget_bytes (const pemap_dev * d)
 {
   return (size_t) (d->kn.dir_budget_gb * 1073741824.0);
+}
+
+// ---- a chunk's SW problems of one kind, those of the read-ends with exactly one hit or those of the ends with several, as the DP
+// cascade (launch_cascade) sees them.  A set's task array is PM_TASK_QUARTERS quarters of task_quarter_words words: every problem
+// (written by the seed stage), then what the gapless rule leaves to the full DP, to the banded DP, and to its own second launch.
+#define PM_TASK_QUARTERS 4
+struct PmTaskList
+{
+  uint32_t *all, *dp, *band, *c3;       // band: null with PEMAP_BAND=0; c3: null below PEMAP_GAPLESS=3
+  unsigned *n_all, *n_dp, *n_band, *n_c3, *dp_next, *band_next; // the lists' lengths; the work counters of the full and the banded DP
+};
+
+static size_t task_quarter_words (int n_ends, bool multi)
+{
+  return (size_t) n_ends * (multi ? PM_MAX_HITS : 1);
+}
+
+static PmTaskList task_list (const pemap_dev * d, const PmChunkSet & S, PmCounters * ctr, bool multi)
+{
+  uint32_t *const t = multi ? S.tasks_m : S.tasks_s;
+  const size_t q = task_quarter_words (d->cap_ends, multi);
+  const bool rule = pm_gapless_on (d);
+  PmTaskList l;
+  l.all = t;
+  l.n_all = multi ? &ctr->n_tasks_m : &ctr->n_tasks_s;
+  l.dp = rule ? t + q : l.all;  // (PEMAP_GAPLESS=0: no rule, the full DP takes the seed stage's list as it is)
+  l.n_dp = !rule ? l.n_all : multi ? &ctr->n_tasks_mdp : &ctr->n_tasks_dp;
+  l.band = rule && d->kn.band ? t + 2 * q : nullptr;
+  l.c3 = rule && pm_gapless_max_x (d) >= 3 ? t + 3 * q : nullptr;
+  l.n_band = &ctr->n_band[multi];
+  l.n_c3 = &ctr->n_c3[multi];
+  l.dp_next = &ctr->sw_next[multi];
+  l.band_next = &ctr->band_next[multi];
+  return l;
 }
 
 static int alloc_hits (pemap_dev * d, PmHits & h, int n_ends)
@@ -870,14 +938,13 @@ static int ensure_work (pemap_dev * d, int n_ends)
   if (n_ends > d->cap_ends)
     {
       free_work (d);
-      const size_t nh = (size_t) n_ends * PM_MAX_HITS;
       for (PmChunkSet & s : d->set)
         {
           TRY (alloc_hits (d, s.hits, n_ends));
           TRY (dev_alloc (d, &s.wins, (size_t) n_ends));
           TRY (dev_alloc (d, &s.walks, (size_t) n_ends));
-          TRY (dev_alloc (d, &s.tasks_s, (size_t) n_ends * 4));       // second quarter: the problems left to the DP, third: to the banded DP, last: to case (3)
-          TRY (dev_alloc (d, &s.tasks_m, nh * 4));
+          TRY (dev_alloc (d, &s.tasks_s, task_quarter_words (n_ends, false) * PM_TASK_QUARTERS));
+          TRY (dev_alloc (d, &s.tasks_m, task_quarter_words (n_ends, true) * PM_TASK_QUARTERS));
         }
       TRY (dev_alloc (d, &d->d_redo, (size_t) n_ends));
       d->cap_ends = n_ends;
@@ -998,7 +1065,6 @@ struct PmChunkCtr
 };
 
 #define PM_MAX_CHUNKS 256
-#define PM_NEV 12               // events per chunk: lookup start/end, the vote kernel's end, the seed stage's end, then the ALU stream's kernel boundaries
 
 static int seg_template (int L)
 {
@@ -1045,9 +1111,9 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
   L.positions = &cc->positions;
   L.next_end = &cc->next_end;
   // (an event recorded straight after a stream wait is stamped when the wait is queued, not when it is satisfied: the empty
-  // kernel makes the stamp the moment the look-up kernel can start, so that ev[0]..ev[1] is the kernel's own duration)
+  // kernel makes the stamp the moment the look-up kernel can start, so that LOOKUP_BEGIN..LOOKUP_END is the kernel's own duration)
   hipLaunchKernelGGL (pm_nop_kernel, dim3 (1), dim3 (1), 0, st);
-  hipEventRecord (ev[0], st);
+  hipEventRecord (ev[PM_EV_LOOKUP_BEGIN], st);
   // PEMAP_LOOKUP_WAVES=n: n persistent one-wave workgroups per CU.  Default 9 (pm_seed4_kernel: 14.6 KB of LDS and 128 VGPRs a wave): 8
   // steps of the default workload take 23.4 / 21.3 / 20.7 / 21.3 ms each on resident reads with 7 / 8 / 9 / 10 (profiles/r04_ab_sweeps.txt;
   // the third form, 19.6 KB and 168 VGPRs, took 25.2 at its best, 7) -- the kernel itself keeps gaining (5.06 / 4.53 / 4.05 / 3.84 ms per
@@ -1082,7 +1148,7 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
       {
         hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_lookup_wave_kernel < sm.value, 4 >), dim3 (lgrid), dim3 (64), 0, st, c.ix, c.b, c.prm, L, lprio);
       });
-      hipEventRecord (ev[1], st);
+      hipEventRecord (ev[PM_EV_LOOKUP_END], st);
       return;
     }
   // the fused seed kernel's first tier, then its second tier over the ends the first passed over: the same kernel with four times
@@ -1097,16 +1163,16 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
   {
     hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed4_kernel < sm.value, 0 >), dim3 (lgrid), dim3 (64), sizeof (PmSeed4Shared < sm.value, 0 >), st, c.ix, c.b,
                         c.prm, H, L, (const uint32_t *) nullptr, (const unsigned *) nullptr, lprio);
-    hipEventRecord (ev[1], st);
+    hipEventRecord (ev[PM_EV_LOOKUP_END], st);
     hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed4_kernel < sm.value, 1 >), dim3 (grid2), dim3 (64), sizeof (PmSeed4Shared < sm.value, 1 >), st, c.ix, c.b,
                         c.prm, H, L2, (const uint32_t *) L.big_list, (const unsigned *) L.n_big, lprio);
   });
   // the vote is part of the kernel: its interval is empty
-  hipEventRecord (ev[2], st);
-  hipEventRecord (ev[3], st);
+  hipEventRecord (ev[PM_EV_VOTE_BEGIN], st);
+  hipEventRecord (ev[PM_EV_VOTE_END], st);
 }
 
-// ---- the reference layout's vote kernel on the set's lists; ev[2]..ev[3] is its own interval
+// ---- the reference layout's vote kernel on the set's lists; VOTE_BEGIN..VOTE_END is its own interval
 static void launch_vote (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
 {
   PmLists L = S.lists;
@@ -1121,12 +1187,12 @@ static void launch_vote (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChun
   if (vgrid > c.b.n_ends)
     vgrid = c.b.n_ends;
   hipLaunchKernelGGL (pm_nop_kernel, dim3 (1), dim3 (1), 0, st);
-  hipEventRecord (ev[2], st);
+  hipEventRecord (ev[PM_EV_VOTE_BEGIN], st);
   with_seg_template (c.L, [&] (auto sm)
   {
     hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_vote_wave_kernel < sm.value >), dim3 (vgrid), dim3 (64), 0, st, c.ix, c.b, c.prm, H, L, vprio);
   });
-  hipEventRecord (ev[3], st);
+  hipEventRecord (ev[PM_EV_VOTE_END], st);
 }
 
 // ---- the big-end remainder: pm_seed_kernel over the read-ends the look-up / vote kernels (the fused kernel's second tier) passed
@@ -1157,11 +1223,11 @@ static void launch_rest (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChun
   hipEventRecord (S.ev_lists_free, st);
 }
 
-// ---- the emit kernel (windows, slab numbers, SW task lists); the seed stage ends at ev[10]
+// ---- the emit kernel (windows, slab numbers, SW task lists); the seed stage ends here
 static void launch_emit (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
 {
   hipLaunchKernelGGL (pm_emit_kernel, dim3 ((c.b.n_ends + 63) / 64), dim3 (64), 0, st, c.ix, c.b, S.hits, S.tasks_s, S.tasks_m, &cc->c);
-  hipEventRecord (ev[10], st);
+  hipEventRecord (ev[PM_EV_SEED_END], st);
 }
 
 // ---- the seed stream's work for chunk g (the chunk's rows in c.b)
@@ -1193,15 +1259,51 @@ static int enqueue_seed (pemap_dev * d, const PmSchedule & s, const RunCtx & c, 
   return 0;
 }
 
+// ---- the DP cascade over one task list, on the ALU stream: the gapless rule, its second launch for case (3), the banded DP, the full
+//      DP.  DIRS: the single-hit ends' list, scored with direction nibbles (the multi-hit ends' problems get scores only; a winner the
+//      rule decided is not scored again).  (`auto`: instantiated where launch_chunk names it, which keeps the kernels' order in the code object)
+template < int W, int LPA, bool DIRS > static auto launch_cascade (pemap_dev * d, const RunCtx & c, const PmChunkSet & S, PmCounters * ctr, const PmTaskList & l)
+{
+  const int n_ends = c.b.n_ends, max_x = pm_gapless_max_x (d);
+  // the multi-hit list's rule and band launches fill the device; the single-hit list holds at most one problem per read-end
+  int ggrid = d->n_cus * 16, bgrid = d->n_cus * d->kn.band_waves_per_cu;
+  if (DIRS)
+    {
+      // The rule's kernel and the NEXT chunk's seed kernel are launched at the same moment (both wait for this chunk's seed kernel), and
+      // whichever gets its waves onto the SIMDs first keeps them: the seed kernel's persistent waves need 168 registers each, six of
+      // this kernel's fill a SIMD's 512.  For reads of up to 160 bases 24 workgroups per CU are the measured optimum (the seed
+      // kernel's launch is short of its 7 waves per CU for 0.4 ms at most); for longer reads the seed kernel's launches are twice
+      // as long, its waves came up late on many CUs, and the step was 69 ms with 12 or more against 54 with 6 (2 x 245 bases:
+      // profiles/r03_ab_sweeps.txt; round 2's 256-thread workgroups had hidden this: they rarely found room at all)
+      const int gbp = d->kn.gapless_blocks_per_cu > 0 ? d->kn.gapless_blocks_per_cu : (seg_template (c.L) <= 10 ? 24 : 6);
+      ggrid = (n_ends + PM_GL_PER_BLOCK - 1) / PM_GL_PER_BLOCK;
+      if (ggrid > d->n_cus * gbp)
+        ggrid = d->n_cus * gbp;
+      if (bgrid > (n_ends + 15) / 16)
+        bgrid = (n_ends + 15) / 16;
+    }
+  if (pm_gapless_on (d))
+    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < false >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, S.hits, l.all, l.n_all,
+                        l.dp, l.n_dp, max_x, l.band, l.n_band, l.c3, l.n_c3);
+  // case (3) in a launch of its own over the problems it may decide (one in eight; what it refuses joins the DP's lists)
+  if (l.c3)
+    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < true >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, S.hits, l.c3, l.n_c3,
+                        l.dp, l.n_dp, max_x, l.band, l.n_band, (uint32_t *) nullptr, (unsigned *) nullptr);
+  // the problems the rule left open whose best diagonal has few mismatches: the DP restricted to a band of 32 diagonals,
+  // four lanes per problem (pemap_band.hip.h); what is left for pm_sw_kernel are mostly the reads with a real indel
+  if (l.band)
+    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_band_kernel < DIRS >), dim3 (bgrid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, S.hits, l.band, l.n_band, ctr,
+                        S.dirbuf, slab_dwords_for (d, c.L), l.band_next);
+  hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, DIRS >), dim3 (d->sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, S.hits, l.dp, l.n_dp, ctr,
+                      S.dirbuf, S.dirbuf + c.dump_off, c.tstride, c.L, d->kn.sw_prio, l.dp_next);
+}
+
 // ---- the ALU stream's work for one chunk: the rest of the seed stage, SW, selection, traceback.
 template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSchedule & s, const RunCtx & c, uint32_t * m1, uint32_t * m2, int *mt,
                                              PmChunkSet & S, PmChunkCtr * cc, hipEvent_t * ev)
 {
-  const int swprio = d->kn.sw_prio;
   const PmHits & H = S.hits;
-  uint32_t *wins = S.wins, *dirbuf = S.dirbuf, *tasks_s = S.tasks_s, *tasks_m = S.tasks_m;
-  uint32_t *dump_slab = dirbuf + c.dump_off;
-  const int n_ends = c.b.n_ends;
+  uint32_t *wins = S.wins, *dirbuf = S.dirbuf;
   PmCounters *ctr = &cc->c;
   if (!pm_fused (d))
     {
@@ -1211,98 +1313,33 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
     }
   else if (s.emit_on_alu)
     launch_emit (d, c, S, cc, ev, d->stream);
-  if (pm_gapless_on (d))
-    {
-      uint32_t *tasks_dp = tasks_s + d->cap_ends;
-      uint32_t *tasks_band = d->kn.band ? tasks_s + 2 * (size_t) d->cap_ends : nullptr;
-      int ggrid = (n_ends + PM_GL_PER_BLOCK - 1) / PM_GL_PER_BLOCK;
-      // The rule's kernel and the NEXT chunk's seed kernel are launched at the same moment (both wait for this chunk's seed kernel), and
-      // whichever gets its waves onto the SIMDs first keeps them: the seed kernel's persistent waves need 168 registers each, six of
-      // this kernel's fill a SIMD's 512.  For reads of up to 160 bases 24 workgroups per CU are the measured optimum (the seed
-      // kernel's launch is short of its 7 waves per CU for 0.4 ms at most); for longer reads the seed kernel's launches are twice
-      // as long, its waves came up late on many CUs, and the step was 69 ms with 12 or more against 54 with 6 (2 x 245 bases:
-      // profiles/r03_ab_sweeps.txt; round 2's 256-thread workgroups had hidden this: they rarely found room at all)
-      const int gbp = d->kn.gapless_blocks_per_cu > 0 ? d->kn.gapless_blocks_per_cu : (seg_template (c.L) <= 10 ? 24 : 6);
-      if (ggrid > d->n_cus * gbp)
-        ggrid = d->n_cus * gbp;
-      // case (3) in a launch of its own over the problems it may decide (one in eight; what it refuses joins the DP's lists)
-      uint32_t *tasks_c3 = pm_gapless_max_x (d) >= 3 ? tasks_s + 3 * (size_t) d->cap_ends : nullptr;
-      hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < false >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, H, tasks_s,
-                          &ctr->n_tasks_s, tasks_dp, &ctr->n_tasks_dp, pm_gapless_max_x (d), tasks_band, &ctr->n_band[0], tasks_c3, &ctr->n_c3[0]);
-      if (tasks_c3)
-        hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < true >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, H, tasks_c3,
-                            &ctr->n_c3[0], tasks_dp, &ctr->n_tasks_dp, pm_gapless_max_x (d), tasks_band, &ctr->n_band[0], (uint32_t *) nullptr,
-                            (unsigned *) nullptr);
-      if (tasks_band)
-        {
-          // the problems the rule left open whose best diagonal has few mismatches: the DP restricted to a band of 32 diagonals,
-          // four lanes per problem (pemap_band.hip.h); what is left for pm_sw_kernel are mostly the reads with a real indel
-          int bgrid = (n_ends + 15) / 16;
-          if (bgrid > d->n_cus * d->kn.band_waves_per_cu)
-            bgrid = d->n_cus * d->kn.band_waves_per_cu;
-          hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_band_kernel < true >), dim3 (bgrid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H, tasks_band,
-                              &ctr->n_band[0], ctr, dirbuf, slab_dwords_for (d, c.L), &ctr->band_next[0]);
-        }
-      hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, true >), dim3 (d->sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H,
-                          tasks_dp, &ctr->n_tasks_dp, ctr, dirbuf, dump_slab, c.tstride, c.L, swprio, &ctr->sw_next[0]);
-    }
-  else
-    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, true >), dim3 (d->sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H,
-                        tasks_s, &ctr->n_tasks_s, ctr, dirbuf, dump_slab, c.tstride, c.L, swprio, &ctr->sw_next[0]);
-  hipEventRecord (ev[4], d->stream);
-  if (pm_gapless_on (d))
-    {
-      // the same rule on the problems of the multi-hit ends (scores only; a winner it decided is not scored again);
-      // sw_next[3] counts what is left to the DP
-      uint32_t *tasks_mdp = tasks_m + (size_t) d->cap_ends * PM_MAX_HITS;
-      uint32_t *tasks_mband = d->kn.band ? tasks_m + 2 * (size_t) d->cap_ends * PM_MAX_HITS : nullptr;
-      uint32_t *tasks_mc3 = pm_gapless_max_x (d) >= 3 ? tasks_m + 3 * (size_t) d->cap_ends * PM_MAX_HITS : nullptr;
-      hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < false >), dim3 (d->n_cus * 16), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, H, tasks_m,
-                          &ctr->n_tasks_m, tasks_mdp, &ctr->sw_next[3], pm_gapless_max_x (d), tasks_mband, &ctr->n_band[1], tasks_mc3, &ctr->n_c3[1]);
-      if (tasks_mc3)
-        hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < true >), dim3 (d->n_cus * 16), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, H, tasks_mc3,
-                            &ctr->n_c3[1], tasks_mdp, &ctr->sw_next[3], pm_gapless_max_x (d), tasks_mband, &ctr->n_band[1], (uint32_t *) nullptr,
-                            (unsigned *) nullptr);
-      if (tasks_mband)
-        hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_band_kernel < false >), dim3 (d->n_cus * d->kn.band_waves_per_cu), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H,
-                            tasks_mband, &ctr->n_band[1], ctr, dirbuf, slab_dwords_for (d, c.L), &ctr->band_next[1]);
-      hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, false >), dim3 (d->sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H,
-                          tasks_mdp, &ctr->sw_next[3], ctr, dirbuf, dump_slab, c.tstride, c.L, swprio, &ctr->sw_next[1]);
-    }
-  else
-    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, false >), dim3 (d->sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H,
-                        tasks_m, &ctr->n_tasks_m, ctr, dirbuf, dump_slab, c.tstride, c.L, swprio, &ctr->sw_next[1]);
-  hipEventRecord (ev[5], d->stream);
+  launch_cascade < W, LPA, true > (d, c, S, ctr, task_list (d, S, ctr, false));
+  hipEventRecord (ev[PM_EV_SW_SINGLE_END], d->stream);
+  launch_cascade < W, LPA, false > (d, c, S, ctr, task_list (d, S, ctr, true));
+  hipEventRecord (ev[PM_EV_SW_MULTI_END], d->stream);
   hipLaunchKernelGGL (pm_select_kernel, dim3 ((c.b.n + 63) / 64), dim3 (64), 0, d->stream, c.b, c.prm, H, d->d_redo, wins, S.walks,
                       ctr, m1, m2, mt);
-  hipEventRecord (ev[6], d->stream);
+  hipEventRecord (ev[PM_EV_SELECT_END], d->stream);
   hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, true >), dim3 (d->sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H,
-                      d->d_redo, &ctr->n_redo, ctr, dirbuf, dump_slab, c.tstride, c.L, swprio, &ctr->sw_next[2]);
-  hipEventRecord (ev[7], d->stream);
-  hipEventRecord (ev[9], d->stream);
+                      d->d_redo, &ctr->n_redo, ctr, dirbuf, dirbuf + c.dump_off, c.tstride, c.L, d->kn.sw_prio, &ctr->sw_next[2]);
+  hipEventRecord (ev[PM_EV_SW_REDO_END], d->stream);
   // PEMAP_WALK_BLOCKS_PER_CU (default 4, swept 1..16): resident 256-lane blocks of the walk per CU; few enough walkers that
   // their direction lines stay in L2 between steps
   const int wbp = d->kn.walk_blocks_per_cu;
-  int wgrid = (n_ends + 63) / 64;
+  int wgrid = (c.b.n_ends + 63) / 64;
   if (wgrid > d->n_cus * wbp * 4)
     wgrid = d->n_cus * wbp * 4;         // (waves: the knob counts blocks of four)
-  // (the walk on the look-up stream, beside the next chunk's vote and SW, was tried: 107 ms per step against 103; it stays on the ALU
-  // stream)
-  hipStream_t ws = d->stream;
-  unsigned long long *path = S.path;
-  uint16_t *nsteps = S.nsteps;
-  hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_walk_kernel < W, LPA >), dim3 (wgrid), dim3 (64), 0, ws, c.b, H, wins, S.walks, ctr, d->d_cur,
-                      dirbuf, c.tstride, pile_of (d), d->d_ins_log, d->ins_cap, path, d->path_words, nsteps);
-  {
-    // one wave per winning alignment applies the recorded steps to the pileup
-    const int pbp = d->kn.pile_blocks_per_cu;
-    int pgrid = n_ends;
-    if (pgrid > d->n_cus * pbp * 4)
-      pgrid = d->n_cus * pbp * 4;       // (waves: the knob counts blocks of four)
-    hipLaunchKernelGGL (pm_pile_kernel, dim3 (pgrid), dim3 (64), 0, ws, c.b, H, wins, ctr, pile_of (d), path, d->path_words, nsteps);
-  }
-  hipEventRecord (ev[8], ws);
-  hipEventRecord (S.ev_walk_done, ws);
+  // (the walk on the look-up stream, beside the next chunk's vote and SW, was tried: 107 ms per step against 103; it stays here)
+  hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_walk_kernel < W, LPA >), dim3 (wgrid), dim3 (64), 0, d->stream, c.b, H, wins, S.walks, ctr, d->d_cur,
+                      dirbuf, c.tstride, pile_of (d), d->d_ins_log, d->ins_cap, S.path, d->path_words, S.nsteps);
+  // one wave per winning alignment applies the recorded steps to the pileup
+  const int pbp = d->kn.pile_blocks_per_cu;
+  int pgrid = c.b.n_ends;
+  if (pgrid > d->n_cus * pbp * 4)
+    pgrid = d->n_cus * pbp * 4;         // (waves: the knob counts blocks of four)
+  hipLaunchKernelGGL (pm_pile_kernel, dim3 (pgrid), dim3 (64), 0, d->stream, c.b, H, wins, ctr, pile_of (d), S.path, d->path_words, S.nsteps);
+  hipEventRecord (ev[PM_EV_WALK_END], d->stream);
+  hipEventRecord (S.ev_walk_done, d->stream);
 }
 
 // wait for the run in flight and fold its chunks' counters and kernel times into the run's totals
@@ -1343,7 +1380,7 @@ static int absorb_run (pemap_dev * d)
       t.n_tasks_s += c.n_tasks_s;
       t.n_tasks_m += c.n_tasks_m;
       t.n_tasks_dp += pm_gapless_on (d) ? c.n_tasks_dp : c.n_tasks_s;
-      t.sw_next[3] += pm_gapless_on (d) ? c.sw_next[3] : c.n_tasks_m;
+      t.n_tasks_mdp += pm_gapless_on (d) ? c.n_tasks_mdp : c.n_tasks_m;
       t.n_band[0] += c.n_band[0];
       t.n_band[1] += c.n_band[1];
       t.cells_band += c.cells_band;
@@ -1360,18 +1397,12 @@ static int absorb_run (pemap_dev * d)
       d->last_big2 += hc[k].n_big2;
       hipEvent_t *ev = &d->evs[(size_t) k * PM_NEV];
       float ms = 0.f;
-      if (hipEventElapsedTime (&ms, ev[0], ev[1]) == hipSuccess)
-        {
-          d->last_ms[0] += ms;
-          d->last_ms[6] += ms;
-        }
-      if (hipEventElapsedTime (&ms, ev[2], ev[10]) == hipSuccess)
-        d->last_ms[0] += ms;
-      if (hipEventElapsedTime (&ms, ev[2], ev[3]) == hipSuccess)
-        d->last_ms[7] += ms;
-      for (int i = 1; i < 6; i++)
-        if (hipEventElapsedTime (&ms, (i == 1) ? ev[10] : ev[2 + i], (i == 4) ? ev[9] : ev[3 + i]) == hipSuccess)
-          d->last_ms[i] += ms;
+      for (const auto & iv : pm_intervals)
+        if (hipEventElapsedTime (&ms, ev[iv.from], ev[iv.to]) == hipSuccess)
+          {
+            d->last_ms[iv.slot] += ms;
+            d->last_ms[PM_T_SEED] += iv.seed_too ? ms : 0.f;
+          }
     }
   if (d->last_cur.ins_overflow)
     return fail (d, "insertion log overflow (%u bytes): lower PEMAP_CHUNK_PAIRS or map smaller slices", d->ins_cap);
@@ -1485,22 +1516,8 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
   s.seed = s.ahead ? d->stream2 : d->stream;
   s.emit_on_alu = s.ahead && pm_fused (d) && seg_template (L) <= 10;
   RunCtx c;
-  c.ix.pos_index = d->d_pos_index;
-  c.ix.mers = d->d_mers;
-  c.ix.genome = d->d_genome;
-  c.ix.contig_starts = d->d_contig_starts;
-  c.ix.n_mers = d->n_mers;
-  c.ix.gsize = d->gsize;
-  c.ix.n_contigs = d->n_contigs;
-  c.ix.idepth = d->idepth;
-  c.ix.rep = d->d_rep;
-  c.ix.multi = d->d_multi;
-  c.ix.multi_base = d->multi_base;
-  c.ix.n_rep = d->n_rep;
-  c.prm.min_dist = d->min_dist;
-  c.prm.max_dist = d->max_dist;
-  c.prm.min_align = d->min_align;
-  c.prm.bisulfite = d->bisulfite;
+  c.ix = index_of (d);
+  c.prm = params_of (d);
   c.L = L;
   c.tstride = tstride_for (d, L);
   // (the last slab of the allocation, whatever this run's chunk size: chunks of earlier, larger runs may still be in flight)
@@ -1517,7 +1534,6 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
   d->run_n = n;
   d->run_ends += (uint64_t) n * per;
   d->run_chunks = k0 + nch;
-  d->run_chunk_pairs = chunk;
   d->run_L = L;
   // fresh per-chunk counters: zeroed on the stream that touches them first (the seed stream, so that a queued run's first
   // look-ups do not wait for the previous run's ALU work)
@@ -1560,27 +1576,10 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
       HIPCHK (d, hipStreamWaitEvent (d->stream, S.ev_lists_ready, 0));
       uint32_t *m1 = d->d_m1 + f, *m2 = d->paired ? d->d_m2 + f : nullptr;
       int *mt = d->d_mtype + f;
+      with_sw_geom (d, L, [&] (auto w, auto lanes)
       {
-        int lanes, w;
-        pick_geom (d, L, &lanes, &w);
-#define PM_CH(WW, LL) launch_chunk < WW, LL > (d, s, c, m1, m2, mt, S, cc, ev)
-        if (lanes == 8)
-          {
-            if (w == 13)
-              PM_CH (13, 8);
-            else
-              PM_CH (19, 8);
-          }
-        else
-          switch (w)
-            {
-            case 10: PM_CH (10, 16); break;
-            case 13: PM_CH (13, 16); break;
-            case 16: PM_CH (16, 16); break;
-            default: PM_CH (19, 16); break;
-            }
-#undef PM_CH
-      }
+        launch_chunk < w.value, lanes.value > (d, s, c, m1, m2, mt, S, cc, ev);
+      });
       HIPCHK (d, hipGetLastError ());
       if (s.ahead && k + PM_SETS < nch)
         TRY (enqueue_seed_k (k + PM_SETS));
@@ -2090,7 +2089,7 @@ extern "C" int pemap_dev_run_stats (pemap_dev * d, uint64_t * s, float *t)
       s[9] = c.n_redo;
       s[10] = d->last_big;
       s[11] = (uint64_t) d->run_chunks;
-      s[12] = ((uint64_t) c.n_tasks_s - c.n_tasks_dp - c.n_band[0]) + ((uint64_t) c.n_tasks_m - c.sw_next[3] - c.n_band[1]);
+      s[12] = ((uint64_t) c.n_tasks_s - c.n_tasks_dp - c.n_band[0]) + ((uint64_t) c.n_tasks_m - c.n_tasks_mdp - c.n_band[1]);
       s[13] = (uint64_t) c.n_band[0] + c.n_band[1];
       s[14] = c.cells_band;
       s[15] = d->last_big2;

@@ -105,7 +105,8 @@ struct PmCounters
   unsigned long long cells_dirs;
   unsigned long long pile_incs;
   unsigned long long n_ins;
-  unsigned int sw_next[4];         // work counters of the three SW launches of a chunk (single-hit, multi-hit, redo)
+  unsigned int sw_next[3];         // work counters of the three SW launches of a chunk (single-hit, multi-hit, redo)
+  unsigned int n_tasks_mdp;        // multi-hit problems the gapless rule leaves to the DP
   unsigned int n_band[2];          // problems left to the banded DP (pm_band_kernel): single-hit ends, multi-hit ends
   unsigned int band_next[2];       // their work counters
   unsigned int n_c3[2];            // problems the gapless rule's first launch leaves to its second (case (3)): single-hit ends, multi-hit ends

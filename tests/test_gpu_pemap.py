@@ -113,6 +113,30 @@ def test_lookup_replicas_encode_the_reference_table(dev):
     assert np.array_equal(win[one], mers[pi[:-1][one]])
 
 
+def test_run_stats_times_cover_every_stage(dev):
+    """the eight kernel times of run_stats (pemap_hip.h) are sums of event intervals of the run's chunks; an interval between
+    a wrong pair of events fails silently and leaves 0.  Every stage that launches a kernel must show a time, and the seed
+    stage's time holds its look-ups' (and, with the reference's table layout, the vote kernel's, which the fused seed kernel
+    does not have) whatever the GPU's speed: the intervals are nested.  (Replicas 8 first: the layout the test before leaves.)"""
+    r1, l1, r2, l2 = fixtures.reads("r150")
+    dev.set_params(paired=True, min_dist=0, max_dist=500, min_align=0.85)
+    for replicas in (8, 0):
+        dev.set_lookup_replicas(replicas)
+        dev.reset_pileup()
+        dev.map_batch(r1, l1, r2, l2)
+        _, t = dev.run_stats()
+        print(replicas, t)
+        assert sorted(t) == sorted(["seed", "sw_single", "sw_multi", "select", "sw_redo", "walk", "lookup", "vote"])
+        assert all(np.isfinite(v) and v >= 0 for v in t.values()), t
+        if replicas == 8:
+            for k in ("seed", "lookup", "sw_single", "sw_multi", "select", "sw_redo", "walk"):
+                assert t[k] > 0, (k, t)
+            assert t["seed"] >= t["lookup"], t
+        else:
+            assert t["vote"] > 0, t
+            assert t["seed"] >= t["lookup"] + t["vote"], t
+
+
 @pytest.mark.parametrize("replicas", [8, 0])
 @pytest.mark.parametrize("name", ["r150", "r100", "r250"])
 def test_map_matches_reference_golden(dev, name, replicas):
@@ -438,8 +462,9 @@ print("full dp ok")
     here = os.path.dirname(os.path.abspath(__file__))
     # the full DP in the default pipeline (8 lanes x 19 columns per alignment for 150 bases); the gapless rule without the banded
     # DP behind it (what the rule leaves goes to the full DP, 16 lanes x 10); the two-stream pipeline's kernels on ONE stream; and
-    # the same on the reference's table layout (the schedule no other test runs)
-    for extra in (dict(PEMAP_GAPLESS="0"), dict(PEMAP_BAND="0"), dict(PEMAP_PIPELINE="2"), dict(PEMAP_PIPELINE="2", PEMAP_REPLICAS="0")):
+    # the same on the reference's table layout (the schedule no other test runs); and the rule with its first case only
+    for extra in (dict(PEMAP_GAPLESS="0"), dict(PEMAP_BAND="0"), dict(PEMAP_PIPELINE="2"), dict(PEMAP_PIPELINE="2", PEMAP_REPLICAS="0"),
+                  dict(PEMAP_GAPLESS="1")):
         env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(here), here]), **extra)
         r = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
         assert r.returncode == 0 and b"full dp ok" in r.stdout, (extra, r.stdout[-2000:])

@@ -109,7 +109,14 @@ int pemap_dev_lookup_replicas (pemap_dev * dev, int *n_replicas, uint64_t * reco
  * 5 the look-up replicas (u32[8][2^32]; replica p holds the entry of k-mer k at k with its 4-bit fields 0 and p
  * swapped), 6 the records of the multi-position buckets (16-byte units {count, positions...}); 5 and 6 are empty
  * (n_bytes = 0) when no replicas are in use.
- * For collectives (broadcast of 0..3 at start-up, sum of 4 at the end) and for copying the index back to the host. */
+ * For collectives (broadcast of 0..3 at start-up, sum of 4 at the end) and for copying the index back to the host.
+ * Buffer 4 while the object maps: its first plane then holds differences of neighbouring counters, not counts (two atomics per
+ * run of matched bases instead of one per word), and is turned back into counts -- a scan over the plane, waited for -- by
+ * pemap_dev_buffer (which = 4) and pemap_dev_read_buffer through it, pemap_dev_fetch_pileup, pemap_dev_fetch_records,
+ * pemap_dev_absorb (both objects) and pemap_dev_map_batch before it returns; NOT by pemap_dev_run, pemap_dev_run_slice,
+ * pemap_dev_sync, pemap_dev_submit_batch or pemap_dev_wait_batch.  So the view of buffer 4 holds counts when it is obtained, and
+ * again after every pemap_dev_map_batch; a view kept across asynchronous runs (run / run_slice / submit_batch) must be obtained
+ * again before it is read.  A caller may write counts into the view while nothing is in flight and the view holds counts. */
 int pemap_dev_buffer (pemap_dev * dev, int which, void **d_ptr, uint64_t * n_bytes);
 int pemap_dev_index_info (pemap_dev * dev, uint64_t * n_mers, uint64_t * genome_size, int *n_contigs, int *idepth);
 /* copy one of the buffers above (or a byte range of it) to host memory */

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pemap_pile_add.h"
+#include "pemap_pile_diff.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // Index build.  index_genome_whole.c:206-299: a rolling 32-bit 2-bit-per-base register over each contig; 'N' resets
@@ -547,6 +548,110 @@ __global__ __launch_bounds__ (PA_BLOCK) void pm_pile_add_kernel (uint4 * __restr
       r.z = pm_add_u16x2 (a.z, b.z);
       r.w = pm_add_u16x2 (a.w, b.w);
       dst[i] = r;
+    }
+}
+
+// ---- plane 0 between its two forms (pemap_pile_diff.h), in place, over all n_words words of the plane, padding included.  A tile is
+// PD_TILE words, one 16-byte vector per lane of a 256-lane block; n_words is a multiple of 64, so there is no partial vector.
+#define PD_BLOCK 256
+#define PD_TILE (PD_BLOCK * 4)
+// exclusive sums over the block's lanes, modulo 2^32 (the callers keep the low 16 bits); s_wave: one word per wave
+__device__ __forceinline__ uint32_t pd_block_exclusive (uint32_t mine, uint32_t * s_wave)
+{
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint32_t inc = mine;
+  for (int o = 1; o < 64; o <<= 1)
+    {
+      const uint32_t t = __shfl_up (inc, o);
+      if (lane >= o)
+        inc += t;
+    }
+  if (lane == 63)
+    s_wave[wv] = inc;
+  __syncthreads ();
+  uint32_t before = 0;
+  for (int k = 0; k < wv; k++)
+    before += s_wave[k];
+  return before + inc - mine;
+}
+
+// counts -> differences, first half: the count in front of every tile (the high half of the word before it), saved before the
+// tile in front is overwritten
+__global__ __launch_bounds__ (PD_BLOCK) void pd_unfold_save_kernel (const uint32_t * w, uint64_t n_tiles, uint32_t * tile_prev)
+{
+  for (uint64_t t = (uint64_t) blockIdx.x * PD_BLOCK + threadIdx.x; t < n_tiles; t += (uint64_t) gridDim.x * PD_BLOCK)
+    tile_prev[t] = t ? w[t * PD_TILE - 1] >> 16 : 0u;
+}
+
+// second half: every word of a tile is read (with the word in front of each vector) before any word of it is written
+__global__ __launch_bounds__ (PD_BLOCK) void pd_unfold_apply_kernel (uint32_t * w, uint64_t n_words, const uint32_t * tile_prev)
+{
+  const uint64_t at = (uint64_t) blockIdx.x * PD_TILE + (uint64_t) threadIdx.x * 4;
+  const bool in = at < n_words;
+  uint4 v = make_uint4 (0u, 0u, 0u, 0u);
+  uint32_t prev = 0;
+  if (in)
+    {
+      v = *(const uint4 *) (w + at);
+      prev = threadIdx.x ? w[at - 1] >> 16 : tile_prev[blockIdx.x];
+    }
+  asm volatile ("s_waitcnt vmcnt(0)":::"memory");        // the loads have landed, not merely been issued, when the barrier opens
+  __syncthreads ();
+  if (in)
+    {
+      uint4 r;
+      r.x = pm_diff_unfold_word (v.x, prev);
+      r.y = pm_diff_unfold_word (v.y, v.x >> 16);
+      r.z = pm_diff_unfold_word (v.z, v.y >> 16);
+      r.w = pm_diff_unfold_word (v.w, v.z >> 16);
+      *(uint4 *) (w + at) = r;
+    }
+}
+
+// differences -> counts: every tile's sum, an exclusive scan of the sums (ix_sumscan_tiles_kernel: modulo 2^32, of which modulo
+// 2^16 is the low half), then every tile folded from the sum carried into it
+__global__ __launch_bounds__ (PD_BLOCK) void pd_fold_sums_kernel (const uint32_t * w, uint64_t n_words, uint32_t * tile_sum)
+{
+  __shared__ uint32_t s_wave[PD_BLOCK / 64];
+  const uint64_t at = (uint64_t) blockIdx.x * PD_TILE + (uint64_t) threadIdx.x * 4;
+  uint32_t m = 0;
+  if (at < n_words)
+    {
+      const uint4 v = *(const uint4 *) (w + at);
+      m = pm_diff_word_sum (v.x) + pm_diff_word_sum (v.y) + pm_diff_word_sum (v.z) + pm_diff_word_sum (v.w);
+    }
+  for (int o = 32; o; o >>= 1)
+    m += __shfl_xor (m, o);
+  if ((threadIdx.x & 63) == 0)
+    s_wave[threadIdx.x >> 6] = m;
+  __syncthreads ();
+  if (threadIdx.x == 0)
+    {
+      uint32_t t = 0;
+      for (int k = 0; k < PD_BLOCK / 64; k++)
+        t += s_wave[k];
+      tile_sum[blockIdx.x] = t & 0xFFFFu;
+    }
+}
+
+__global__ __launch_bounds__ (PD_BLOCK) void pd_fold_apply_kernel (uint32_t * w, uint64_t n_words, const uint32_t * tile_carry)
+{
+  __shared__ uint32_t s_wave[PD_BLOCK / 64];
+  const uint64_t at = (uint64_t) blockIdx.x * PD_TILE + (uint64_t) threadIdx.x * 4;
+  const bool in = at < n_words;
+  uint4 v = make_uint4 (0u, 0u, 0u, 0u);
+  if (in)
+    v = *(const uint4 *) (w + at);
+  const uint32_t mine = pm_diff_word_sum (v.x) + pm_diff_word_sum (v.y) + pm_diff_word_sum (v.z) + pm_diff_word_sum (v.w);
+  const uint32_t carry = pm_diff_combine (tile_carry[blockIdx.x], pd_block_exclusive (mine, s_wave));
+  if (in)
+    {
+      uint4 r;
+      r.x = pm_diff_fold_word (v.x, carry);
+      r.y = pm_diff_fold_word (v.y, r.x >> 16);
+      r.z = pm_diff_fold_word (v.z, r.y >> 16);
+      r.w = pm_diff_fold_word (v.w, r.z >> 16);
+      *(uint4 *) (w + at) = r;
     }
 }
 

@@ -141,7 +141,7 @@ static void read_knobs (PmKnobs & k)
   k.vote_waves = env_int ("PEMAP_VOTE_WAVES", 1024);
   if (k.vote_waves < 1) k.vote_waves = 1;
   k.walk_blocks_per_cu = env_int ("PEMAP_WALK_BLOCKS_PER_CU", 4);
-  k.pile_blocks_per_cu = env_int ("PEMAP_PILE_BLOCKS_PER_CU", 8);
+  k.pile_blocks_per_cu = env_int ("PEMAP_PILE_BLOCKS_PER_CU", 4);
   if (k.walk_blocks_per_cu < 1) k.walk_blocks_per_cu = 1;
   if (k.pile_blocks_per_cu < 1) k.pile_blocks_per_cu = 1;
   k.pipeline = env_int ("PEMAP_PIPELINE", 1);
@@ -176,6 +176,10 @@ struct pemap_dev
   bool index_ready = false;
   uint32_t *d_counts = nullptr; // the pileup counter planes (PmPile): 6 planes of pile_plane_words words
   size_t pile_plane_words = 0;
+  // plane 0 holds differences while the object maps (PmPile): guarded by mu.  run_slice unfolds, pile_fold folds back for every
+  // entry that reads or hands out the counters; d_pile_tiles is the conversions' word per tile of PD_TILE words.
+  bool pile_diff = false;
+  uint32_t *d_pile_tiles = nullptr;
   // each chunk's big-end remainder is enqueued exactly once: checked in launch_rest (the round-3 fault)
   uint64_t run_serial = 0;
   bool rest_twice = false;
@@ -350,6 +354,8 @@ static void free_index (pemap_dev * d)
   d->d_genome = nullptr;
   dev_free (d->d_contig_starts);
   dev_free (d->d_counts);
+  dev_free (d->d_pile_tiles);
+  d->pile_diff = false;
   d->index_ready = false;
 }
 
@@ -494,6 +500,7 @@ extern "C" int pemap_dev_index_alloc (pemap_dev * d, uint64_t n_mers, uint64_t g
   // (a plane is a whole number of 256-byte blocks: planes start line-aligned)
   d->pile_plane_words = (((size_t) genome_size + 2) / 2 + 63) & ~(size_t) 63;
   TRY (dev_alloc (d, &d->d_counts, 6 * d->pile_plane_words));
+  TRY (dev_alloc (d, &d->d_pile_tiles, (d->pile_plane_words + PD_TILE - 1) / PD_TILE));
   HIPCHK (d, hipMemset (d->d_genome + genome_size, 0, 512));
   HIPCHK (d, hipMemset (d->d_counts, 0, 6 * d->pile_plane_words * sizeof (uint32_t)));
   return 0;
@@ -737,10 +744,97 @@ extern "C" int pemap_dev_build_index_resident (pemap_dev * d, const void *d_geno
   return build_from_device_genome (d, contig_len, n_contigs, bisulfite);
 }
 
+// ---- plane 0 between counts and differences (PmPile, pemap_pile_diff.h).  Both conversions run on the ALU stream, behind whatever
+// is queued there; both want mu held.  On an hg38-sized plane either moves 6.2 GB in and out.
+struct PmConvTimer
+{
+  hipEvent_t ev[2] = {};
+  bool on = false;
+  PmConvTimer (hipStream_t st)
+  {
+    on = hipEventCreate (&ev[0]) == hipSuccess && hipEventCreate (&ev[1]) == hipSuccess && hipEventRecord (ev[0], st) == hipSuccess;
+  }
+  void stop (hipStream_t st)
+  {
+    on = on && hipEventRecord (ev[1], st) == hipSuccess;
+  }
+  // (after the stream was waited for)
+  void report (const char *what)
+  {
+    float ms = 0.f;
+    if (on && hipEventElapsedTime (&ms, ev[0], ev[1]) == hipSuccess)
+      fprintf (stderr, "libpemap_hip: plane 0 %s in %.3f ms\n", what, ms);
+  }
+  ~PmConvTimer ()
+  {
+    for (int i = 0; i < 2; i++)
+      if (ev[i])
+        hipEventDestroy (ev[i]);
+  }
+};
+
+// counts -> differences, enqueued only: the pile kernels behind it on the stream find differences
+static int pile_unfold_locked (pemap_dev * d)
+{
+  if (d->pile_diff)
+    return 0;
+  const uint64_t n_words = d->pile_plane_words, n_tiles = (n_words + PD_TILE - 1) / PD_TILE;
+  uint64_t sgrid = (n_tiles + PD_BLOCK - 1) / PD_BLOCK;
+  if (sgrid > (uint64_t) d->n_cus * 8)
+    sgrid = (uint64_t) d->n_cus * 8;
+  const bool log = env_int ("PEMAP_PILE_CONV_LOG", 0) != 0;
+  std::unique_ptr < PmConvTimer > tm (log ? new PmConvTimer (d->stream) : nullptr);
+  hipLaunchKernelGGL (pd_unfold_save_kernel, dim3 ((unsigned) sgrid), dim3 (PD_BLOCK), 0, d->stream, d->d_counts, n_tiles, d->d_pile_tiles);
+  hipLaunchKernelGGL (pd_unfold_apply_kernel, dim3 ((unsigned) n_tiles), dim3 (PD_BLOCK), 0, d->stream, d->d_counts, n_words, d->d_pile_tiles);
+  HIPCHK (d, hipGetLastError ());
+  if (tm)
+    {
+      // (the logged figure is worth a wait: the knob is for measuring)
+      tm->stop (d->stream);
+      HIPCHK (d, hipStreamSynchronize (d->stream));
+      tm->report ("unfolded");
+    }
+  d->pile_diff = true;
+  return 0;
+}
+
+// differences -> counts, and waited for: afterwards the planes hold what the reference's array would
+static int pile_fold_locked (pemap_dev * d)
+{
+  if (!d->pile_diff)
+    return 0;
+  HIPCHK (d, hipSetDevice (d->device));
+  const uint64_t n_words = d->pile_plane_words, n_tiles = (n_words + PD_TILE - 1) / PD_TILE;
+  DevTmp < unsigned long long > d_total;
+  TRY (dev_alloc (d, &d_total.p, 1));
+  // PEMAP_PILE_CONV_LOG=1: either conversion's time on the device goes to stderr
+  const bool log = env_int ("PEMAP_PILE_CONV_LOG", 0) != 0;
+  std::unique_ptr < PmConvTimer > tm (log ? new PmConvTimer (d->stream) : nullptr);
+  hipLaunchKernelGGL (pd_fold_sums_kernel, dim3 ((unsigned) n_tiles), dim3 (PD_BLOCK), 0, d->stream, d->d_counts, n_words, d->d_pile_tiles);
+  hipLaunchKernelGGL (ix_sumscan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d->d_pile_tiles, n_tiles, d_total);
+  hipLaunchKernelGGL (pd_fold_apply_kernel, dim3 ((unsigned) n_tiles), dim3 (PD_BLOCK), 0, d->stream, d->d_counts, n_words, d->d_pile_tiles);
+  if (tm)
+    tm->stop (d->stream);
+  HIPCHK (d, hipGetLastError ());
+  HIPCHK (d, hipStreamSynchronize (d->stream));
+  if (tm)
+    tm->report ("folded");
+  d->pile_diff = false;
+  return 0;
+}
+
+static int pile_fold (pemap_dev * d)
+{
+  std::lock_guard < std::mutex > lk (d->mu);
+  return pile_fold_locked (d);
+}
+
 extern "C" int pemap_dev_buffer (pemap_dev * d, int which, void **d_ptr, uint64_t * n_bytes)
 {
   if (!d->d_pos_index)
     return fail (d, "buffer: no index");
+  if (which == 4)
+    TRY (pile_fold (d));        // the view holds counts when it is handed out (include/pemap_hip.h)
   switch (which)
     {
     case 0: *d_ptr = d->d_pos_index; *n_bytes = POS_INDEX_N * 4; break;
@@ -1114,11 +1208,12 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
   // kernel makes the stamp the moment the look-up kernel can start, so that LOOKUP_BEGIN..LOOKUP_END is the kernel's own duration)
   hipLaunchKernelGGL (pm_nop_kernel, dim3 (1), dim3 (1), 0, st);
   hipEventRecord (ev[PM_EV_LOOKUP_BEGIN], st);
-  // PEMAP_LOOKUP_WAVES=n: n persistent one-wave workgroups per CU.  Default 9 (pm_seed4_kernel: 14.6 KB of LDS and 128 VGPRs a wave): 8
-  // steps of the default workload take 23.4 / 21.3 / 20.7 / 21.3 ms each on resident reads with 7 / 8 / 9 / 10 (profiles/r04_ab_sweeps.txt;
-  // the third form, 19.6 KB and 168 VGPRs, took 25.2 at its best, 7) -- the kernel itself keeps gaining (5.06 / 4.53 / 4.05 / 3.84 ms per
-  // launch) while the other stream's DP kernels lose the SIMDs' registers to it
-  int lw = d->kn.lookup_waves > 0 ? d->kn.lookup_waves : 9;
+  // PEMAP_LOOKUP_WAVES=n: n persistent one-wave workgroups per CU (pm_seed4_kernel: 14.6 KB of LDS and 128 VGPRs a wave).  The kernel
+  // itself keeps gaining with n (5.06 / 4.53 / 4.05 / 3.84 ms per launch with 7 / 8 / 9 / 10, profiles/r04_ab_sweeps.txt) while the other
+  // stream's DP kernels lose the SIMDs' registers to it.  Default 10 since the pileup's plane 0 is kept as differences: with the long
+  // pile stage 10 was the slower setting (round 4: 21.3 ms per step against 20.7; the parent of round 9: 19.74 against 19.35), behind
+  // the short one, launched with four blocks per CU, it is the faster one (18.57 against 19.3, profiles/r09_ab_sweeps.txt)
+  int lw = d->kn.lookup_waves > 0 ? d->kn.lookup_waves : 10;
   if (pm_fused (d))
     {
       // (no more workgroups than are resident at once: a workgroup owns its first ends by its number, and one that starts when
@@ -1332,12 +1427,15 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
   // (the walk on the look-up stream, beside the next chunk's vote and SW, was tried: 107 ms per step against 103; it stays here)
   hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_walk_kernel < W, LPA >), dim3 (wgrid), dim3 (64), 0, d->stream, c.b, H, wins, S.walks, ctr, d->d_cur,
                       dirbuf, c.tstride, pile_of (d), d->d_ins_log, d->ins_cap, S.path, d->path_words, S.nsteps);
-  // one wave per winning alignment applies the recorded steps to the pileup
+  // the winners applied to the pileup: the plain diagonals two to a wave, then the walked ones, one wave each, by their recorded steps
+  // PEMAP_PILE_BLOCKS_PER_CU (default 4, swept 2 / 3 / 4 / 6 / 8 in round 9): the waves wait for their atomics' old words, and more of
+  // them than this only take wave slots from the seed kernel on the other stream
   const int pbp = d->kn.pile_blocks_per_cu;
   int pgrid = c.b.n_ends;
   if (pgrid > d->n_cus * pbp * 4)
     pgrid = d->n_cus * pbp * 4;         // (waves: the knob counts blocks of four)
-  hipLaunchKernelGGL (pm_pile_kernel, dim3 (pgrid), dim3 (64), 0, d->stream, c.b, H, wins, ctr, pile_of (d), S.path, d->path_words, S.nsteps);
+  hipLaunchKernelGGL (pm_pile_kernel, dim3 (pgrid), dim3 (64), 0, d->stream, c.b, H, wins, ctr, pile_of (d));
+  hipLaunchKernelGGL (pm_pile_walked_kernel, dim3 (pgrid), dim3 (64), 0, d->stream, c.b, H, wins, S.walks, ctr, pile_of (d), S.path, d->path_words, S.nsteps);
   hipEventRecord (ev[PM_EV_WALK_END], d->stream);
   hipEventRecord (S.ev_walk_done, d->stream);
 }
@@ -1473,6 +1571,7 @@ static int chunk_pairs_for (const pemap_dev * d, int n, int L)
 
 // copy_evs (may be NULL): one event per chunk, recorded behind the host-to-device copy of that chunk's rows; the first stream
 // that touches the rows waits for it
+// (mu held: the form of plane 0 changes here)
 static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_t * copy_evs = nullptr)
 {
   HIPCHK (d, hipSetDevice (d->device));
@@ -1529,6 +1628,8 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
       d->last_big = d->last_big2 = 0;
       d->run_ends = 0;
     }
+  // the first chunk that finds plane 0 holding counts has them turned into differences, ahead of its pile kernel on the ALU stream
+  TRY (pile_unfold_locked (d));
   d->run_serial++;
   d->run_first = first;
   d->run_n = n;
@@ -1597,11 +1698,13 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
 
 extern "C" int pemap_dev_run (pemap_dev * d, int sync)
 {
+  std::lock_guard < std::mutex > lk (d->mu);
   return run_slice (d, 0, d->n_staged, sync);
 }
 
 extern "C" int pemap_dev_run_slice (pemap_dev * d, int first, int n, int sync)
 {
+  std::lock_guard < std::mutex > lk (d->mu);
   return run_slice (d, first, n, sync);
 }
 
@@ -2062,7 +2165,9 @@ extern "C" int pemap_dev_map_batch (pemap_dev * d, const char *reads1, const int
       TRY (absorb_run (d));
       d->run_pending = false;
     }
-  return 0;
+  // the one-call entry hands the counters back as counts: a view of buffer 4 taken before the call is read after it.  (With other
+  // threads' batches still in flight the fold queues behind them, and their next chunk unfolds again.)
+  return pile_fold_locked (d);
 }
 
 extern "C" int pemap_dev_summary (pemap_dev * d, long *out13)
@@ -2153,6 +2258,11 @@ extern "C" int pemap_dev_reset_pileup (pemap_dev * d)
     return fail (d, "reset_pileup: no index");
   HIPCHK (d, hipStreamSynchronize (d->stream));
   HIPCHK (d, hipMemset (d->d_counts, 0, 6 * d->pile_plane_words * sizeof (uint32_t)));
+  {
+    // a plane of zeros is one in both forms: no conversion, whichever form it had
+    std::lock_guard < std::mutex > lk (d->mu);
+    d->pile_diff = false;
+  }
   HIPCHK (d, hipMemset (d->d_cur, 0, sizeof (PmInsCursor)));
   d->h_ins.clear ();
   memset (d->summary, 0, sizeof (d->summary));
@@ -2238,7 +2348,10 @@ extern "C" int pemap_dev_absorb (pemap_dev * dst, pemap_dev * src)
     return fail (dst, "absorb: %s object has a submitted batch that was not waited for", ring_busy (dst) ? "the destination" : "the source");
   if (pemap_dev_sync (src) || (hipSetDevice (src->device) != hipSuccess) || drain_ins (src))
     return fail (dst, "absorb: the source object: %.400s", src->err);
+  if (pile_fold (src))
+    return fail (dst, "absorb: the source object: %.400s", src->err);
   TRY (pemap_dev_sync (dst));   // (leaves dst's device current)
+  TRY (pile_fold (dst));
   // ---- counters: every 16-bit counter of the planes becomes (dst + src) mod 2^16, padding included
   const size_t bytes = 6 * dst->pile_plane_words * sizeof (uint32_t);
   // (a plane is a whole number of 256-byte blocks, index_alloc: whole 16-byte vectors, no tail)
@@ -2291,6 +2404,7 @@ extern "C" int pemap_dev_fetch_pileup (pemap_dev * d, uint16_t * counts, pemap_i
   if (!d->d_counts)
     return fail (d, "fetch_pileup: no index");
   TRY (pemap_dev_sync (d));
+  TRY (pile_fold (d));
   TRY (drain_ins (d));
   if (counts)
     {
@@ -2341,6 +2455,7 @@ extern "C" int pemap_dev_fetch_records (pemap_dev * d, uint64_t first, uint64_t 
     }
   if (count > (1ull << 31))
     return fail (d, "fetch_records: at most 2^31 sites per call");
+  TRY (pile_fold (d));          // (on the ALU stream, behind everything queued, and waited for)
   HIPCHK (d, hipStreamSynchronize (d->stream));
   const uint64_t n_tiles = (count + PR_BLOCK - 1) / PR_BLOCK;
   DevTmp < uint64_t > d_total, d_to;

@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "pemap_pile_diff.h"
 
 #define PM_MAX_HITS 200            // max_hits, pemapper.c:162
 #define PM_TOO_MANY 100            // too_many_spots, pemapper.c:163
@@ -41,12 +42,14 @@ struct PmIndex
 // Plane-major, 16 bits each, two positions to a word: plane q of position pos is half (pos & 1) of word q * plane_words + (pos >> 1).
 // WHICH plane holds column col of a position depends on the reference letter there: for A / C / G / T (codes 0..3) the four base
 // columns are rotated so that the column of the reference base itself is plane 0, q = (col - code) & 3; for every other letter, and
-// for the Del / Ins columns 4 and 5, q = col.  Reads mostly agree with the reference, so the ~150 increments of a read fall into
-// the ~5 lines of plane 0 under it plus a line per mismatch -- 7 lines instead of ~23 with a plane per base (and 57 with six u32
-// counters per position side by side) -- and every touched line goes back to HBM once.  The arithmetic is the reference's: 16
-// bits, wrapping.  Both halves are incremented with 32-bit atomics; the high half wraps by itself, the low half's wrap would carry
-// into its neighbour, so increments of a low half return the old value and take the carry back when they see 0xFFFF.  A rotation
-// per position is a bijection on that position's counters: sums over ranks, totals and resets do not see it; the export undoes it.
+// for the Del / Ins columns 4 and 5, q = col.  A rotation per position is a bijection on that position's counters: sums over ranks,
+// totals and resets do not see it; the export undoes it.  Reads mostly agree with the reference, so nearly all increments of a read
+// are "+1 on every position of a run" in plane 0.  While the object maps, plane 0 therefore holds DIFFERENCES (pemap_pile_diff.h:
+// D[p] = c[p] - c[p-1] modulo 2^16): a run a..b costs D[a] += 1 and D[b+1] -= 1, two 32-bit atomics whatever its length, and the
+// plane has a half for b + 1 = genome size.  The host keeps the plane's form (pemap_dev::pile_diff) and folds it back to counts
+// before anything reads it.  Planes 1-5 always hold counts; their increments (mismatches, deletions, insertions) are single adds.
+// The arithmetic is the reference's in both forms: 16 bits, wrapping.  The high half of a word wraps by itself; what the low half
+// carries or borrows lands in its neighbour, so an add to a low half returns the old word and takes that back when it must.
 struct PmPile
 {
   uint32_t *w;
@@ -66,23 +69,39 @@ __device__ __forceinline__ uint32_t *pm_pile_word (const PmPile & p, size_t pos,
   return p.w + (size_t) q * p.plane_words + (pos >> 1);
 }
 
-// `add` = 1 (the low half), 0x10000 (the high half) or 0x10001 (both halves of a word: two neighbouring positions)
-__device__ __forceinline__ void pm_pile_add (uint32_t * q, uint32_t add)
+// one counter of planes 1-5 (or of a plane 0 that holds counts) + 1
+__device__ __forceinline__ void pm_pile_add (uint32_t * q, int odd)
 {
-  if (!(add & 1u))
-    atomicAdd (q, add);
+  const uint32_t addend = pm_diff_addend (odd, +1);
+  if (odd)
+    atomicAdd (q, addend);
   else
     {
-      const uint32_t old = atomicAdd (q, add);
-      if ((old & 0xFFFFu) == 0xFFFFu)
-        atomicSub (q, 0x10000u);
+      const uint32_t back = pm_diff_takeback (atomicAdd (q, addend), addend);
+      if (back)
+        atomicAdd (q, back);
+    }
+}
+
+// D[pos] of plane 0 in difference form + sign (+1 where a run of matched bases starts, -1 behind its last position)
+__device__ __forceinline__ void pm_pile_diff_add (const PmPile & p, size_t pos, int sign)
+{
+  uint32_t *q = p.w + (pos >> 1);
+  const uint32_t addend = pm_diff_addend ((int) (pos & 1), sign);
+  if (pos & 1)
+    atomicAdd (q, addend);
+  else
+    {
+      const uint32_t back = pm_diff_takeback (atomicAdd (q, addend), addend);
+      if (back)
+        atomicAdd (q, back);
     }
 }
 
 __device__ __forceinline__ void pm_pile_inc (const PmPile & p, size_t pos, int col)
 {
   const int q = col > 3 ? col : pm_pile_plane (p.genome[pos], col);
-  pm_pile_add (pm_pile_word (p, pos, q), (pos & 1) ? 0x10000u : 1u);
+  pm_pile_add (pm_pile_word (p, pos, q), (int) (pos & 1));
 }
 
 __device__ __forceinline__ uint16_t pm_pile_get (const PmPile & p, size_t pos, int col)

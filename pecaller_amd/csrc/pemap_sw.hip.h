@@ -1258,8 +1258,8 @@ __global__ __launch_bounds__ (64) void pm_select_kernel (PmBatch b, PmParams prm
 // ============================================================================================================
 // K5: traceback + pileup (smith_waterman_backtrack, pemapper.c:1752-1965).  One lane per winning alignment that is not known
 // to be a plain diagonal (pm_select_kernel's list `walks`) walks the nibbles of its slab from the start cell to the first row
-// or column.  Pileup counters are u32 in HBM updated with
-// no-return atomics (the reference's u16 counters wrap; the fetch truncates, which is the same arithmetic).
+// or column.  The pileup counters are the reference's wrapping u16 counters, two to a 32-bit word (PmPile, pemap_kernels.hip.h):
+// plane 0 holds differences while the object maps, and the pile kernels add at the boundaries of the matched runs.
 // Insertions go to a byte log through an atomic cursor.
 // ============================================================================================================
 __device__ __forceinline__ void pm_log_insertion (uint8_t * ins_log, unsigned ins_cap, PmInsCursor * cur, uint32_t pos, const uint8_t * read,
@@ -1279,11 +1279,12 @@ __device__ __forceinline__ void pm_log_insertion (uint8_t * ins_log, unsigned in
     atomicExch (&cur->ins_overflow, 1u);
 }
 
-// The traceback in two kernels.  pm_walk_kernel only follows the direction nibbles and records the walk as 2-bit steps
+// The traceback in two stages.  pm_walk_kernel only follows the direction nibbles and records the walk as 2-bit steps
 // (0 diagonal, 1 vertical = deletion, 2 horizontal = inserted base), 32 per 64-bit word, PM_PATH_WORDS(L) words per
-// alignment; insertions -- rare -- are logged there and then.  pm_pile_kernel replays the steps with one WAVE per
-// alignment, lane = step: row and read column of every step come from prefix popcounts, the pileup increments of an
-// alignment go out as a few wave-wide atomic instructions over consecutive positions.  A lane-per-alignment kernel that
+// alignment; insertions -- rare -- are logged there and then.  pm_pile_walked_kernel replays the steps with one WAVE per
+// alignment, lane = step: row and read column of every step come from prefix popcounts, and the lanes at the boundaries of the
+// matched runs add to the difference plane; pm_pile_kernel does the same for the alignments that are plain diagonals and
+// have no recorded steps (both below).  A lane-per-alignment kernel that
 // did both had each of its half million walkers hold a direction line, a read line and a pileup line in L2 at once;
 // they did not fit, every step refetched its lines and the kernel ran at the HBM limit for random 64-byte lines.
 #define PM_PATH_WORDS(L) ((((2 * (L) + 21 + 31) / 32) + 1) & ~1)
@@ -1393,93 +1394,239 @@ template < int W, int PM_LPA > __global__ __launch_bounds__ (64) void pm_walk_ke
     atomicAdd (&ctr->n_ins, nins);
 }
 
-// second half: the recorded steps of every alignment applied to the pileup (pemapper.c:1840-1870), one wave per alignment.
-// An alignment decided by pm_gapless_kernel has no recorded steps: it is mm diagonal steps from (row sti, column mm).
-// Lane = step, so neighbouring lanes usually hold neighbouring positions of the same plane (PmPile: the plane of the reference
-// base), i.e. the two halves of one word: the even position's lane then adds to both halves at once and its neighbour stays out.
-__global__ __launch_bounds__ (64) void pm_pile_kernel (PmBatch b, PmHits h, const uint32_t * wins, PmCounters * ctr, PmPile counts,
-                                                       const unsigned long long *path, int path_words, const uint16_t * n_steps)
+// second half: every winning alignment applied to the pileup (pemapper.c:1840-1870).  The rule, for gapped and ungapped alignments
+// alike: let Z be the positions at which this alignment's increment lands in plane 0 (pm_pile_plane: the read letter is an upper-case
+// A / C / G / T equal to the reference letter, or the reference letter is none of the four and the read letter is 'A').  A position
+// occurs at most once per alignment.  Plane 0 holds differences (PmPile), so for p in Z with p - 1 not in Z: D[p] += 1, and for p in Z
+// with p + 1 not in Z: D[p + 1] -= 1.  A read letter outside A / C / G / T increments nothing and ends a run, a deleted position goes
+// to plane 4 and ends a run, an inserted base has no position and ends nothing.  Every other increment is a single add to its counter.
+//
+// Two kernels, each with the registers its own loop needs.  pm_pile_kernel serves the alignments with PM_GAPLESS (nine in ten: mm
+// diagonal steps from (row sti, column mm), no recorded steps), one per HALF-wave and pass, lane = eight bases: read and window are
+// compared eight bytes at a time where all sixteen are plain bases, and the lanes that hold a run boundary -- two beside each
+// mismatch, one at either end -- add to D together: one returned atomic's round trip per pass, not three per alignment.
+// pm_pile_walked_kernel serves the walked alignments, one per wave, lane = step, the boundaries from ballots.
+//
+// An alignment's record (winner -> read, strand, window, start cell, steps).  Both kernels fetch it one round ahead and the winner's
+// word two rounds ahead: the round itself waits for the read and reference bytes, then for the boundary adds' old words.  (No
+// branches around these loads -- past the end they read the last winner again: a load under a condition makes the compiler wait for
+// every outstanding load where the paths join.)
+struct PmPileRec
+{
+  int mm, orient, sti;
+  uint32_t gpos;
+  bool gapless;
+  const uint8_t *read;
+};
+
+__device__ __forceinline__ PmPileRec pm_pile_rec (const PmBatch & b, const PmHits & h, uint32_t win_word)
+{
+  PmPileRec r;
+  const size_t o = win_word;
+  r.read = pm_read_ptr (b, (int) (o / PM_MAX_HITS), &r.mm);
+  r.orient = h.orient[o];
+  r.gpos = h.gpos[o];
+  r.gapless = (h.stk[o] & PM_GAPLESS) != 0;
+  r.sti = h.sti[o];
+  return r;
+}
+
+__device__ __forceinline__ int pm_pile_slot (uint8_t ch)
+{
+  return (ch == 'A') ? 0 : (ch == 'C') ? 1 : (ch == 'G') ? 2 : (ch == 'T') ? 3 : -1;       // pemapper.c:1850-1857
+}
+
+__global__ __launch_bounds__ (64) void pm_pile_kernel (PmBatch b, PmHits h, const uint32_t * wins, PmCounters * ctr, PmPile counts)
 {
   const int lane = threadIdx.x & 63;
   const unsigned n_wins = ctr->n_wins;
   const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-  const unsigned long long below = (1ull << lane) - 1ull;
   unsigned long long incs = 0;
-  // an alignment's record (winner -> read, strand, window, start cell, steps) is fetched one round ahead, the winner's word two
-  // rounds ahead: the round itself waits for the steps, then the read and reference bytes, then nothing (the adds return nothing)
-  struct Rec
-  {
-    int mm, orient, ns, sti;
-    uint32_t gpos;
-    bool gapless;
-    const uint8_t *read;
-  };
-  // (no branches around these loads -- past the end they read the last winner again: a load under a condition makes the compiler wait
-  // for every outstanding load where the paths join)
   if (n_wins == 0u)
     return;
   auto load_win = [&] (unsigned ww)->uint32_t
   {
     return wins[ww < n_wins ? ww : n_wins - 1u];
   };
-  auto load_rec = [&] (unsigned ww, uint32_t win_word)->Rec
   {
-    Rec r;
-    const size_t o = win_word;
-    r.read = pm_read_ptr (b, (int) (o / PM_MAX_HITS), &r.mm);
-    r.orient = h.orient[o];
-    r.gpos = h.gpos[o];
-    r.gapless = (h.stk[o] & PM_GAPLESS) != 0;
-    r.ns = n_steps[ww < n_wins ? ww : n_wins - 1u];
-    r.sti = h.sti[o];
-    return r;
+    const int l = lane & 31, half = lane & 32;
+    const unsigned stride = 2u * n_waves;
+    unsigned w = 2u * wave + (unsigned) (lane >> 5);
+    PmPileRec nx = pm_pile_rec (b, h, load_win (w));
+    uint32_t win2 = load_win (w + stride);
+    for (unsigned w0 = 2u * wave; w0 < n_wins; w0 += stride, w += stride)
+      {
+        const PmPileRec cur = nx;
+        nx = pm_pile_rec (b, h, win2);
+        win2 = load_win (w + 2u * stride);
+        const bool go = w < n_wins && cur.gapless;
+        const int mm = cur.mm, orient = cur.orient;
+        // read column c lies on position first + c; a half-wave without an alignment of this kind reads the window's first bytes
+        const size_t first = go ? (size_t) cur.gpos + (size_t) (cur.sti - mm) : (size_t) cur.gpos;
+        // pieces of eight columns: the one that holds column mm (no base, but the position behind the last run) is the last
+        const int n_pieces = go ? (mm + 8) >> 3 : 0;
+        unsigned long long top_before = 0ull;
+#pragma nounroll
+        for (int u = 0; u < 2; u++)     // (a lane's second piece: reads of 256 bases and more)
+          {
+            if (u && !__any (n_pieces > 32))
+              break;
+            const int c = l + 32 * u;
+            const bool on = c < n_pieces;
+            const int nb = !on ? 0 : mm - 8 * c < 8 ? mm - 8 * c : 8;
+            // both loads unconditional (the record prefetch stays in flight): a lane without bases reads piece 0.  (The genome buffer
+            // and the read rows are padded: a few bytes past a window or a read are safe, as in pm_gapless_kernel, whose pieces
+            // these are: a piece of the reverse strand is the mirrored piece of the read, bytes swapped end for end and complemented.)
+            int s0 = nb > 0 ? (orient ? mm - 8 - 8 * c : 8 * c) : 0, sh_up = 0;
+            if (s0 < 0)
+              {
+                sh_up = -8 * s0;
+                s0 = 0;
+              }
+            uint64_t q = *(const pm_u64_unaligned *) (cur.read + s0);
+            uint64_t r = *(const pm_u64_unaligned *) (counts.genome + first + (nb > 0 ? 8 * c : 0));
+            if (orient)
+              {
+                q <<= sh_up;
+                q = pm_rc8 (q, sh_up);
+              }
+            // the bytes past the piece's bases count as 'A' on both sides: plain bases that agree, masked out of z below
+            const uint64_t keep = nb >= 8 ? ~0ull : (1ull << (8 * nb)) - 1ull;
+            q = (q & keep) | (0x4141414141414141ull & ~keep);
+            r = (r & keep) | (0x4141414141414141ull & ~keep);
+            const unsigned have = (1u << nb) - 1u;
+            unsigned z = 0u, direct = 0u;       // bit k: column 8 c + k lands in plane 0 / in another plane
+            const uint32_t ql = (uint32_t) q, qh = (uint32_t) (q >> 32), rl = (uint32_t) r, rh = (uint32_t) (r >> 32);
+            if (pm_comp4 (pm_comp4 (ql)) == ql && pm_comp4 (pm_comp4 (qh)) == qh && pm_comp4 (pm_comp4 (rl)) == rl && pm_comp4 (pm_comp4 (rh)) == rh)
+              {
+                direct = pm_nonzero_bytes (q ^ r);      // (no bit past the bases: the padding agrees)
+                z = ~direct & have;
+              }
+            else
+#pragma nounroll
+              for (int k = 0; k < nb; k++)
+                {
+                  const int slot = pm_pile_slot ((uint8_t) (q >> (8 * k)));
+                  if (slot < 0)
+                    continue;
+                  if (pm_pile_plane ((uint8_t) (r >> (8 * k)), slot) == 0)
+                    z |= 1u << k;
+                  else
+                    direct |= 1u << k;
+                }
+            incs += __popc (z | direct);
+            // a boundary lies in front of column k where k - 1 and k differ in z (the column in front of the lane's first is its
+            // neighbour's last; none in front of the alignment, none in its last piece's padding): + 1 where a run starts, - 1 behind it
+            const unsigned long long top = __ballot ((z >> 7) & 1u);
+            const unsigned before = l > 0 ? (unsigned) (top >> (lane - 1)) & 1u : u ? (unsigned) (top_before >> (half + 31)) & 1u : 0u;
+            top_before = top;
+            const unsigned z9 = (z << 1) | before;
+            unsigned edges = on ? (z9 ^ (z9 >> 1)) & 0xFFu : 0u;
+            const size_t pos0 = first + (size_t) (8 * c);
+            while (edges)
+              {
+                const int k = __ffs ((int) edges) - 1;
+                edges &= edges - 1u;
+                pm_pile_diff_add (counts, pos0 + (size_t) k, ((z >> k) & 1u) ? +1 : -1);
+              }
+            while (direct)
+              {
+                const int k = __ffs ((int) direct) - 1;
+                direct &= direct - 1u;
+                const int q_plane = pm_pile_plane ((uint8_t) (r >> (8 * k)), pm_pile_slot ((uint8_t) (q >> (8 * k))));
+                pm_pile_add (pm_pile_word (counts, pos0 + (size_t) k, q_plane), (int) ((pos0 + (size_t) k) & 1));
+              }
+          }
+      }
+  }
+  for (int o = 32; o; o >>= 1)
+    incs += __shfl_xor (incs, o);
+  if (lane == 0 && incs)
+    atomicAdd (&ctr->pile_incs, incs);
+}
+
+// The walked alignments (the list pm_walk_kernel followed; one flagged PM_GAPLESS since is a plain diagonal and was served above), one
+// per wave, lane = step.  The walk runs towards lower positions: a step that has a position (0 diagonal, 1 deletion) looks at the last
+// such step before it -- in this round by the ballot, across rounds by one carried bit -- and where the two differ in z, the boundary
+// lies between them, at the earlier step's position: - 1 when this step starts a run (seen from below: the run's top end), + 1 when it
+// has just ended one (its bottom end).  A run still open at the walk's end has its bottom end at the last position.
+__global__ __launch_bounds__ (64) void pm_pile_walked_kernel (PmBatch b, PmHits h, const uint32_t * wins, const uint32_t * walks, PmCounters * ctr,
+                                                              PmPile counts, const unsigned long long *path, int path_words, const uint16_t * n_steps)
+{
+  const int lane = threadIdx.x & 63;
+  const unsigned n_walks = ctr->n_walks;
+  const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned long long incs = 0;
+  if (n_walks == 0u)
+    return;
+  // (the list's entry three rounds ahead, the winner's word two, the record and the step count one)
+  auto load_walk = [&] (unsigned xx)->uint32_t
+  {
+    return walks[xx < n_walks ? xx : n_walks - 1u];
   };
-  Rec nx = load_rec (wave, load_win (wave));
-  uint32_t win2 = load_win (wave + n_waves);
-  for (unsigned w = wave; w < n_wins; w += n_waves)
+  unsigned w1 = load_walk (wave);
+  PmPileRec nx = pm_pile_rec (b, h, wins[w1]);
+  int ns_nx = n_steps[w1];
+  unsigned w2 = load_walk (wave + n_waves);
+  uint32_t win2 = wins[w2];
+  unsigned w3 = load_walk (wave + 2u * n_waves);
+  for (unsigned x = wave; x < n_walks; x += n_waves)
     {
-      const Rec cur = nx;
-      nx = load_rec (w + n_waves, win2);
-      win2 = load_win (w + 2u * n_waves);
+      const PmPileRec cur = nx;
+      const unsigned w = w1;
+      const int ns = ns_nx;
+      nx = pm_pile_rec (b, h, win2);
+      ns_nx = n_steps[w2];
+      w1 = w2;
+      w2 = w3;
+      win2 = wins[w3];
+      w3 = load_walk (x + 3u * n_waves);
+      if (cur.gapless)
+        continue;
       const int mm = cur.mm, orient = cur.orient;
       const uint8_t *read = cur.read;
       const uint32_t gpos = cur.gpos;
-      const bool gapless = cur.gapless;
-      const int ns = gapless ? mm : cur.ns;
       const unsigned long long *pw = path + (size_t) w * path_words;
       int i = cur.sti, j = mm;
+      unsigned open = 0u;       // the last step with a position so far landed in plane 0
       for (int s0 = 0; s0 < ns; s0 += 64)
         {
           const int s = s0 + lane;
           int code = 3;
           if (s < ns)
-            code = gapless ? 0 : (int) ((pw[s >> 5] >> (2 * (s & 31))) & 3ull);
+            code = (int) ((pw[s >> 5] >> (2 * (s & 31))) & 3ull);
           const unsigned long long mi = __ballot (code == 0 || code == 1), mj = __ballot (code == 0 || code == 2);
           const int ib = i - __popcll (mi & below), jb = j - __popcll (mj & below);      // row and column before this step
-          uint32_t *q = nullptr;
           const size_t pos = (size_t) gpos + (size_t) (ib - 1);
+          int q_plane = -1;
           if (code == 0)
             {
-              const uint8_t ch = pm_oriented (read, mm, orient, jb - 1);
-              const int slot = (ch == 'A') ? 0 : (ch == 'C') ? 1 : (ch == 'G') ? 2 : (ch == 'T') ? 3 : -1;       // pemapper.c:1850-1857
+              const int slot = pm_pile_slot (pm_oriented (read, mm, orient, jb - 1));
               if (slot >= 0)
-                q = pm_pile_word (counts, pos, pm_pile_plane (counts.genome[pos], slot));
+                q_plane = pm_pile_plane (counts.genome[pos], slot);
             }
           else if (code == 1)
-            q = pm_pile_word (counts, pos, 4);
-          incs += q != nullptr;
-          // the walk runs towards lower positions: lane + 1 holds pos - 1 after a diagonal or vertical step; with pos odd the two
-          // share a word, and this lane (the high half) leaves its increment to that one (the low half's, which reads the old value)
-          const unsigned long long qn = __shfl_down ((unsigned long long) (uintptr_t) q, 1);
-          const unsigned long long qp = __shfl_up ((unsigned long long) (uintptr_t) q, 1);
-          const int odd_n = __shfl_down ((int) (pos & 1), 1), odd_p = __shfl_up ((int) (pos & 1), 1);
-          const bool give = q != nullptr && (pos & 1) && lane < 63 && qn == (unsigned long long) (uintptr_t) q && !odd_n;
-          const bool take = q != nullptr && !(pos & 1) && lane > 0 && qp == (unsigned long long) (uintptr_t) q && odd_p;
-          if (q != nullptr && !give)
-            pm_pile_add (q, take ? 0x10001u : (pos & 1) ? 0x10000u : 1u);
+            q_plane = 4;
+          incs += q_plane >= 0;
+          const unsigned long long mz = __ballot (q_plane == 0);
+          if (code == 0 || code == 1)
+            {
+              const unsigned long long earlier = mi & below;
+              const unsigned was = earlier ? (unsigned) (mz >> (63 - __clzll ((long long) earlier))) & 1u : open;
+              const unsigned is = q_plane == 0;
+              if (was != is)
+                pm_pile_diff_add (counts, pos + 1, was ? +1 : -1);
+              if (q_plane > 0)
+                pm_pile_add (pm_pile_word (counts, pos, q_plane), (int) (pos & 1));
+            }
+          if (mi)
+            open = (unsigned) (mz >> (63 - __clzll ((long long) mi))) & 1u;
           i -= __popcll (mi);
           j -= __popcll (mj);
         }
+      if (open && lane == 0)
+        pm_pile_diff_add (counts, (size_t) gpos + (size_t) i, +1);
     }
   for (int o = 32; o; o >>= 1)
     incs += __shfl_xor (incs, o);

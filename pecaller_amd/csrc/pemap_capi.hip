@@ -1354,6 +1354,18 @@ static int enqueue_seed (pemap_dev * d, const PmSchedule & s, const RunCtx & c, 
   return 0;
 }
 
+// ---- one launch of the gapless rule over `tasks`; short_rows: the form whose rows hold reads of up to PM_GL_SHORT_MM bases
+template < bool C3 > static void launch_gapless (pemap_dev * d, bool short_rows, int ggrid, const RunCtx & c, const PmChunkSet & S, const uint32_t * tasks,
+                                                 const unsigned *n_tasks, const PmTaskList & l, int max_x, uint32_t * tasks_c3, unsigned *n_tasks_c3)
+{
+  if (short_rows)
+    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < C3, true >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, S.hits, tasks, n_tasks,
+                        l.dp, l.n_dp, max_x, l.band, l.n_band, tasks_c3, n_tasks_c3);
+  else
+    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < C3, false >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, S.hits, tasks, n_tasks,
+                        l.dp, l.n_dp, max_x, l.band, l.n_band, tasks_c3, n_tasks_c3);
+}
+
 // ---- the DP cascade over one task list, on the ALU stream: the gapless rule, its second launch for case (3), the banded DP, the full
 //      DP.  DIRS: the single-hit ends' list, scored with direction nibbles (the multi-hit ends' problems get scores only; a winner the
 //      rule decided is not scored again).  (`auto`: instantiated where launch_chunk names it, which keeps the kernels' order in the code object)
@@ -1365,25 +1377,32 @@ template < int W, int LPA, bool DIRS > static auto launch_cascade (pemap_dev * d
   if (DIRS)
     {
       // The rule's kernel and the NEXT chunk's seed kernel are launched at the same moment (both wait for this chunk's seed kernel), and
-      // whichever gets its waves onto the SIMDs first keeps them: the seed kernel's persistent waves need 168 registers each, six of
-      // this kernel's fill a SIMD's 512.  For reads of up to 160 bases 24 workgroups per CU are the measured optimum (the seed
+      // whichever gets its waves onto the SIMDs first keeps them: the seed kernel's persistent waves (pm_seed4_kernel < 10, 0 >, ten per
+      // CU) take 128 registers and 15,360 bytes of LDS each, this kernel's 109 to 115 registers (four fill a SIMD's 512) and 1 KB of LDS
+      // with short rows.  Beside all ten seed waves a CU has room for six of these waves by registers (1 + 1 + 2 + 2) and for eight
+      // to ten by LDS (allocated in units of 1,280 or of 512 bytes); where these come first, sixteen of them hold a CU's registers
+      // until they end.  (Until round 10 the kernel had one form, compiled for six waves per SIMD -- 80 registers and 96 to 112 bytes
+      // of scratch per lane -- whose 1.7 KB of LDS admitted four or five beside ten seed waves.)
+      // For reads of up to 160 bases 24 workgroups per CU are the measured optimum (the seed
       // kernel's launch is short of its 7 waves per CU for 0.4 ms at most); for longer reads the seed kernel's launches are twice
       // as long, its waves came up late on many CUs, and the step was 69 ms with 12 or more against 54 with 6 (2 x 245 bases:
-      // profiles/r03_ab_sweeps.txt; round 2's 256-thread workgroups had hidden this: they rarely found room at all)
-      const int gbp = d->kn.gapless_blocks_per_cu > 0 ? d->kn.gapless_blocks_per_cu : (seg_template (c.L) <= 10 ? 24 : 6);
+      // profiles/r03_ab_sweeps.txt; round 2's 256-thread workgroups had hidden this: they rarely found room at all).  Since the
+      // kernel takes 109 to 115 registers instead of 80, four per CU are the optimum there (2 x 245: 54.95 M reads/s against 54.72
+      // with 6, 54.35 with 8, 54.10 with 12; profiles/r10_ab_sweeps.txt)
+      const int gbp = d->kn.gapless_blocks_per_cu > 0 ? d->kn.gapless_blocks_per_cu : (seg_template (c.L) <= 10 ? 24 : 4);
       ggrid = (n_ends + PM_GL_PER_BLOCK - 1) / PM_GL_PER_BLOCK;
       if (ggrid > d->n_cus * gbp)
         ggrid = d->n_cus * gbp;
       if (bgrid > (n_ends + 15) / 16)
         bgrid = (n_ends + 15) / 16;
     }
+  // (reads of up to PM_GL_SHORT_MM = 160 bases, the seed stage's class boundary: the kernel's short rows, 1 KB of LDS per workgroup)
+  const bool short_rows = seg_template (c.L) <= 10;
   if (pm_gapless_on (d))
-    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < false >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, S.hits, l.all, l.n_all,
-                        l.dp, l.n_dp, max_x, l.band, l.n_band, l.c3, l.n_c3);
+    launch_gapless < false > (d, short_rows, ggrid, c, S, l.all, l.n_all, l, max_x, l.c3, l.n_c3);
   // case (3) in a launch of its own over the problems it may decide (one in eight; what it refuses joins the DP's lists)
   if (l.c3)
-    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < true >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, S.hits, l.c3, l.n_c3,
-                        l.dp, l.n_dp, max_x, l.band, l.n_band, (uint32_t *) nullptr, (unsigned *) nullptr);
+    launch_gapless < true > (d, short_rows, ggrid, c, S, l.c3, l.n_c3, l, max_x, (uint32_t *) nullptr, (unsigned *) nullptr);
   // the problems the rule left open whose best diagonal has few mismatches: the DP restricted to a band of 32 diagonals,
   // four lanes per problem (pemap_band.hip.h); what is left for pm_sw_kernel are mostly the reads with a real indel
   if (l.band)

@@ -20,6 +20,9 @@
 // lanes per alignment in the SW kernels are a template parameter: 8 (half a DPP row) or 16 (a whole one)
 // register budget of the SW kernels: 4 VGPRs of state per owned column (two doubles) plus temporaries
 #define PM_WAVES_PER_EU(W) ((W) <= 13 ? 4 : (W) <= 19 ? 3 : (W) <= 32 ? 2 : 1)
+// ... of pm_sw_kernel per form: the bound under which the form has no scratch (W = 13 under four waves spilled 22 to 33 VGPRs,
+// < 16, 16, false > and < 19, *, true > under three 1 and 2)
+#define PM_SW_WAVES_PER_EU(W, DIRS) ((W) <= 10 ? 4 : (W) <= 13 ? 3 : (W) <= 16 ? ((DIRS) ? 3 : 2) : ((DIRS) ? 2 : 3))
 
 struct PmIndex
 {

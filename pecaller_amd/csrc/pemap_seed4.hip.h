@@ -102,6 +102,10 @@ template < int SMAX, int TIER > struct __align__ (16) PmSeed4Shared
 };
 
 static_assert (sizeof (PmSeed4Shared < 19, 1 >) <= 65536, "dynamic LDS of a launch without an attribute");
+// a first-tier wave's LDS for reads of up to 160 bases: allocated as 15,360 bytes, so ten waves leave 10,240 of a CU's 163,840 bytes
+// to the other stream's kernels (tests/test_kernel_resources_cpu.py reads this constant: the struct does not grow unnoticed)
+#define PM_S4_SHARED_10_0_BYTES 14976
+static_assert (sizeof (PmSeed4Shared < 10, 0 >) == PM_S4_SHARED_10_0_BYTES, "the first tier's LDS per wave");
 extern __shared__ __align__ (16) uint8_t pm_seed4_lds[];
 
 #ifdef PEMAP_TIMING_PROBES

@@ -192,7 +192,10 @@ template < int W > __device__ __noinline__ uint64_t pm_slow_mask (const uint8_t 
 // ([lane][step][DW]) and flushed with 16-byte-per-lane stores in which 4 (or more) adjacent lanes cover one lane's
 // chunk, i.e. whole 64-byte lines (chunks are 64-byte multiples because tstride is a multiple of 16).
 // steps collected per flush: the smallest count that makes a lane's chunk a whole number of 64-byte lines
-#define PM_STAGE_OF(DW) ((DW) == 2 ? 8 : 16)
+#ifndef PM_STAGE_DW2
+#define PM_STAGE_DW2 8
+#endif
+#define PM_STAGE_OF(DW) ((DW) == 2 ? PM_STAGE_DW2 : 16)
 
 template < int W, int PM_LPA > __device__ __forceinline__ void pm_flush_dirs (const uint32_t * stage, uint32_t * const *slab_of_group, int lane, int tstride,
                                                                   int t0)
@@ -498,7 +501,8 @@ __device__ __forceinline__ uint64_t pm_rc8 (uint64_t v, int vacated_bits)
 }
 
 #define PM_GAPLESS 4            // flag in PmHits::stk beside the plane number
-#define PM_GL_QUEUE 32           // problems a wave of pm_gapless_kernel collects before it fetches a list's counter
+#define PM_GL_QUEUE 32           // problems a wave of pm_gapless_kernel collects before it fetches a list's counter (long rows)
+#define PM_GL_QUEUE_SHORT 24     // ... with short rows: three queues of 24 words beside the rows are the block's 1,024 bytes
 
 // problems the rule leaves open go to tasks_band (pm_band_kernel, pemap_band.hip.h) when the best diagonal has at most
 // PM_BAND_MAXX_ mismatches -- the condition under which the banded DP is exact -- and to tasks_dp (the full DP) otherwise
@@ -513,19 +517,51 @@ static_assert (PM_BAND_K >= 2 && PM_BAND_K <= 5, "the band holds at most 32 diag
 // (one-wave workgroups: a wave goes wherever a SIMD has room beside the seed kernel's waves; four to a workgroup waited for room for four)
 #define PM_GL_BLOCK 64
 #define PM_GL_PER_BLOCK (PM_GL_BLOCK / 32)     // problems a workgroup works on at a time: one per half-wave
+// Waves per SIMD the kernel is compiled for: four, 109 and 115 registers, no scratch in either row form.
+// Short rows run beside the ten waves of pm_seed4_kernel < 10, 0 > on a CU (128 VGPRs each: three on two SIMDs, two on the other two),
+// which leave a SIMD 128 or 256 of its 512 registers: one or two of these waves find room at anything from 88 to 128 registers.
+// Five (96 registers, 16 and 32 bytes of scratch per lane) measures the same, six (80 registers, 96 and 112 bytes of scratch, the
+// bound until round 10) slower (profiles/r10_ab_sweeps.txt, block b1).
+// Long rows run beside seed waves compiled for two to a SIMD (179 to 200 registers each).  With six workgroups per CU, the launch
+// width chosen for the six-wave build, four waves were slower at 2 x 245 bases (54.46 M reads/s against 55.00 with six); with FOUR
+// workgroups per CU (launch_cascade) they are level with it (profiles/r10_ab_sweeps.txt, blocks r2tsw and r2tsw3).
+#ifndef PM_GL_WAVES_PER_EU
+#define PM_GL_WAVES_PER_EU 4
+#endif
+// The rows of a problem in LDS.  SHORT: reads of up to PM_GL_SHORT_MM bases (the host's class boundary, seg_template <= 10).
+//   rd:   pieces are stored at rd[8 c] for 8 c < ((mm + 7) & ~7) and read for c < nch = (mm + 7) >> 3, the same set: the row ends at
+//         (mm + 7) & ~7 <= 160 for mm <= 160.
+//   win:  the window starts at byte 8 of its row, so that case (3)'s diagonal -1 (off = 8 c - 1, off & ~7 = 8 c - 8) finds a piece
+//         in front of it at byte 8 c >= 0 (never written for c = 0; its one byte is never used).  Pieces are stored at win[8 + 8 c] for
+//         8 c < nn + 16, the last one at 8 c = (nn + 15) & ~7: the stores end at 16 + ((nn + 15) & ~7).  A comparison reads 16 bytes at
+//         win[8 + (off & ~7)], off = d + 8 c with d <= nn - mm + 1 (case (3)'s diagonal D + 1) and 8 c <= ((mm + 7) & ~7) - 8, so
+//         off <= nn and the reads end at 24 + (nn & ~7) <= 16 + ((nn + 15) & ~7): inside what was stored.  With nn <= mm + 2 PM_SLOP + 1
+//         <= 181 that is 16 + 192 = 208 bytes.
+//   Two problems per block: 2 x (160 + 208) = 736 bytes, and 3 x 24 queue words (C3: 2 x 24 + 1) make 1,024 (932).
+// Long rows (reads of up to 278 bases, nn <= 299): 320 and 16 + 312 = 328 <= 360 bytes, as before.
+#define PM_GL_SHORT_MM 160
+template < bool SHORT > struct PmGlRows
+{
+  static constexpr int RD = SHORT ? (PM_GL_SHORT_MM + 7) / 8 * 8 : 320;
+  static constexpr int WIN = SHORT ? 16 + (PM_GL_SHORT_MM + 2 * PM_SLOP + 1 + 15) / 8 * 8 : 360;
+  static constexpr int QUEUE = SHORT ? PM_GL_QUEUE_SHORT : PM_GL_QUEUE;
+};
+static_assert (PmGlRows < true >::RD == 160 && PmGlRows < true >::WIN == 208, "short rows as derived above");
+static_assert (PM_GL_PER_BLOCK * (PmGlRows < true >::RD + PmGlRows < true >::WIN) + 3 * 4 * PmGlRows < true >::QUEUE <= 1024, "the short form's LDS budget");
 // C3 = false, the launch over all problems: cases (1) and (2); a problem that case (3) may decide goes to tasks_c3 when that list is
 // given, and to the DP's lists like the rest when it is not.  C3 = true, a second launch over tasks_c3 alone: all three cases.  (Case
 // (3) inside the one launch took registers from every problem's path: the kernel was a third slower for one problem in eight.)
-template < bool C3 > __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gapless_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, const uint32_t * tasks,
+// SHORT: the rows and queues of PmGlRows < true >; the host (launch_gapless) chooses it for reads of up to PM_GL_SHORT_MM bases.
+template < bool C3, bool SHORT > __global__ __launch_bounds__ (PM_GL_BLOCK, PM_GL_WAVES_PER_EU) void pm_gapless_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, const uint32_t * tasks,
                                                           const unsigned *n_tasks_p, uint32_t * tasks_dp, unsigned *n_tasks_dp, int max_x,
                                                           uint32_t * tasks_band, unsigned *n_tasks_band, uint32_t * tasks_c3, unsigned *n_tasks_c3)
 {
-  __shared__ __align__ (8) uint8_t rd[PM_GL_PER_BLOCK][320];
-  // the window: nn <= 299 bytes, read in 8-byte pieces up to 8 bytes past 8-byte boundaries; it starts at byte 8 of its row, so that
-  // case (3)'s diagonal -1 finds a piece (never written, its one byte never used) in front of it
-  __shared__ __align__ (8) uint8_t win[PM_GL_PER_BLOCK][360];
-  __shared__ uint32_t q_band[PM_GL_BLOCK / 64][PM_GL_QUEUE], q_dp[PM_GL_BLOCK / 64][PM_GL_QUEUE];       // per wave: problems on their way to the two DP lists
-  __shared__ uint32_t q_c3[PM_GL_BLOCK / 64][C3 ? 1 : PM_GL_QUEUE];       // ... and to the second launch
+  using Rows = PmGlRows < SHORT >;
+  constexpr int QN = Rows::QUEUE;       // (a round adds at most PM_GL_PER_BLOCK = 2 problems to a queue: flushed above QN - 2)
+  __shared__ __align__ (8) uint8_t rd[PM_GL_PER_BLOCK][Rows::RD];
+  __shared__ __align__ (8) uint8_t win[PM_GL_PER_BLOCK][Rows::WIN];
+  __shared__ uint32_t q_band[PM_GL_BLOCK / 64][QN], q_dp[PM_GL_BLOCK / 64][QN];       // per wave: problems on their way to the two DP lists
+  __shared__ uint32_t q_c3[PM_GL_BLOCK / 64][C3 ? 1 : QN];       // ... and to the second launch
   const int wv = threadIdx.x >> 6;
   int n_qb = 0, n_qd = 0, n_q3 = 0;
   auto flush_queue = [&] (const uint32_t * q, int &n, uint32_t * dst, unsigned *counter)
@@ -914,7 +950,7 @@ template < bool C3 > __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gaple
             sc = (double) mm;
         }
       // what the rule leaves open goes to the banded DP's list or to the full DP's, through a queue of the wave in LDS: one fetch of
-      // the list's counter per PM_GL_QUEUE problems.  (One per problem -- 70 K same-address atomics per launch, each a round trip
+      // the list's counter per QN problems.  (One per problem -- 70 K same-address atomics per launch, each a round trip
       // that the next one waits behind -- was the kernel's time: the single-address rate is ~85 M per second.)
       {
         int xmin = mism;
@@ -931,9 +967,9 @@ template < bool C3 > __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gaple
           q_dp[wv][n_qd + (int) __popcll (md & ((1ull << lane) - 1ull))] = (uint32_t) o;
         n_qb += (int) __popcll (mb);
         n_qd += (int) __popcll (md);
-        if (n_qb > PM_GL_QUEUE - 2)
+        if (n_qb > QN - 2)
           flush_queue (q_band[wv], n_qb, tasks_band, n_tasks_band);
-        if (n_qd > PM_GL_QUEUE - 2)
+        if (n_qd > QN - 2)
           flush_queue (q_dp[wv], n_qd, tasks_dp, n_tasks_dp);
         if (!C3)
           {
@@ -941,7 +977,7 @@ template < bool C3 > __global__ __launch_bounds__ (PM_GL_BLOCK, 6) void pm_gaple
             if (to_c3)
               q_c3[wv][n_q3 + (int) __popcll (m3 & ((1ull << lane) - 1ull))] = (uint32_t) o;
             n_q3 += (int) __popcll (m3);
-            if (n_q3 > PM_GL_QUEUE - 2)
+            if (n_q3 > QN - 2)
               flush_queue (q_c3[wv], n_q3, tasks_c3, n_tasks_c3);
           }
       }
@@ -990,7 +1026,7 @@ __device__ __forceinline__ int pm_wave_max (int v)
 
 // One persistent wave per 64 / PM_LPA problems.  DIRS: the problems are traceable alignments (the only hit of an end, or the winner
 // of a multi-hit end) and write their nibbles to the end's slab.
-template < int W, int PM_LPA, bool DIRS > __global__ __launch_bounds__ (64, PM_WAVES_PER_EU (W)) void pm_sw_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h,
+template < int W, int PM_LPA, bool DIRS > __global__ __launch_bounds__ (64, PM_SW_WAVES_PER_EU (W, DIRS)) void pm_sw_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h,
                                                                                               const uint32_t * tasks,
                                                                                               const unsigned *n_tasks_p, PmCounters * ctr,
                                                                                               uint32_t * dirbuf, uint32_t * dump_slab, int tstride,

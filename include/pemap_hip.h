@@ -294,6 +294,16 @@ int pecall_dev_sites_stage (pecall_dev * dev, const uint16_t * reads, const uint
 int pecall_dev_sites_run (pecall_dev * dev, int haploid, double threshold, double theta, float *kernel_ms);
 int pecall_dev_sites_collect (pecall_dev * dev, int8_t * call, double *posterior, int8_t * site_type, int32_t * allele_count,
                               int8_t * n_pass, int32_t * denovo);
+/* How the last pecall_dev_sites_run divided its columns among the kernels (what PECALL_LIST_STATS prints), valid from that run until
+ * something new is staged or called.  out[10]:
+ *   [0]     columns run
+ *   [1..4]  columns the shortcut kernels left to the beam search, by unsettled samples < 3 / < 8 / < 20 / more (beyond 128 samples a
+ *           column too deep for the head of the ln n! table counts under "more"); where a chunk had a second pass with the whole
+ *           table, what both passes listed
+ *   [5]     columns on the deep list (up to 128 samples: a sample of 1,447 reads or more; they get the second pass)
+ *   [6..9]  columns whose beam search was started ahead of the shortcut kernels (PECALL_HEAVY_MIN), by samples with variant reads
+ *           < 12 / < 20 / < 32 / more; these are in none of [1..5] */
+int pecall_dev_sites_stats (pecall_dev * dev, uint64_t * out);
 /* ---- PECaller: pileup columns made on the device from the samples' record streams ----
  * What the host otherwise does before pecall_dev_call_sites: the k-way merge of the pileup streams (find_lowest and the dispatcher's
  * per-column loop, pecaller.c:865-923, 1820-1833).  A record is the pileup file's own 16 bytes, little-endian:

@@ -33,6 +33,24 @@
 #define NA 6                    /* NO_ALLELES: A C G T Del Ins */
 #define NG 14                   /* MAX_GENOTYPES */
 #define MAX_CONFIGS 514         /* pecaller.c:1180 */
+/* Per-column coverage statistics (ora_call_sites_stats; tests/oracle_py.py names them the same way).  "Unsettled": a sample above the
+ * depth floor whose best genotype in pass 1 is not the reference homozygote, or is by 2.31 nats or less. */
+enum
+{
+  ORA_ST_DEEP,                  /* pass 1: samples above the depth floor (0 where the site filters dropped the column) */
+  ORA_ST_UNSET,                 /* pass 1: unsettled samples */
+  ORA_ST_EARLY,                 /* pass 1: an unsettled sample precedes a settled one in the margin order */
+  ORA_ST_PRE_LIST,              /* pass 1: the longest list an unsettled sample's expansion started from */
+  ORA_ST_NO_HOM,                /* pass 1: the cut after an unsettled sample's expansion left no homozygous configuration */
+  ORA_ST_MAX_LIST,              /* longest list an expansion built */
+  ORA_ST_CUT,                   /* the cut at MAX_CONFIGS engaged */
+  ORA_ST_FALLBACK,              /* 1 the homozygous fallback was added | 2 with best_hom > 3 | 4 and the list was sorted again */
+  ORA_ST_POST_TIE,              /* two neighbouring kept configurations had equal posteriors after a sort */
+  ORA_ST_MARGIN_TIE,            /* two samples above the floor had equal margins: 1 in pass 1 | 2 in any pass */
+  ORA_ST_PASSES,
+  ORA_ST_N
+};
+
 #define minim(a,b) ((a<b)?a:b)
 #define maxim(a,b) ((a>b)?a:b)
 
@@ -60,6 +78,8 @@ typedef struct
   int cap_cur, cap_nxt;
   int *idx, *tmp;
   int max_list;                 /* longest list fill_config_probs has built (test coverage statistic) */
+  int32_t *st;                  /* the column's statistics (ORA_ST_*), or NULL; st_unset: the expansion in hand is pass 1's, of an unsettled sample */
+  int st_unset;
   int site_hap;                 /* HAPLOID of the column: the run's, or forced for chrY / chrMT in BED guide mode (pecaller.c:955-957) */
   /* pedigree (use_ped = y) */
   int use_ped;
@@ -400,6 +420,14 @@ clean_cfgs (Caller * c, int n, int ref, double ct, const int *tot, const double 
   for (int i = 1; i < max; i++)
     if (cn[0].post > cn[i].post + ct)
       max = i;
+  if (c->st)
+    {
+      if (max == MAX_CONFIGS && n > MAX_CONFIGS)
+        c->st[ORA_ST_CUT] = 1;
+      for (int i = 1; i < max; i++)
+        if (cn[i].post == cn[i - 1].post)
+          c->st[ORA_ST_POST_TIE] = 1;
+    }
   int found_hom = 0;
   for (int i = 0; i < max && !found_hom; i++)
     if (cn[i].no_alleles == 1)
@@ -410,6 +438,12 @@ clean_cfgs (Caller * c, int n, int ref, double ct, const int *tot, const double 
       for (int i = 1; i < NA; i++)
         if (cn[0].acount[i] > cn[0].acount[best_hom])
           best_hom = i;
+      if (c->st)
+        {
+          c->st[ORA_ST_FALLBACK] |= 1 | (best_hom > 3 ? 2 : 0);
+          if (c->st_unset)
+            c->st[ORA_ST_NO_HOM] = 1;
+        }
       if (best_hom > 3)
         best_hom = ref;
       cfg_init (c, &cn[max], best_hom, tot);
@@ -417,7 +451,11 @@ clean_cfgs (Caller * c, int n, int ref, double ct, const int *tot, const double 
       cfg_like (c, &cn[max], tot, like);
       cn[max].post = cn[max].like;
       if (cn[max].post > cn[max - 1].post)
-        sort_cfgs (c, cn, max + 1, c->nxt);
+        {
+          sort_cfgs (c, cn, max + 1, c->nxt);
+          if (c->st)
+            c->st[ORA_ST_FALLBACK] |= 4;
+        }
       max++;
     }
   return max;
@@ -526,6 +564,8 @@ expand_cfgs (Caller * c, int n, int who, int ref, int chrom, double thres, const
     cfg_copy (&cn[i], &nw[i], c->indiv);
   if (newcount > c->max_list)
     c->max_list = newcount;
+  if (c->st && newcount > c->st[ORA_ST_MAX_LIST])
+    c->st[ORA_ST_MAX_LIST] = newcount;
   return newcount;
 }
 
@@ -784,6 +824,35 @@ call_site (Caller * c, const uint16_t * rd, int dom, int chrom_in, int8_t * call
             }
           ord[k] = v;
         }
+      int unset[N];
+      for (int i = 0; i < N; i++)
+        unset[i] = pass == 1 && tot[i] > md && !(initial_call[i] == dom && initial_p[i] > 2.31);
+      if (c->st)
+        {
+          int seen_unset = 0;
+          for (int k = 0; k < N; k++)
+            {
+              const int ind = ord[k];
+              if (tot[ind] <= md)
+                continue;
+              if (pass == 1)
+                {
+                  c->st[ORA_ST_DEEP]++;
+                  c->st[ORA_ST_UNSET] += unset[ind];
+                  if (unset[ind])
+                    seen_unset = 1;
+                  else if (seen_unset)
+                    c->st[ORA_ST_EARLY] = 1;
+                }
+              for (int q = k + 1; q < N; q++)
+                if (tot[ord[q]] > md)
+                  {
+                    if (initial_p[ord[q]] == initial_p[ind])
+                      c->st[ORA_ST_MARGIN_TIE] |= pass == 1 ? 3 : 2;
+                    break;
+                  }
+            }
+        }
       for (int i = 0; i < total; i++)
         cfg_like (c, &c->cur[i], tot, (const double (*)[NG + 1]) like);
       total = clean_cfgs (c, total, dom, ct, tot, (const double (*)[NG + 1]) like);
@@ -792,8 +861,12 @@ call_site (Caller * c, const uint16_t * rd, int dom, int chrom_in, int8_t * call
           const int ind = ord[k];
           if (tot[ind] > md)
             {
+              c->st_unset = unset[ind];
+              if (c->st && unset[ind] && total > c->st[ORA_ST_PRE_LIST])
+                c->st[ORA_ST_PRE_LIST] = total;
               total = expand_cfgs (c, total, ind, dom, chrom, ct, reads[ind], like[ind]);
               total = clean_cfgs (c, total, dom, ct, tot, (const double (*)[NG + 1]) like);
+              c->st_unset = 0;
             }
           else
             {
@@ -978,19 +1051,26 @@ call_site (Caller * c, const uint16_t * rd, int dom, int chrom_in, int8_t * call
           }
       }
   *n_pass = pass;
+  if (c->st)
+    c->st[ORA_ST_PASSES] = pass;
   return type;
 }
 
 /* reads[n_sites][indiv][6], dom[n_sites] (0..3 = A C G T; anything else is a site the reference skips: outputs 'N'/1, type -1),
- * chrom[n_sites] (0 autosome, 1 chrX, 2 chrY, 3 chrMT, + 16 = HAPLOID forced for the column; NULL = all autosomal) -> call[n_sites][indiv], p[n_sites][indiv], type[n_sites], allele_count[n_sites][6], n_pass[n_sites] */
+ * chrom[n_sites] (0 autosome, 1 chrX, 2 chrY, 3 chrMT, + 16 = HAPLOID forced for the column; NULL = all autosomal) -> call[n_sites][indiv], p[n_sites][indiv], type[n_sites], allele_count[n_sites][6], n_pass[n_sites]
+ * ora_call_sites_stats: the same, and stats[n_sites][ORA_ST_N] (NULL: none) */
 void
-ora_call_sites (void *p, const uint16_t * reads, const uint8_t * dom, const uint8_t * chrom, long n_sites, int8_t * call, double *post,
-                int8_t * type, int32_t * allele_count, int8_t * n_pass, int32_t * denovo)
+ora_call_sites_stats (void *p, const uint16_t * reads, const uint8_t * dom, const uint8_t * chrom, long n_sites, int8_t * call, double *post,
+                      int8_t * type, int32_t * allele_count, int8_t * n_pass, int32_t * denovo, int32_t * stats)
 {
   Caller *c = p;
+  if (stats)
+    memset (stats, 0, (size_t) n_sites * ORA_ST_N * sizeof (int32_t));
   for (long s = 0; s < n_sites; s++)
     {
       int ac[NA] = { 0, 0, 0, 0, 0, 0 }, np = 0, dn = 0;
+      c->st = stats ? stats + s * ORA_ST_N : NULL;
+      c->st_unset = 0;
       if (dom[s] > 3)
         {
           for (int i = 0; i < c->indiv; i++)
@@ -1009,4 +1089,18 @@ ora_call_sites (void *p, const uint16_t * reads, const uint8_t * dom, const uint
       if (denovo)
         denovo[s] = dn;
     }
+  c->st = NULL;
+}
+
+void
+ora_call_sites (void *p, const uint16_t * reads, const uint8_t * dom, const uint8_t * chrom, long n_sites, int8_t * call, double *post,
+                int8_t * type, int32_t * allele_count, int8_t * n_pass, int32_t * denovo)
+{
+  ora_call_sites_stats (p, reads, dom, chrom, n_sites, call, post, type, allele_count, n_pass, denovo, NULL);
+}
+
+int
+ora_site_stats_n (void)
+{
+  return ORA_ST_N;
 }

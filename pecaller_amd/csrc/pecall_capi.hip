@@ -255,6 +255,10 @@ struct pecall_dev
   size_t cap_chunks = 0;        // chunks whose events and counters are all there
   unsigned long long *d_chunk_ctr = nullptr;    // [cap_chunks][PCS_CTRS]
   unsigned long long *d_heavy_ctr = nullptr;    // [1 + cap_chunks][PCS_CTRS]: slot 0 for a whole run's list (resident columns), slot 1 + k for chunk k's (the seam)
+  // pecall_dev_sites_stats: what the first pass listed in the chunks whose second pass then cleared their counters; was the early list made?
+  unsigned long long run_listed_first[4] = { 0ull, 0ull, 0ull, 0ull };
+  bool run_heavy = false;
+  long run_stats_sites = 0;     // columns of the sites_run the counters belong to (0: the last results are a seam call's, whose chunks count for themselves)
   unsigned long long *h_ctrs = nullptr; // page-locked: the chunks' counters, behind them the sparse list's length, on their way to the host (pcs_sparse_len_at)
   char *h_in[PCS_SLOTS] = { }, *h_out[PCS_SLOTS] = { }; // pinned staging for callers whose buffers are not pinned
   size_t h_in_bytes = 0, h_out_bytes = 0;
@@ -998,6 +1002,7 @@ extern "C" int pecall_dev_sites_run (pecall_dev * d, int haploid, double thresho
   if (d->staged_sites <= 0)
     return pc_fail (d, "sites_run: nothing staged");
   d->result_sites = 0;
+  d->run_stats_sites = 0;
   PcsParams P;
   PCTRY (pcs_params (d, indiv, haploid, threshold, theta, P));
   PCTRY (pcs_ensure_chunks (d, d->staged_sites));
@@ -1017,9 +1022,16 @@ extern "C" int pecall_dev_sites_run (pecall_dev * d, int haploid, double thresho
   PCTRY (pcs_run_join (d, nch, heavy));
   std::vector < int >deep;
   PCTRY (pcs_deep_chunks (d, P, nch, deep));
+  for (int b = 0; b < PCS_BUCKETS; b++)
+    d->run_listed_first[b] = 0ull;
+  d->run_heavy = heavy;
   if (!deep.empty ())
     {
-      // (deep chunks: the second pass is part of the run; its interval ends behind it)
+      // (deep chunks: the second pass is part of the run; its interval ends behind it.  It clears the chunk's counts of listed columns, which
+      // pcs_deep_chunks has just brought to the host: kept for pecall_dev_sites_stats)
+      for (int q : deep)
+        for (int b = 0; b < PCS_BUCKETS; b++)
+          d->run_listed_first[b] += ((const unsigned *) (d->h_ctrs + (size_t) q * PCS_CTRS + PCS_CTR_LISTED))[b];
       for (int q : deep)
         PCTRY (pcs_chunk_kernels (d, P, q, true, false, heavy ? 1 : 0));
       PCTRY (pcs_run_join (d, nch, heavy));
@@ -1029,6 +1041,39 @@ extern "C" int pecall_dev_sites_run (pecall_dev * d, int haploid, double thresho
   if (getenv ("PECALL_LIST_STATS"))
     pcs_list_stats (d, nch, heavy);
   d->result_sites = d->staged_sites;
+  d->run_stats_sites = d->staged_sites;
+  return 0;
+}
+
+// what PECALL_LIST_STATS prints, as numbers (the layout is described at the declaration)
+extern "C" int pecall_dev_sites_stats (pecall_dev * d, uint64_t * out)
+{
+  PCCHK (d, hipSetDevice (d->device));
+  if (!out)
+    return pc_fail (d, "sites_stats: no array");
+  if (d->staged_sites <= 0 || d->result_sites != d->staged_sites || d->run_stats_sites != d->staged_sites)
+    return pc_fail (d, "sites_stats: valid after sites_run only");
+  const int nch = pcs_n_chunks (d);
+  for (int i = 0; i < 2 + 2 * PCS_BUCKETS; i++)
+    out[i] = 0;
+  out[0] = (uint64_t) d->staged_sites;
+  PCCHK (d, hipMemcpy (d->h_ctrs, d->d_chunk_ctr, (size_t) nch * PCS_CTRS * sizeof (unsigned long long), hipMemcpyDeviceToHost));
+  for (int q = 0; q < nch; q++)
+    {
+      const unsigned *c = (const unsigned *) (d->h_ctrs + (size_t) q * PCS_CTRS + PCS_CTR_LISTED);
+      for (int b = 0; b < PCS_BUCKETS; b++)
+        out[1 + b] += c[b];
+      out[1 + PCS_BUCKETS] += (unsigned) d->h_ctrs[(size_t) q * PCS_CTRS + PCS_CTR_DEEP];
+    }
+  for (int b = 0; b < PCS_BUCKETS; b++)
+    out[1 + b] += d->run_listed_first[b];
+  if (d->run_heavy)
+    {
+      unsigned hc[PCS_BUCKETS];
+      PCCHK (d, hipMemcpy (hc, pcs_heavy_ctrs (d, 0) + PCS_CTR_LISTED, sizeof hc, hipMemcpyDeviceToHost));
+      for (int b = 0; b < PCS_BUCKETS; b++)
+        out[2 + PCS_BUCKETS + b] = hc[b];
+    }
   return 0;
 }
 
@@ -1278,6 +1323,7 @@ static int pcs_call_sites_impl (pecall_dev * d, PcsIo io, long n_sites, int indi
   if (io.sparse && (!io.post_site || !io.post_rows || !io.n_post || io.post_cap == 0))
     return pc_fail (d, "call_sites_sparse: the list of posteriors needs post_site, post_rows, a capacity and n_post");
   d->result_sites = 0;
+  d->run_stats_sites = 0;
   if (io.sparse)
     {
       *io.n_post = 0;

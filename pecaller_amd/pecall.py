@@ -37,6 +37,7 @@ class PecallDev:
         L.pecall_dev_set_pedigree.argtypes = [vp, i, vp, vp, vp, vp, vp, dbl]
         L.pecall_dev_sites_stage.argtypes = [vp, vp, vp, vp, C.c_long, i]
         L.pecall_dev_sites_run.argtypes = [vp, i, dbl, dbl, C.POINTER(C.c_float)]
+        L.pecall_dev_sites_stats.argtypes = [vp, vp]
         L.pecall_dev_sites_collect.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.pecall_dev_pin_host.argtypes = [vp, vp, C.c_uint64]
         L.pecall_dev_unpin_host.argtypes = [vp, vp]
@@ -115,6 +116,15 @@ class PecallDev:
         self._rindiv = self._sshape[1]
         self._ck(self.L.pecall_dev_sites_run(self.h, int(haploid), float(threshold), float(theta), C.byref(ms)))
         return ms.value
+
+    def sites_stats(self):
+        """how the last sites_run divided its columns (pecall_dev_sites_stats) -> dict(columns, listed [4], deep, early [4]): columns the
+        shortcut kernels left to the beam search by unsettled samples (< 3, < 8, < 20, more), columns on the deep list, columns whose
+        beam search started ahead of the shortcut kernels by samples with variant reads (< 12, < 20, < 32, more)"""
+        out = np.zeros(10, np.uint64)
+        self._ck(self.L.pecall_dev_sites_stats(self.h, _p(out)))
+        v = [int(x) for x in out]
+        return dict(columns=v[0], listed=v[1:5], deep=v[5], early=v[6:10])
 
     def sites_collect(self):
         n_sites, indiv = self._sshape

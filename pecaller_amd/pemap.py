@@ -25,7 +25,7 @@ SYMBOLS = [
     "pemap_dev_run_stats", "pemap_dev_debug_hits", "pemap_dev_index_share", "pemap_dev_absorb",
     "pecall_dev_create", "pecall_dev_destroy", "pecall_dev_last_error", "pecall_dev_site_like", "pecall_dev_stage",
     "pecall_dev_run", "pecall_dev_collect", "pecall_dev_call_sites", "pecall_dev_call_sites_sparse", "pecall_dev_set_pedigree",
-    "pecall_dev_sites_stage", "pecall_dev_sites_run", "pecall_dev_sites_collect", "pecall_dev_pin_host", "pecall_dev_unpin_host",
+    "pecall_dev_sites_stage", "pecall_dev_sites_run", "pecall_dev_sites_stats", "pecall_dev_sites_collect", "pecall_dev_pin_host", "pecall_dev_unpin_host",
     "pecall_dev_sites_stage_records", "pecall_dev_sites_gather", "pecall_dev_sites_merge_ms", "pecall_dev_call_records",
     "pecall_dev_sites_base_text",
 ]

@@ -153,6 +153,8 @@ def pecall_lib():
         L.ora_caller_max_list.argtypes = [C.c_void_p]
         L.ora_call_sites.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ora_call_sites_stats.argtypes = L.ora_call_sites.argtypes + [C.c_void_p]
+        assert L.ora_site_stats_n() == len(SITE_STATS)
         L.ora_caller_set_ped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]
         _plib = L
     return _plib
@@ -184,10 +186,16 @@ def kid_lists(dad, mom, order=None):
     return off, np.array([x for k in kids for x in k] + [0], np.int32)
 
 
+# the per-column statistics of ora_call_sites_stats, in the order of the ORA_ST_* of oracle/pecall_site_oracle.c (described there)
+SITE_STATS = ("deep", "unset", "early", "pre_list", "no_hom", "max_list", "cut", "fallback", "post_tie", "margin_tie", "passes")
+FALLBACK_ADDED, FALLBACK_INDEL, FALLBACK_RESORT = 1, 2, 4
+
+
 def call_sites(reads, dom, threshold=0.95, theta=0.001, haploid=False, chrom=None, ped=None, threads=None):
     """the per-site caller oracle (oracle/pecall_site_oracle.c): reads[n_sites][indiv][6], dom[n_sites] in 0..3 (else skipped),
     chrom[n_sites] 0 autosome / 1 X / 2 Y / 3 MT, ped = dict(dad, mom, sex, order, denovo_rate) or None
-    -> call[n_sites][indiv] (0..13, 14 = N), p, site type, allele counts, passes; call_sites.denovo = d_count per site.
+    -> call[n_sites][indiv] (0..13, 14 = N), p, site type, allele counts, passes; call_sites.denovo = d_count per site,
+    call_sites.stats = dict of the per-column statistics named in SITE_STATS (int32 [n_sites] each).
     Columns are independent: blocks of them go to `threads` callers side by side (default: up to 8, one per CPU; a variant column of a
     few hundred samples costs the oracle seconds), each with its own handle, writing its rows of the shared result arrays."""
     import threading
@@ -202,6 +210,7 @@ def call_sites(reads, dom, threshold=0.95, theta=0.001, haploid=False, chrom=Non
     ac = np.zeros((n_sites, 6), np.int32)
     npass = np.zeros(n_sites, np.int8)
     den = np.zeros(n_sites, np.int32)
+    stats = np.zeros((n_sites, len(SITE_STATS)), np.int32)
     if ped is not None:
         dad = np.ascontiguousarray(ped["dad"], np.int32)
         mom = np.ascontiguousarray(ped["mom"], np.int32)
@@ -224,8 +233,8 @@ def call_sites(reads, dom, threshold=0.95, theta=0.001, haploid=False, chrom=Non
                 if a is None:
                     break
                 b = min(a + block, n_sites)
-                L.ora_call_sites(h, _p(reads[a:b]), _p(dom[a:b]), _p(cy[a:b]), b - a, _p(call[a:b]), _p(p[a:b]), _p(typ[a:b]), _p(ac[a:b]), _p(npass[a:b]),
-                                 _p(den[a:b]))
+                L.ora_call_sites_stats(h, _p(reads[a:b]), _p(dom[a:b]), _p(cy[a:b]), b - a, _p(call[a:b]), _p(p[a:b]), _p(typ[a:b]), _p(ac[a:b]),
+                                       _p(npass[a:b]), _p(den[a:b]), _p(stats[a:b]))
             with lock:
                 max_list[0] = max(max_list[0], L.ora_caller_max_list(h))      # longest configuration list seen (coverage statistic)
         except Exception as e:          # (surfaced by the caller: a thread's exception would otherwise be lost)
@@ -246,4 +255,5 @@ def call_sites(reads, dom, threshold=0.95, theta=0.001, haploid=False, chrom=Non
         raise errors[0]
     call_sites.max_list = max_list[0]
     call_sites.denovo = den
+    call_sites.stats = {k: stats[:, i].copy() for i, k in enumerate(SITE_STATS)}
     return call, p, typ, ac, npass

@@ -10,6 +10,16 @@ def test_site_oracle_matches_reference_text(tag):
     f = fx.load(tag)
     call, p, typ, ac, npass = oracle_py.call_sites(f["reads"], f["dom"], ped=f.get("ped"))
     den = oracle_py.call_sites.denovo
+    max_list, stats = oracle_py.call_sites.max_list, oracle_py.call_sites.stats
+    assert max_list == stats["max_list"].max()
+    # what the fixtures reach in the beam search, so that a changed generator cannot lose it: pcs_call_kernel's move from the LDS pool (32
+    # entries) to the HBM pool; the cut at max_configs = 514 (the list is 3 x 514 there); the fallback configuration sorted into the list
+    if tag == "pecall_sites":
+        assert max_list > 32
+    if tag == "pecall_wide":
+        assert max_list >= 515 and stats["cut"].any()
+    if tag == "pecall_ped":
+        assert (stats["fallback"] & oracle_py.FALLBACK_RESORT).any()
     n_base = n_snp = 0
     bad = []
     for i, pos in enumerate(f["pos"]):

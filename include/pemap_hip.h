@@ -342,6 +342,32 @@ int pecall_dev_call_records (pecall_dev * dev, const void *const *recs, const ui
                              int haploid, double threshold, double theta, int8_t * call, uint32_t * post_site, double *post_rows,
                              uint64_t post_cap, uint64_t * n_post, int8_t * site_type, int32_t * allele_count, int8_t * n_pass,
                              int32_t * denovo);
+/* ---- PECaller: the columns of a guide file's intervals made on the device ----
+ * What the host otherwise does with a BED guide file (the per-position loop of pecaller.c:941-1039): every position of the listed
+ * intervals is a column, covered or not.  pecall_dev_sites_stage_records_guided is pecall_dev_sites_stage_records with the columns'
+ * positions taken from a list of intervals instead of from the records; recs, n_recs, indiv, p0, span, ref_letters, ref_len, *n_cols
+ * and col_slot are as there, and instead of chrom_by_slot:
+ *   iv_first[n_iv], iv_count[n_iv]    interval k holds the slots (slot = position - p0) [iv_first[k], iv_first[k] + iv_count[k])
+ *   iv_chrom[n_iv] (may be NULL: 0)   the chromosome byte of every column of interval k (chrom_type above; the host program passes
+ *                                     chrom_type | 16 for chrY / chrMT, whose columns are called with HAPLOID forced, pecaller.c:955-957)
+ *   *n_cols                           columns made: a position is a column if and only if it lies in an interval, so the sum of the
+ *                                     counts.  A sample's counts are its record's at that position, six zeros where it has none.
+ * Records at positions outside every interval are allowed: they are checked for order and range like the others (PECALL_RC_UNORDERED
+ * as above, nothing staged) and ignored.  The reference byte is made as above.  The intervals are checked on the host before any
+ * kernel runs, because they become addresses: iv_count[k] >= 1, iv_first[k] + iv_count[k] <= span, and
+ * iv_first[k] + iv_count[k] <= iv_first[k + 1] (ascending, disjoint; adjacent is fine).  A violation is a non-zero return with a
+ * message, never PECALL_RC_UNORDERED.  n_iv == 0: 0, *n_cols = 0, nothing staged.  Limits as above.  pecall_dev_sites_gather,
+ * _sites_run / _collect, _sites_base_text and _sites_merge_ms (mark = the marks from the intervals and the records' check) follow a
+ * guided stage unchanged.  pecall_dev_call_records_guided is the one-call form, as pecall_dev_call_records. */
+int pecall_dev_sites_stage_records_guided (pecall_dev * dev, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0,
+                                           uint32_t span, const char *ref_letters, uint32_t ref_len, const uint32_t * iv_first,
+                                           const uint32_t * iv_count, const uint8_t * iv_chrom /* may be NULL */ , uint32_t n_iv, long *n_cols,
+                                           uint32_t * col_slot /* [span], may be NULL */ );
+int pecall_dev_call_records_guided (pecall_dev * dev, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0, uint32_t span,
+                                    const char *ref_letters, uint32_t ref_len, const uint32_t * iv_first, const uint32_t * iv_count,
+                                    const uint8_t * iv_chrom, uint32_t n_iv, long *n_cols, uint32_t * col_slot, int haploid, double threshold,
+                                    double theta, int8_t * call, uint32_t * post_site, double *post_rows, uint64_t post_cap, uint64_t * n_post,
+                                    int8_t * site_type, int32_t * allele_count, int8_t * n_pass, int32_t * denovo);
 /* ---- PECaller: the rows of <outfile>.base.gz made on the device ----
  * What the host otherwise does behind a call: the per-sample text of every column (emit_rows of pecaller_main.c; in the reference
  * the gzprintf loop of pecaller.c:1760-1775).  Valid after pecall_dev_call_sites, _call_sites_sparse, _call_records or

@@ -168,6 +168,8 @@ struct PcmState
   uint8_t *d_marks = nullptr, *d_letters = nullptr, *d_chrom = nullptr;
   unsigned *d_colof = nullptr, *d_colslot = nullptr, *d_bsum = nullptr;
   size_t cap_span = 0;
+  unsigned *d_iv = nullptr;     // the guided form's intervals: first[cap_iv], count[cap_iv], then a byte each
+  size_t cap_iv = 0;
   PcmCtl *d_ctl = nullptr;
   char *h_stage = nullptr;      // page-locked: what comes back (PcmCtl, col_slot), then what goes up (offsets, letters, classes, records that are not pinned)
   size_t h_stage_bytes = 0;
@@ -179,9 +181,9 @@ struct PcmState
 
 static void pcm_free (PcmState & g)
 {
-  pc_free (g.d_recs, g.d_off, g.d_ctl, g.d_bsum, g.d_marks, g.d_letters, g.d_chrom, g.d_colof, g.d_colslot, g.d_gather);
+  pc_free (g.d_recs, g.d_off, g.d_ctl, g.d_bsum, g.d_marks, g.d_letters, g.d_chrom, g.d_colof, g.d_colslot, g.d_gather, g.d_iv);
   pc_host_free (g.h_stage, g.h_gather);
-  g.cap_recs = g.cap_span = g.h_stage_bytes = g.cap_gather = 0;
+  g.cap_recs = g.cap_span = g.h_stage_bytes = g.cap_gather = g.cap_iv = 0;
   for (hipEvent_t & e : g.ev)
     if (e && hipEventDestroy (e) == hipSuccess)
       e = nullptr;
@@ -1400,9 +1402,17 @@ static inline size_t pcm_up64 (size_t x)
   return (x + 63) & ~(size_t) 63;
 }
 
-static int pcm_ensure (pecall_dev * d, size_t total, size_t span_pad, size_t stage_bytes)
+static int pcm_ensure (pecall_dev * d, size_t total, size_t span_pad, size_t stage_bytes, size_t n_iv)
 {
   PcmState & g = d->mg;
+  if (n_iv > g.cap_iv)
+    {
+      pc_free (g.d_iv);
+      g.cap_iv = 0;
+      const size_t cap = pcm_up64 (n_iv + n_iv / 4);
+      PCCHK (d, hipMalloc ((void **) &g.d_iv, cap * 9));
+      g.cap_iv = cap;
+    }
   if (!g.d_bsum)
     {
       for (hipEvent_t & e : g.ev)
@@ -1444,8 +1454,18 @@ static int pcm_ensure (pecall_dev * d, size_t total, size_t span_pad, size_t sta
 // Replaces the host's k-way merge of the pileup streams (find_lowest and the per-column loop, pecaller.c:865-923, 1820-1833) for a
 // range of positions: the samples' records go up as they are, the kernels of pecall_merge.hip.h make the columns.  The host waits
 // twice: for the number of columns (the column arrays are sized by it) and for the end.
-extern "C" int pecall_dev_sites_stage_records (pecall_dev * d, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0, uint32_t span,
-                                               const char *ref_letters, uint32_t ref_len, const uint8_t * chrom_by_slot, long *n_cols, uint32_t * col_slot)
+//
+// The guided form (gd: the intervals; the guide-file loop, pecaller.c:941-1039): the marks come from the intervals, the records are only
+// checked, and the slots' chromosome bytes are made on the device.  Everything behind the marks is the same code.
+struct PcmGuide
+{
+  const uint32_t *first, *count;
+  const uint8_t *chrom;         // may be nullptr: 0
+  uint32_t n;
+};
+
+static int pcm_stage_impl (pecall_dev * d, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0, uint32_t span, const char *ref_letters,
+                           uint32_t ref_len, const uint8_t * chrom_by_slot, const PcmGuide * gd, long *n_cols, uint32_t * col_slot)
 {
   PCCHK (d, hipSetDevice (d->device));
   if (n_cols)
@@ -1456,6 +1476,23 @@ extern "C" int pecall_dev_sites_stage_records (pecall_dev * d, const void *const
     return pc_fail (d, "stage_records: indiv %d (1..%d), span %u (1..%u)", indiv, PCS_MAXN, span, PCM_MAX_SPAN);
   if (ref_len > span || (ref_len && !ref_letters))
     return pc_fail (d, "stage_records: %u reference letters for a range of %u positions", ref_len, span);
+  if (gd)
+    {
+      // the intervals become addresses on the device: none empty, all inside the span, ascending and disjoint
+      if (gd->n && (!gd->first || !gd->count))
+        return pc_fail (d, "stage_records_guided: %u intervals and no arrays", gd->n);
+      if (gd->n > span)
+        return pc_fail (d, "stage_records_guided: %u intervals in a range of %u positions", gd->n, span);
+      unsigned long long next = 0;
+      for (uint32_t k = 0; k < gd->n; k++)
+        {
+          const unsigned long long f = gd->first[k], c = gd->count[k];
+          if (c < 1 || f + c > span || f < next)
+            return pc_fail (d, "stage_records_guided: interval %u (slots %llu .. %llu of %u) is empty, leaves the range or does not lie beyond its predecessor",
+                            k, f, f + c, span);
+          next = f + c;
+        }
+    }
   // (a stream of more than span records has a record out of order or out of range among its first span + 1: those go up)
   unsigned long long off[PCS_MAXN + 1];
   size_t staged_bytes = 0;
@@ -1471,14 +1508,15 @@ extern "C" int pecall_dev_sites_stage_records (pecall_dev * d, const void *const
     }
   d->staged_sites = d->result_sites = 0;
   const size_t total = (size_t) off[indiv];
-  if (total == 0)
+  if (gd ? gd->n == 0 : total == 0)
     return 0;
+  const size_t n_iv = gd ? gd->n : 0;
   const size_t span_pad = ((size_t) span + PCM_SCAN_TILE - 1) / PCM_SCAN_TILE * PCM_SCAN_TILE;
   const unsigned nb = (unsigned) (span_pad / PCM_SCAN_TILE);
-  // staging: [PcmCtl][col_slot span][offsets][letters][classes][records of ranges that are not pinned]
+  // staging: [PcmCtl][col_slot span][offsets][letters][classes, or the guided form's intervals][records of ranges that are not pinned]
   const size_t at_slot = 64, at_off = at_slot + pcm_up64 ((size_t) span * 4), at_let = at_off + pcm_up64 (sizeof off), at_chr = at_let + pcm_up64 (span),
-    at_rec = at_chr + pcm_up64 (span), need = at_rec + staged_bytes;
-  PCTRY (pcm_ensure (d, total, span_pad, need));
+    at_rec = at_chr + (gd ? pcm_up64 (n_iv * 9) : pcm_up64 (span)), need = at_rec + staged_bytes;
+  PCTRY (pcm_ensure (d, total, span_pad, need, n_iv));
   char *st = d->mg.h_stage;
   memcpy (st + at_off, off, sizeof (unsigned long long) * (size_t) (indiv + 1));
   PCCHK (d, hipMemcpyAsync (d->mg.d_off, st + at_off, sizeof (unsigned long long) * (size_t) (indiv + 1), hipMemcpyHostToDevice, d->stream));
@@ -1487,7 +1525,21 @@ extern "C" int pecall_dev_sites_stage_records (pecall_dev * d, const void *const
       memcpy (st + at_let, ref_letters, ref_len);
       PCCHK (d, hipMemcpyAsync (d->mg.d_letters, st + at_let, ref_len, hipMemcpyHostToDevice, d->stream));
     }
-  if (chrom_by_slot)
+  if (gd)
+    {
+      // on the device: first[cap_iv], count[cap_iv], then the bytes
+      const size_t cap = d->mg.cap_iv;
+      char *iv = st + at_chr;
+      memcpy (iv, gd->first, n_iv * 4);
+      memcpy (iv + n_iv * 4, gd->count, n_iv * 4);
+      if (gd->chrom)
+        memcpy (iv + n_iv * 8, gd->chrom, n_iv);
+      PCCHK (d, hipMemcpyAsync (d->mg.d_iv, iv, n_iv * 4, hipMemcpyHostToDevice, d->stream));
+      PCCHK (d, hipMemcpyAsync (d->mg.d_iv + cap, iv + n_iv * 4, n_iv * 4, hipMemcpyHostToDevice, d->stream));
+      if (gd->chrom)
+        PCCHK (d, hipMemcpyAsync (d->mg.d_iv + 2 * cap, iv + n_iv * 8, n_iv, hipMemcpyHostToDevice, d->stream));
+    }
+  else if (chrom_by_slot)
     {
       memcpy (st + at_chr, chrom_by_slot, span);
       PCCHK (d, hipMemcpyAsync (d->mg.d_chrom, st + at_chr, span, hipMemcpyHostToDevice, d->stream));
@@ -1509,7 +1561,8 @@ extern "C" int pecall_dev_sites_stage_records (pecall_dev * d, const void *const
         PCCHK (d, hipMemcpyAsync (d->mg.d_recs + off[i], src, bytes, hipMemcpyHostToDevice, d->stream));
       }
   }
-  PCCHK (d, hipMemsetAsync (d->mg.d_marks, 0, span_pad, d->stream));
+  if (!gd)
+    PCCHK (d, hipMemsetAsync (d->mg.d_marks, 0, span_pad, d->stream));
   PCCHK (d, hipMemsetAsync (&d->mg.d_ctl->bad, 0xff, sizeof (unsigned long long), d->stream));
   PCCHK (d, hipMemsetAsync (&d->mg.d_ctl->n_cols, 0, 2 * sizeof (unsigned), d->stream));
   // ---- stage 1: the marks; stage 2's first half: the number of columns
@@ -1519,8 +1572,16 @@ extern "C" int pecall_dev_sites_stage_records (pecall_dev * d, const void *const
       most = off[i + 1] - off[i];
   const unsigned gx = (unsigned) ((most + PCM_BLOCK - 1) / PCM_BLOCK < 1024 ? (most + PCM_BLOCK - 1) / PCM_BLOCK : 1024);
   PCCHK (d, hipEventRecord (d->mg.ev[0], d->stream));
-  hipLaunchKernelGGL (pcm_mark_kernel, dim3 (gx, (unsigned) indiv), dim3 (PCM_BLOCK), 0, d->stream, (const uint4 *) d->mg.d_recs, (const unsigned long long *) d->mg.d_off, p0, span,
-                      d->mg.d_marks, d->mg.d_ctl);
+  if (gd)
+    {
+      const unsigned n16 = (unsigned) (span_pad / 16);
+      const unsigned *iv = d->mg.d_iv;
+      hipLaunchKernelGGL (pcm_guide_marks_kernel, dim3 ((n16 + PCM_BLOCK - 1) / PCM_BLOCK), dim3 (PCM_BLOCK), 0, d->stream, iv, iv + d->mg.cap_iv,
+                          gd->chrom ? (const uint8_t *) (iv + 2 * d->mg.cap_iv) : (const uint8_t *) nullptr, gd->n, n16, (uint4 *) d->mg.d_marks, (uint4 *) d->mg.d_chrom);
+    }
+  if (gx)                       // (the guided form may come without any record)
+    hipLaunchKernelGGL (pcm_mark_kernel, dim3 (gx, (unsigned) indiv), dim3 (PCM_BLOCK), 0, d->stream, (const uint4 *) d->mg.d_recs, (const unsigned long long *) d->mg.d_off, p0,
+                        span, gd ? (uint8_t *) nullptr : d->mg.d_marks, d->mg.d_ctl);
   PCCHK (d, hipEventRecord (d->mg.ev[1], d->stream));
   hipLaunchKernelGGL (pcm_scan_reduce_kernel, dim3 (nb), dim3 (PCM_BLOCK), 0, d->stream, (const uint4 *) d->mg.d_marks, d->mg.d_bsum);
   hipLaunchKernelGGL (pcm_scan_top_kernel, dim3 (1), dim3 (PCM_MAX_SCAN_BLOCKS), 0, d->stream, d->mg.d_bsum, nb, d->mg.d_ctl);
@@ -1544,7 +1605,7 @@ extern "C" int pecall_dev_sites_stage_records (pecall_dev * d, const void *const
   // ---- stage 2's second half: the slots' columns; stage 3: the columns' reads
   PCCHK (d, hipEventRecord (d->mg.ev[3], d->stream));
   hipLaunchKernelGGL (pcm_scan_apply_kernel, dim3 (nb), dim3 (PCM_BLOCK), 0, d->stream, (const uint4 *) d->mg.d_marks, (const unsigned *) d->mg.d_bsum, span,
-                      (const uint8_t *) d->mg.d_letters, ref_len, chrom_by_slot ? (const uint8_t *) d->mg.d_chrom : (const uint8_t *) nullptr, d->mg.d_colof, d->mg.d_colslot,
+                      (const uint8_t *) d->mg.d_letters, ref_len, gd || chrom_by_slot ? (const uint8_t *) d->mg.d_chrom : (const uint8_t *) nullptr, d->mg.d_colof, d->mg.d_colslot,
                       d->cols.d_dom, d->cols.d_chromy);
   PCCHK (d, hipEventRecord (d->mg.ev[4], d->stream));
   const int S = pcm_tile_slots (indiv);
@@ -1569,6 +1630,20 @@ extern "C" int pecall_dev_sites_stage_records (pecall_dev * d, const void *const
   d->staged_indiv = indiv;
   *n_cols = n;
   return 0;
+}
+
+extern "C" int pecall_dev_sites_stage_records (pecall_dev * d, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0, uint32_t span,
+                                               const char *ref_letters, uint32_t ref_len, const uint8_t * chrom_by_slot, long *n_cols, uint32_t * col_slot)
+{
+  return pcm_stage_impl (d, recs, n_recs, indiv, p0, span, ref_letters, ref_len, chrom_by_slot, nullptr, n_cols, col_slot);
+}
+
+extern "C" int pecall_dev_sites_stage_records_guided (pecall_dev * d, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0, uint32_t span,
+                                                      const char *ref_letters, uint32_t ref_len, const uint32_t * iv_first, const uint32_t * iv_count,
+                                                      const uint8_t * iv_chrom, uint32_t n_iv, long *n_cols, uint32_t * col_slot)
+{
+  const PcmGuide gd = { iv_first, iv_count, iv_chrom, n_iv };
+  return pcm_stage_impl (d, recs, n_recs, indiv, p0, span, ref_letters, ref_len, nullptr, &gd, n_cols, col_slot);
 }
 
 extern "C" int pecall_dev_sites_merge_ms (pecall_dev * d, float *ms3)
@@ -1865,6 +1940,14 @@ extern "C" int pecall_dev_sites_base_text (pecall_dev * d, const char *names, co
   return 0;
 }
 
+// the chunk pipeline of pecall_dev_call_sites_sparse over the columns a stage of records left on the device
+static int pcs_call_resident (pecall_dev * d, int8_t * call, uint32_t * post_site, double *post_rows, uint64_t post_cap, uint64_t * n_post, int8_t * site_type,
+                              int32_t * allele_count, int8_t * n_pass, int32_t * denovo, long n, int indiv, int haploid, double threshold, double theta)
+{
+  return pcs_call_sites_impl (d, { nullptr, nullptr, nullptr, call, nullptr, site_type, allele_count, n_pass, denovo, true, post_site, post_rows, post_cap, n_post, true },
+                              n, indiv, haploid, threshold, theta);
+}
+
 extern "C" int pecall_dev_call_records (pecall_dev * d, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0, uint32_t span, const char *ref_letters,
                                         uint32_t ref_len, const uint8_t * chrom_by_slot, long *n_cols, uint32_t * col_slot, int haploid, double threshold, double theta,
                                         int8_t * call, uint32_t * post_site, double *post_rows, uint64_t post_cap, uint64_t * n_post, int8_t * site_type,
@@ -1872,11 +1955,25 @@ extern "C" int pecall_dev_call_records (pecall_dev * d, const void *const *recs,
 {
   if (n_post)
     *n_post = 0;
-  const int rc = pecall_dev_sites_stage_records (d, recs, n_recs, indiv, p0, span, ref_letters, ref_len, chrom_by_slot, n_cols, col_slot);
+  const int rc = pcm_stage_impl (d, recs, n_recs, indiv, p0, span, ref_letters, ref_len, chrom_by_slot, nullptr, n_cols, col_slot);
   if (rc || *n_cols == 0)
     return rc;
-  return pcs_call_sites_impl (d, { nullptr, nullptr, nullptr, call, nullptr, site_type, allele_count, n_pass, denovo, true, post_site, post_rows, post_cap, n_post, true },
-                              *n_cols, indiv, haploid, threshold, theta);
+  return pcs_call_resident (d, call, post_site, post_rows, post_cap, n_post, site_type, allele_count, n_pass, denovo, *n_cols, indiv, haploid, threshold, theta);
+}
+
+extern "C" int pecall_dev_call_records_guided (pecall_dev * d, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0, uint32_t span,
+                                               const char *ref_letters, uint32_t ref_len, const uint32_t * iv_first, const uint32_t * iv_count, const uint8_t * iv_chrom,
+                                               uint32_t n_iv, long *n_cols, uint32_t * col_slot, int haploid, double threshold, double theta, int8_t * call,
+                                               uint32_t * post_site, double *post_rows, uint64_t post_cap, uint64_t * n_post, int8_t * site_type, int32_t * allele_count,
+                                               int8_t * n_pass, int32_t * denovo)
+{
+  if (n_post)
+    *n_post = 0;
+  const PcmGuide gd = { iv_first, iv_count, iv_chrom, n_iv };
+  const int rc = pcm_stage_impl (d, recs, n_recs, indiv, p0, span, ref_letters, ref_len, nullptr, &gd, n_cols, col_slot);
+  if (rc || *n_cols == 0)
+    return rc;
+  return pcs_call_resident (d, call, post_site, post_rows, post_cap, n_post, site_type, allele_count, n_pass, denovo, *n_cols, indiv, haploid, threshold, theta);
 }
 
 extern "C" int pecall_dev_call_sites (pecall_dev * d, const uint16_t * reads, const uint8_t * ref_base, const uint8_t * chrom_type, long n_sites,

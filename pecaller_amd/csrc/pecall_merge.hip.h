@@ -14,6 +14,14 @@
 //                          it, and the marked slots' rows written to the column array as whole rows
 // A record's position becomes an address only after the check of stage 1 has passed for it: stage 3 takes a record only if its
 // position lies inside the workgroup's own run, and does nothing at all when stage 1 found a bad record.
+//
+// The guided form (pecall_dev_sites_stage_records_guided; the guide-file loop of the reference, pecaller.c:941-1039): the columns are
+// the positions of a list of intervals, covered or not, not the records' positions.  Only stage 1 differs:
+//   1a. pcm_guide_marks_kernel   a thread per 16 slots of the padded span: the marks and the chromosome bytes of its slots from the
+//                                interval list, a 16-byte store each (the zeros too: no memset of the marks)
+//   1b. pcm_mark_kernel          with marks = nullptr: every record checked as before, no mark stored
+// Stages 2 and 3 run unchanged on those marks.  A record at a slot outside every interval lands in the tile of stage 3 and stays there
+// (its slot has no column); a run whose marked slots hold no record is written as the zeros it was cleared to.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,7 +69,7 @@ __device__ __forceinline__ unsigned pcm_ref_code (unsigned char c)
     }
 }
 
-// grid (x, indiv): the records of sample blockIdx.y, a thread each
+// grid (x, indiv): the records of sample blockIdx.y, a thread each; marks = nullptr: the check alone (the guided form)
 __global__ void __launch_bounds__ (PCM_BLOCK) pcm_mark_kernel (const uint4 * __restrict__ recs, const unsigned long long *__restrict__ rec_off, unsigned p0, unsigned span,
                                                                uint8_t * __restrict__ marks, PcmCtl * __restrict__ ctl)
 {
@@ -75,10 +83,69 @@ __global__ void __launch_bounds__ (PCM_BLOCK) pcm_mark_kernel (const uint4 * __r
       if (ok && j > 0)
         ok = p > pos[4 * (j - 1)];
       if (ok)
-        marks[p - p0] = 1;      // (every writer of a slot stores the same byte)
+        {
+          if (marks)
+            marks[p - p0] = 1;  // (every writer of a slot stores the same byte)
+        }
       else
         atomicMin (&ctl->bad, ((unsigned long long) i << PCM_BAD_SHIFT) | j);
     }
+}
+
+// The guided form's marks.  Intervals k = 0 .. n_iv - 1 take the slots [iv_first[k], iv_first[k] + iv_count[k]): ascending, disjoint,
+// inside the span and none empty (checked on the host: they become addresses).  A thread per 16 slots of the padded span: it finds the
+// first interval that ends beyond its first slot by bisection (22 steps at most; the list is a few MB at most and lies in L2), then walks
+// its 16 slots and the list together -- an interval holds a slot at least, so one step along the list per slot is enough -- and
+// composes the 16 mark bytes and the 16 chromosome bytes in registers.  Two 16-byte stores a thread, consecutive along the wave,
+// whatever the intervals' lengths; slots outside every interval, the padding among them, get zeros.  iv_chrom: nullptr = 0.
+__global__ void __launch_bounds__ (PCM_BLOCK) pcm_guide_marks_kernel (const unsigned *__restrict__ iv_first, const unsigned *__restrict__ iv_count,
+                                                                      const uint8_t * __restrict__ iv_chrom, unsigned n_iv, unsigned n16, uint4 * __restrict__ marks16,
+                                                                      uint4 * __restrict__ chrom16)
+{
+  const unsigned g = blockIdx.x * PCM_BLOCK + threadIdx.x;
+  if (g >= n16)
+    return;
+  const unsigned s0 = g * 16u;
+  unsigned lo = 0, hi = n_iv;
+  while (lo < hi)
+    {
+      const unsigned mid = (lo + hi) >> 1;
+      if (iv_first[mid] + iv_count[mid] <= s0)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+  unsigned k = lo, f = ~0u, e = ~0u, c = 0;     // the interval at hand: [f, e), its byte
+  if (k < n_iv)
+    {
+      f = iv_first[k];
+      e = f + iv_count[k];
+      c = iv_chrom ? iv_chrom[k] : 0u;
+    }
+  unsigned m[4] = { 0u, 0u, 0u, 0u }, y[4] = { 0u, 0u, 0u, 0u };
+#pragma unroll
+  for (int j = 0; j < 16; j++)
+    {
+      const unsigned slot = s0 + (unsigned) j;
+      if (slot >= e)
+        {
+          k++;
+          f = e = ~0u;
+          if (k < n_iv)
+            {
+              f = iv_first[k];
+              e = f + iv_count[k];
+              c = iv_chrom ? iv_chrom[k] : 0u;
+            }
+        }
+      if (slot >= f && slot < e)
+        {
+          m[j >> 2] |= 1u << (8 * (j & 3));
+          y[j >> 2] |= c << (8 * (j & 3));
+        }
+    }
+  marks16[g] = make_uint4 (m[0], m[1], m[2], m[3]);
+  chrom16[g] = make_uint4 (y[0], y[1], y[2], y[3]);
 }
 
 // the marks of 16 slots as four words of 0 / 1 bytes: how many are set
@@ -182,8 +249,11 @@ __global__ void __launch_bounds__ (PCM_BLOCK) pcm_tile_kernel (const uint4 * __r
       marked = slot < span && marks[slot];
       col_of[t] = marked ? col_of_slot[slot] : ~0u;
     }
+  // The early exit is on the marks, not on records.  Without a guide a marked slot has a record and the two are one; in the guided
+  // form a run without marked slots has no column to write, whatever records lie in it, and a run with marked slots goes on even when
+  // no sample has a record in it: its rows are the zeros below, and they are written.
   if (!__syncthreads_or (marked))
-    return;                     // (no record in the run)
+    return;                     // (no column in the run)
   {
     const unsigned n16 = (unsigned) S * row_words / 4u; // (S is a multiple of 8: whole 16-byte pieces)
     const uint4 z = make_uint4 (0u, 0u, 0u, 0u);

@@ -16,6 +16,8 @@
  *
  * With a BED guide file (the last argument, pecaller.c:925-1068) every position of the listed intervals is called, covered
  * or not, and columns on chrY / chrMT are called with HAPLOID forced (955-957).
+ * PECALLER_DEVICE_GUIDE=1 (off by default): runs of BED lines go to the device as ranges of intervals and the columns are made
+ * there (pecall_dev_call_records_guided; fill_guide_range below) instead of one position at a time.
  *
  * Not supported (an error, not a silent difference): more than 512 samples (up to 64 is the device caller's fast case).  `no_threads` - 1 threads (as many as the host has CPUs, at most 128) walk the pileup streams, format the rows and deflate <outfile>.base.gz.
  */
@@ -37,6 +39,8 @@
 /* (weak: the program links against a library without this entry too -- an older build, or the tests' host-only stand-in -- and
    PECALLER_DEVICE_ROWS=1 then ends the run with a message) */
 extern __typeof__ (pecall_dev_sites_base_text) pecall_dev_sites_base_text __attribute__ ((weak));
+/* (weak for the same reason: PECALLER_DEVICE_GUIDE=1 ends the run with a message where the library lacks the entry) */
+extern __typeof__ (pecall_dev_call_records_guided) pecall_dev_call_records_guided __attribute__ ((weak));
 
 #define MAX_SAMPLES 512         /* PCS_MAXN of the device caller */
 #define NA 6
@@ -139,6 +143,14 @@ typedef struct
   uint8_t *chrom_slot;          /* [T]: chromosome class of position p0 + slot */
   uint32_t *col_slot, *vrow, *vlist;    /* [T] */
   unsigned int p0;
+  int from_records;             /* this tile's columns are made on the device from `recs` (every tile under PECALLER_DEVICE_MERGE=1) */
+  /* PECALLER_DEVICE_GUIDE=1 (NULL otherwise): a range of guide intervals for pecall_dev_call_records_guided -- interval k holds the
+     slots [iv_first[k], iv_first[k] + iv_count[k]) of the range [p0, p0 + span) on contig iv_which[k]; `recs` holds the records at
+     those slots only.  n_iv = 0: not such a tile (a line left to the per-position path fills `reads` as without the switch) */
+  uint32_t *iv_first, *iv_count;        /* [T] */
+  uint8_t *iv_chrom;
+  int *iv_which;
+  uint32_t n_iv, span;
   /* PECALLER_DEVICE_ROWS=1 (dtext NULL otherwise): the rows of <outfile>.base.gz as the device made them (pecall_dev_sites_base_text)
      -- those of the columns whose posteriors are all 1 -- and the holes: the host's row of column hole_site[k] (= post_site[k])
      belongs at byte hole_at[k] of dtext.  The rows stage notes where its row of hole k lies (hole_off: in the formatting thread's
@@ -273,7 +285,7 @@ emit_rows (const tile_t * t, long s0, long s1, int indiv, char **contig_names, s
       for (int i = 0; i < indiv; i++)
         {
           sb->n += (size_t) sprintf (sb_room (sb, 64), "\t%c\t%g", GEN[call[i]], p ? p[i] : 1.0);
-          const uint16_t *r = t->reads + ((size_t) (t->vrow ? t->vrow[s] : (uint32_t) s) * indiv + i) * NA;
+          const uint16_t *r = t->reads + ((size_t) (t->from_records ? t->vrow[s] : (uint32_t) s) * indiv + i) * NA;
           for (int a = 0; a < NA; a++)
             pb->n += (size_t) sprintf (sb_room (pb, 16), "\t%d", (int) r[a]);
         }
@@ -357,6 +369,14 @@ struct run_s
      (find_lowest, pecaller.c:865-923, 1820-1833), whatever order the records come in; otherwise by the parallel walk.  device_merge
      (PECALLER_DEVICE_MERGE=1): a range's columns are made on the device from the streams' records; not with a guide file or serial_merge */
   int serial_merge, device_merge;
+  /* device_guide (PECALLER_DEVICE_GUIDE=1, with a guide file, not under serial_merge): runs of BED lines go to the device as ranges of
+     intervals (fill_guide_range).  gline: BED lines read so far; gline_judged / gline_host: the line at hand has been looked at, and
+     is left to the per-position path; gline_taken: the last line counted in dg_ivs; gbad: the line names no contig of the .sdx (the
+     run ends with the reference's message when the walk gets to it); guide_done: the file has no further line */
+  int device_guide, gline_host, gbad, guide_done;
+  long gline, gline_judged, gline_taken;
+  char gbad_name[256];
+  long dg_cols, dg_ivs, dg_ranges;
   /* device_rows (PECALLER_DEVICE_ROWS=1): the rows of <outfile>.base.gz whose posteriors are all 1 are made on the device behind each
      tile's call (pecall_dev_sites_base_text); names / name_off: the contig names as that call takes them */
   int device_rows;
@@ -551,10 +571,17 @@ chrom_class (const ref_t * g, int which, int guide)
         walk_streams is that walk for one thread's streams, in two forms chosen at compile time; both keep the stream's own part (the
         statistics of <outfile>.dist, the pending record, the end of the stream, the check of the order).  to_records = 0: the counters
         go to the stream's plane, zeros between them, and their slots are marked.  to_records = 1 (PECALLER_DEVICE_MERGE=1): the records
-        are appended to the sample's buffer of the tile as they are; the columns are made on the device (pecall_dev_call_records). */
+        are appended to the sample's buffer of the tile as they are; the columns are made on the device (pecall_dev_call_records).
+        to_records = 2 (PECALLER_DEVICE_GUIDE=1): the same over a range of guide intervals (the tile's iv_first / iv_count), from the
+        first guided position p0 to the last one, p1 - 1.  The reference's loop (pecaller.c:975-1029) is the specification: records in
+        front of a guided position are read past without a word, so only the records at guided positions are appended and feed the
+        statistics; those in the gaps between the range's intervals are passed over (still checked for their order); those behind p1
+        stay pending, for the next range's leading skip.  The positions seen (base_count) are the range's columns for every sample,
+        open or not: fill_guide_range adds them, behind the cut at the end of the streams. */
 static inline __attribute__ ((always_inline)) void
-walk_streams (merge_ctx * c, const int to_records)
+walk_streams (merge_ctx * c, const int mode)
 {
+  const int to_records = mode != 0, guided = mode == 2;
   run_t *r = c->r;
   const size_t tile = r->tile;
   const unsigned int p0 = c->p0;
@@ -575,13 +602,17 @@ walk_streams (merge_ctx * c, const int to_records)
       char *out = to_records ? c->t->recs + (size_t) i * tile * 16 : NULL;
       size_t done = 0;          /* slots of the range passed so far: the next record lies at p0 + done or behind */
       const int live = s->cur != 0;
-      if (!to_records && c->guide)
+      if (c->guide)
         {
           /* records in front of the interval are passed over (pecaller.c:975-976); every position of the stretch counts as seen */
           while (s->cur != 0 && s->cur < p0)
             advance (s);
-          s->base_count += (unsigned int) (p1 - p0);
+          if (!to_records)
+            s->base_count += (unsigned int) (p1 - p0);
         }
+      const uint32_t *iv_first = guided ? c->t->iv_first : NULL, *iv_count = guided ? c->t->iv_count : NULL;
+      const uint32_t n_iv = guided ? c->t->n_iv : 0;
+      uint32_t iv = 0;          /* guided: the first interval that ends behind the slot at hand */
       /* The records of the range.  The pending one first (s->cur / s->data); then straight out of the inflater's block as long as whole
          records lie in it -- 64 of these loops are the merge's time: one load of the position, the six counters copied as 8 + 4
          bytes, their sum for the stream's statistics.  (The coverage total is a sum of integers: it is kept in an integer and added
@@ -604,27 +635,37 @@ walk_streams (merge_ctx * c, const int to_records)
                   return;
                 }
               const size_t slot = (size_t) (pos - p0);
-              uint16_t cnt[NA];
-              memcpy (cnt, rec ? (const void *) (rec + 4) : (const void *) s->data, sizeof cnt);
-              if (to_records)
+              int take = 1;
+              if (guided)
                 {
-                  char *dst = out + n_rec * 16;
-                  memcpy (dst, &pos, sizeof pos);
-                  memcpy (dst + 4, cnt, sizeof cnt);
+                  while (iv < n_iv && (size_t) iv_first[iv] + iv_count[iv] <= slot)
+                    iv++;
+                  take = iv < n_iv && slot >= iv_first[iv];
                 }
-              else
+              if (take)
                 {
-                  if (slot != done)
-                    memset (plane + done * NA, 0, (slot - done) * NA * sizeof (uint16_t));
-                  memcpy (plane + slot * NA, cnt, sizeof cnt);
-                  mark[slot] = 1;
+                  uint16_t cnt[NA];
+                  memcpy (cnt, rec ? (const void *) (rec + 4) : (const void *) s->data, sizeof cnt);
+                  if (to_records)
+                    {
+                      char *dst = out + n_rec * 16;
+                      memcpy (dst, &pos, sizeof pos);
+                      memcpy (dst + 4, cnt, sizeof cnt);
+                    }
+                  else
+                    {
+                      if (slot != done)
+                        memset (plane + done * NA, 0, (slot - done) * NA * sizeof (uint16_t));
+                      memcpy (plane + slot * NA, cnt, sizeof cnt);
+                      mark[slot] = 1;
+                    }
+                  const unsigned int cov = (unsigned int) cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[4] + cnt[5];
+                  cov_sum += cov;
+                  if (cov > cov_max)
+                    cov_max = cov;
+                  s->counts[cov < MAX_DIST - 1 ? cov : MAX_DIST - 1]++;
+                  n_rec++;
                 }
-              const unsigned int cov = (unsigned int) cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[4] + cnt[5];
-              cov_sum += cov;
-              if (cov > cov_max)
-                cov_max = cov;
-              s->counts[cov < MAX_DIST - 1 ? cov : MAX_DIST - 1]++;
-              n_rec++;
               done = slot + 1;
               /* the next record, if it lies whole in the block at hand and belongs to the range */
               if (z->pos + 16 > z->cur_len)
@@ -639,11 +680,24 @@ walk_streams (merge_ctx * c, const int to_records)
         }
       s->mean += (double) cov_sum;
       s->max_coverage = cov_max;
-      if (to_records || !c->guide)
+      if (!c->guide)
         s->base_count += (unsigned int) n_rec;
       if (to_records)
         {
           c->t->n_recs[i] = n_rec;
+          /* guided: the stream ended inside this range, at the column of the first guided position at or behind its last record
+             (pecaller.c:975-1023: read past in front of that position, or taken at it) -- all its records lying in front of the range,
+             at the range's first position.  There is such a position: the record lies in front of p1, the last one's successor */
+          if (guided && live && s->cur == 0)
+            {
+              const size_t at = done ? done - 1 : 0;
+              uint32_t k = 0;
+              while (k + 1 < n_iv && (size_t) iv_first[k] + iv_count[k] <= at)
+                k++;
+              const long col_at = at > iv_first[k] ? (long) at : (long) iv_first[k];
+              if (col_at > c->end_slot)
+                c->end_slot = col_at;
+            }
           continue;
         }
       memset (plane + done * NA, 0, (tile - done) * NA * sizeof (uint16_t));
@@ -669,6 +723,13 @@ static void *
 merge_streams_dev (void *arg)
 {
   walk_streams ((merge_ctx *) arg, 1);
+  return NULL;
+}
+
+static void *
+merge_streams_guided (void *arg)
+{
+  walk_streams ((merge_ctx *) arg, 2);
   return NULL;
 }
 
@@ -766,6 +827,8 @@ pool_get (tile_pool * p)
   tile_t t = p->free_tile[--p->n_free];
   pthread_mutex_unlock (&p->mu);
   t.n = 0;
+  t.n_iv = 0;
+  t.from_records = 0;
   return t;
 }
 
@@ -793,7 +856,7 @@ stage_give (stage_t * c, tile_t t)
 static int
 device_call (run_t * r, tile_t * t)
 {
-  if (!r->device_merge)
+  if (!t->from_records)
     return pecall_dev_call_sites_sparse (r->pc, t->reads, t->ref_base, t->chrom, t->n, r->indiv, r->haploid, r->threshold, r->theta, t->call,
                                          t->post_site, t->post_rows, t->post_cap, &t->n_post, t->type, t->ac, NULL, t->denovo);
   const void *ptr[MAX_SAMPLES];
@@ -801,20 +864,29 @@ device_call (run_t * r, tile_t * t)
     ptr[i] = t->recs + (size_t) i * r->tile * 16;
   const size_t left = (size_t) t->p0 < r->ref.gsize ? r->ref.gsize - t->p0 : 0;
   t->n = 0;
+  if (t->n_iv)
+    return pecall_dev_call_records_guided (r->pc, ptr, t->n_recs, r->indiv, t->p0, t->span, r->ref.genome + (left ? t->p0 : 0), (uint32_t) (left < t->span ? left : t->span),
+                                           t->iv_first, t->iv_count, t->iv_chrom, t->n_iv, &t->n, t->col_slot, r->haploid, r->threshold, r->theta, t->call, t->post_site,
+                                           t->post_rows, t->post_cap, &t->n_post, t->type, t->ac, NULL, t->denovo);
   return pecall_dev_call_records (r->pc, ptr, t->n_recs, r->indiv, t->p0, (uint32_t) r->tile, r->ref.genome + (left ? t->p0 : 0),
                                   (uint32_t) (left < r->tile ? left : r->tile), t->chrom_slot, &t->n, t->col_slot, r->haploid, r->threshold, r->theta,
                                   t->call, t->post_site, t->post_rows, t->post_cap, &t->n_post, t->type, t->ac, NULL, t->denovo);
 }
 
 /* behind pecall_dev_call_records: the columns' heads from their slots (what merge_columns fills on the host path; an illegal
-   reference letter ends the run here as it does there), and the variant columns' reads for the rows of <outfile>.piles.gz */
+   reference letter ends the run here as it does there), and the variant columns' reads for the rows of <outfile>.piles.gz.
+   Behind pecall_dev_call_records_guided the contig is the interval's (the BED line's, pecaller.c:964-965), found by a walk along
+   the range's intervals beside the columns. */
 static void
 device_merge_columns (run_t * r, tile_t * t)
 {
   long nv = 0;
+  uint32_t k = 0;
   for (long col = 0; col < t->n; col++)
     {
-      column_header (&r->ref, t, col, t->p0 + t->col_slot[col], -1);
+      while (k + 1 < t->n_iv && t->col_slot[col] >= t->iv_first[k] + t->iv_count[k])
+        k++;
+      column_header (&r->ref, t, col, t->p0 + t->col_slot[col], t->n_iv ? t->iv_which[k] : -1);
       if (t->type[col] > 0)
         {
           t->vrow[col] = (uint32_t) nv;
@@ -823,6 +895,12 @@ device_merge_columns (run_t * r, tile_t * t)
     }
   if (nv && pecall_dev_sites_gather (r->pc, t->vlist, (uint64_t) nv, t->reads, NULL, NULL))
     die ("\n pecaller_hip: %s", pecall_dev_last_error (r->pc));
+  if (t->n_iv)
+    {
+      r->dg_cols += t->n;
+      r->dg_ranges++;
+      return;
+    }
   r->dev_cols += t->n;
   r->dev_ranges++;
 }
@@ -897,7 +975,7 @@ call_tile (run_t * r, tile_t * t)
         die ("\n pecaller_hip: out of memory for %s", "the list of posteriors");
       rc = device_call (r, t);
     }
-  if (rc == PECALL_RC_UNORDERED && r->device_merge)
+  if (rc == PECALL_RC_UNORDERED && t->from_records)
     {
       /* (the walk's own check comes first: this is the library's word for the same thing) */
       r->unordered = 1;
@@ -906,7 +984,7 @@ call_tile (run_t * r, tile_t * t)
     }
   else if (rc)
     die ("\n pecaller_hip: %s", pecall_dev_last_error (r->pc));
-  else if (r->device_merge)
+  else if (t->from_records)
     device_merge_columns (r, t);
   if (r->device_rows)
     device_text (r, t);
@@ -989,7 +1067,16 @@ tile_alloc (run_t * r, tile_t * t)
 {
   const size_t T = r->tile, indiv = (size_t) r->indiv;
   memset (t, 0, sizeof *t);
-  if (r->device_merge)
+  if (r->device_guide)
+    {
+      t->iv_first = (uint32_t *) malloc (T * sizeof (uint32_t));
+      t->iv_count = (uint32_t *) malloc (T * sizeof (uint32_t));
+      t->iv_chrom = (uint8_t *) malloc (T);
+      t->iv_which = (int *) malloc (T * sizeof (int));
+      if (!t->iv_first || !t->iv_count || !t->iv_chrom || !t->iv_which)
+        die ("\n pecaller_hip: out of memory for %s", "a tile's intervals");
+    }
+  if (r->device_merge || r->device_guide)
     {
       t->recs = (char *) malloc (indiv * T * 16);
       t->n_recs = (uint64_t *) calloc (indiv, sizeof (uint64_t));
@@ -1015,9 +1102,11 @@ tile_alloc (run_t * r, tile_t * t)
   t->ac = (int32_t *) malloc (T * NA * sizeof (int32_t));
   if (!t->reads || !t->ref_base || !t->chrom || !t->denovo || !t->ref_char || !t->contig || !t->pos || !t->call || !t->post_site || !t->post_rows || !t->type || !t->ac)
     die ("\n pecaller_hip: out of memory for %s", "a tile");
+  /* (device_guide: a range's records are those at guided positions, a few percent of the buffer on an exome; page-locking the whole
+     buffer costs more at start-up than the library's staged copy of what is in it) */
   if (r->device_merge)
-    tile_pin (r, t, t->recs, (uint64_t) indiv * T * 16);       /* (the columns' arrays do not travel then) */
-  else
+    tile_pin (r, t, t->recs, (uint64_t) indiv * T * 16);
+  if (!r->device_merge)         /* (there the columns' arrays do not travel) */
     {
       tile_pin (r, t, t->reads, (uint64_t) T * indiv * NA * sizeof (uint16_t));
       tile_pin (r, t, t->ref_base, (uint64_t) T);
@@ -1045,7 +1134,7 @@ tile_free (run_t * r, tile_t * t)
   void *rows[] = { t->dtext, t->hole_site, t->hole_len, t->hole_at, t->hole_off, t->hole_pre, (void *) t->hole_src };
   for (size_t k = 0; k < sizeof rows / sizeof rows[0]; k++)
     free (rows[k]);
-  void *all[] = { t->recs, t->n_recs, t->chrom_slot, t->col_slot, t->vrow, t->vlist, t->reads, t->ref_base, t->chrom, t->denovo, t->ref_char, t->contig,
+  void *all[] = { t->iv_first, t->iv_count, t->iv_chrom, t->iv_which, t->recs, t->n_recs, t->chrom_slot, t->col_slot, t->vrow, t->vlist, t->reads, t->ref_base, t->chrom, t->denovo, t->ref_char, t->contig,
     t->pos, t->call, t->post_site, t->post_rows, t->type, t->ac };
   for (size_t k = 0; k < sizeof all / sizeof all[0]; k++)
     free (all[k]);
@@ -1056,6 +1145,7 @@ tile_free (run_t * r, tile_t * t)
 static int
 next_guide_interval (run_t * r, int first)
 {
+  r->gline++;
   const ref_t *g = &r->ref;
   char line[4096];
   line[0] = '\0';
@@ -1071,6 +1161,13 @@ next_guide_interval (run_t * r, int first)
         r->gwhich = i;
         break;
       }
+  if (r->gwhich < 0 && r->device_guide)
+    {
+      /* (the range builder reads a line ahead of the walk: the run ends where the walk gets to this line, fill_tile) */
+      snprintf (r->gbad_name, sizeof r->gbad_name, "%s", tok ? tok : "");
+      r->gbad = 1;
+      return 1;
+    }
   if (r->gwhich < 0)
     {
       printf ("\n For line chrom %s \n", tok ? tok : "");
@@ -1364,6 +1461,9 @@ start_pipeline (run_t * r)
   if ((e = getenv ("PECALLER_POST_CAP")) && atol (e) >= 1)
     r->post_cap = (uint64_t) atol (e);
   r->device_merge = !r->guide_file && !r->serial_merge && (e = getenv ("PECALLER_DEVICE_MERGE")) && atoi (e) == 1;
+  r->device_guide = r->guide_file && !r->serial_merge && (e = getenv ("PECALLER_DEVICE_GUIDE")) && atoi (e) == 1;
+  if (r->device_guide && !pecall_dev_call_records_guided)
+    die ("\n pecaller_hip: PECALLER_DEVICE_GUIDE=1 needs %s, which this library lacks", "pecall_dev_call_records_guided");
   r->device_rows = (e = getenv ("PECALLER_DEVICE_ROWS")) && atoi (e) == 1;
   if (r->device_rows && !pecall_dev_sites_base_text)
     die ("\n pecaller_hip: PECALLER_DEVICE_ROWS=1 needs %s, which this library lacks", "pecall_dev_sites_base_text");
@@ -1522,6 +1622,7 @@ fill_range (run_t * r, tile_t * t)
     {
       chrom_classes (&r->ref, t, p0, r->tile);
       t->p0 = p0;
+      t->from_records = 1;
       t->n = 0;                 /* (known when the device has made the columns: the device thread counts them) */
     }
   else
@@ -1579,13 +1680,126 @@ fill_guide_position (run_t * r, tile_t * t)
   return 0;
 }
 
+/* PECALLER_DEVICE_GUIDE=1: can the range builder take the BED line at hand, from r->lowest on?  Not a line whose end lies in front of
+   its start (the reference still calls the start position), nor one that leaves the genome or begins at position 0 of the .seq (an
+   exhausted stream's pending position is 0 too): such a line goes through the per-position path as without the switch. */
+static int
+guide_line_fits (const run_t * r)
+{
+  return r->lowest >= 1 && r->lowest <= r->gend && (size_t) r->gend < r->ref.gsize && r->lowest >= r->ref.frag_pos[r->gwhich - 1];
+}
+
+/* PECALLER_DEVICE_GUIDE=1: a range of guide intervals, a tile of its own.  The range is a maximal run of consecutive BED lines that
+   ascend, are disjoint and fit from the first guided position on into r->tile positions; a longer line is cut there and goes on in
+   the next range; a line that goes backwards or overlaps begins a new one; a line guide_line_fits refuses ends the range and is left
+   to the per-position path.  The streams are walked from the first to the last guided position (walk_streams, to_records = 2), the
+   columns are made and called on the device (pecall_dev_call_records_guided, the device thread).
+   The reference's loop runs while a stream is open (pecaller.c:952): the column at which the last stream ends is the run's last.  If
+   that happened in this range the intervals are cut behind that column; no record lies behind it. */
+static int
+fill_guide_range (run_t * r, tile_t * t)
+{
+  if (t->n > 0)
+    return 1;                   /* (columns of the per-position path: that tile goes first) */
+  const unsigned int p0 = r->lowest;
+  unsigned long long end = p0;  /* the range so far: [p0, end) */
+  uint32_t n_iv = 0;
+  for (;;)
+    {
+      const unsigned long long first = (unsigned long long) r->lowest - p0;
+      if (first >= r->tile)
+        break;
+      unsigned long long cnt = (unsigned long long) r->gend + 1 - r->lowest;
+      if (first + cnt > r->tile)
+        cnt = r->tile - first;
+      t->iv_first[n_iv] = (uint32_t) first;
+      t->iv_count[n_iv] = (uint32_t) cnt;
+      t->iv_chrom[n_iv] = chrom_class (&r->ref, r->gwhich, 1);
+      t->iv_which[n_iv++] = r->gwhich;
+      end = (unsigned long long) p0 + first + cnt;
+      if (r->gline_taken != r->gline)
+        {
+          r->gline_taken = r->gline;
+          r->dg_ivs++;
+        }
+      if ((unsigned long long) r->lowest + cnt <= r->gend)
+        {
+          r->lowest += (unsigned int) cnt;      /* (cut at the span: the line goes on in the next range) */
+          break;
+        }
+      if (!next_guide_interval (r, 0))
+        {
+          r->guide_done = 1;
+          break;
+        }
+      r->gline_judged = r->gline;
+      r->gline_host = r->gbad || !guide_line_fits (r);
+      if (r->gline_host || (unsigned long long) r->lowest < end)
+        break;
+    }
+  t->n_iv = n_iv;
+  t->p0 = p0;
+  t->span = (uint32_t) (end - p0);
+  t->from_records = 1;
+  t->n = 0;                     /* (known when the device has made the columns: the device thread counts them) */
+  set_range (r, t, p0, end, t->iv_which[0]);
+  run_threads (merge_streams_guided, r);
+  if (r->unordered)
+    {
+      t->n_iv = 0;
+      return abandon (r, t);
+    }
+  r->running = live_streams (r);
+  if (r->running == 0)
+    {
+      long last = 0;
+      for (int k = 0; k < r->MT; k++)
+        if (r->mc[k].end_slot > last)
+          last = r->mc[k].end_slot;
+      while (t->n_iv > 1 && t->iv_first[t->n_iv - 1] > (uint32_t) last)
+        t->n_iv--;
+      t->iv_count[t->n_iv - 1] = (uint32_t) last + 1 - t->iv_first[t->n_iv - 1];
+      t->span = (uint32_t) last + 1;
+    }
+  unsigned int ncols = 0;
+  for (uint32_t k = 0; k < t->n_iv; k++)
+    ncols += t->iv_count[k];
+  /* every sample has seen every column, its stream open or not (pecaller.c:1005, 1028) */
+  for (int i = 0; i < r->indiv; i++)
+    r->sm[i].base_count += ncols;
+  r->tot_bases += ncols;
+  if (r->guide_done)
+    r->running = 0;
+  return 1;
+}
+
 static int
 fill_tile (run_t * r, tile_t * t)
 {
   if (!r->guide_file)
     return (r->serial_merge ? fill_serial_column : fill_range) (r, t);
+  if (r->device_guide)
+    {
+      if (r->gline_judged != r->gline)
+        {
+          r->gline_judged = r->gline;
+          r->gline_host = r->gbad || !guide_line_fits (r);
+        }
+      if (r->gbad)
+        {
+          if (t->n > 0)
+            return 1;           /* (what is in the tile is written first, as the reference's workers would have) */
+          stage_wait_idle (&r->dev_stage);
+          stage_wait_idle (&r->row_stage);
+          printf ("\n For line chrom %s \n", r->gbad_name);
+          exit (1);
+        }
+      if (!r->gline_host)
+        return fill_guide_range (r, t);
+    }
   /* (with the serial merge every guide position goes through the per-column scan, which is the reference's) */
-  if (!r->serial_merge && (unsigned long long) r->gend + 1 - r->lowest >= r->guide_range_min && (size_t) t->n < r->tile)
+  /* (a line whose end lies in front of its start is one position, the start, as in the reference: never a stretch) */
+  if (!r->serial_merge && r->gend >= r->lowest && (unsigned long long) r->gend + 1 - r->lowest >= r->guide_range_min && (size_t) t->n < r->tile)
     return fill_guide_stretch (r, t);
   return fill_guide_position (r, t);
 }
@@ -1701,6 +1915,8 @@ close_outputs (run_t * r)
           r->tot_cols, r->indiv, sec, (double) r->tot_cols / (sec > 0 ? sec : 1) / 1e6, r->sec_merge, r->sec_wait, r->dev_stage.sec, r->row_stage.sec);
   if (r->device_merge && !r->unordered)
     printf (" pecaller_hip: device merge: %ld columns in %ld ranges\n", r->dev_cols, r->dev_ranges);
+  if (r->device_guide && !r->unordered)
+    printf (" pecaller_hip: device guide merge: %ld columns of %ld intervals in %ld ranges\n", r->dg_cols, r->dg_ivs, r->dg_ranges);
   if (r->device_rows && !r->unordered)
     printf (" pecaller_hip: device rows: %ld rows from the device, %ld holes formatted by the host\n", r->rows_dev, r->rows_hole);
 }

@@ -47,6 +47,9 @@ class PecallDev:
         L.pecall_dev_sites_merge_ms.argtypes = [vp, vp]
         L.pecall_dev_call_records.argtypes = [vp, vp, vp, i, u32, u32, vp, u32, vp, C.POINTER(C.c_long), vp,
                                               i, dbl, dbl, vp, vp, vp, u64, vp, vp, vp, vp, vp]
+        L.pecall_dev_sites_stage_records_guided.argtypes = [vp, vp, vp, i, u32, u32, vp, u32, vp, vp, vp, u32, C.POINTER(C.c_long), vp]
+        L.pecall_dev_call_records_guided.argtypes = [vp, vp, vp, i, u32, u32, vp, u32, vp, vp, vp, u32, C.POINTER(C.c_long), vp,
+                                                     i, dbl, dbl, vp, vp, vp, u64, vp, vp, vp, vp, vp]
         L.pecall_dev_sites_base_text.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp]
         self.L = L
         h = vp()
@@ -210,6 +213,51 @@ class PecallDev:
         rc = self.L.pecall_dev_call_records(self.h, C.addressof(ptrs), _p(n), indiv, int(p0), int(span), _p(letters) if letters.size else None, letters.size, _p(cy),
                                             C.byref(n_cols), _p(col_slot), int(haploid), float(threshold), float(theta), _p(call), _p(site), _p(rows), cap,
                                             C.byref(n_post), _p(typ), _p(ac), _p(npass), _p(den))
+        self.sparse_needed = int(n_post.value)
+        self._ck_records(rc)
+        m = n_cols.value
+        self._sshape = (m, indiv)
+        self.denovo = den[:m]
+        return call[:m], (site[:n_post.value], rows[:n_post.value]), typ[:m], ac[:m], npass[:m], col_slot[:m]
+
+    @staticmethod
+    def _interval_args(iv_first, iv_count, iv_chrom):
+        first = np.ascontiguousarray(iv_first, np.uint32)
+        count = np.ascontiguousarray(iv_count, np.uint32)
+        cy = None if iv_chrom is None else np.ascontiguousarray(iv_chrom, np.uint8)
+        if count.size != first.size or (cy is not None and cy.size != first.size):
+            raise ValueError("iv_first, iv_count and iv_chrom have one entry per interval")
+        return first, count, cy
+
+    def sites_stage_records_guided(self, recs, p0, span, ref_letters, iv_first, iv_count, iv_chrom=None):
+        """columns at every position of the intervals (pecall_dev_sites_stage_records_guided): recs, p0, span, ref_letters as for
+        sites_stage_records; interval k holds the slots iv_first[k] .. iv_first[k] + iv_count[k] - 1 (slot = position - p0), its
+        columns get the chromosome byte iv_chrom[k] (None: 0) -> n_cols, col_slot [n_cols]"""
+        keep, ptrs, n, letters, _ = self._record_args(recs, span, ref_letters, None)
+        first, count, cy = self._interval_args(iv_first, iv_count, iv_chrom)
+        col_slot = np.zeros(max(int(span), 1), np.uint32)
+        n_cols = C.c_long(0)
+        rc = self.L.pecall_dev_sites_stage_records_guided(self.h, C.addressof(ptrs), _p(n), len(keep), int(p0), int(span), _p(letters) if letters.size else None,
+                                                          letters.size, _p(first), _p(count), _p(cy), first.size, C.byref(n_cols), _p(col_slot))
+        self._ck_records(rc)
+        self._sshape = (n_cols.value, len(keep))
+        return n_cols.value, col_slot[:n_cols.value]
+
+    def call_records_guided(self, recs, p0, span, ref_letters, iv_first, iv_count, iv_chrom=None, threshold=0.95, theta=0.001, haploid=False, cap=None):
+        """sites_stage_records_guided and the caller in one call (pecall_dev_call_records_guided) -> as call_records"""
+        keep, ptrs, n, letters, _ = self._record_args(recs, span, ref_letters, None)
+        first, count, cy = self._interval_args(iv_first, iv_count, iv_chrom)
+        indiv = len(keep)
+        call, _, typ, ac, npass, den = self.out_arrays(max(int(span), 1), indiv, posterior=False)
+        cap = int(cap) if cap is not None else max(1024, int(span) // 8)
+        site, rows = np.empty(cap, np.uint32), np.empty((cap, indiv), np.float64)
+        col_slot = np.zeros(max(int(span), 1), np.uint32)
+        n_cols, n_post = C.c_long(0), C.c_uint64(0)
+        self.sparse_needed = 0
+        self._rindiv = indiv
+        rc = self.L.pecall_dev_call_records_guided(self.h, C.addressof(ptrs), _p(n), indiv, int(p0), int(span), _p(letters) if letters.size else None, letters.size,
+                                                   _p(first), _p(count), _p(cy), first.size, C.byref(n_cols), _p(col_slot), int(haploid), float(threshold),
+                                                   float(theta), _p(call), _p(site), _p(rows), cap, C.byref(n_post), _p(typ), _p(ac), _p(npass), _p(den))
         self.sparse_needed = int(n_post.value)
         self._ck_records(rc)
         m = n_cols.value

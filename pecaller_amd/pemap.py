@@ -27,6 +27,7 @@ SYMBOLS = [
     "pecall_dev_run", "pecall_dev_collect", "pecall_dev_call_sites", "pecall_dev_call_sites_sparse", "pecall_dev_set_pedigree",
     "pecall_dev_sites_stage", "pecall_dev_sites_run", "pecall_dev_sites_stats", "pecall_dev_sites_collect", "pecall_dev_pin_host", "pecall_dev_unpin_host",
     "pecall_dev_sites_stage_records", "pecall_dev_sites_gather", "pecall_dev_sites_merge_ms", "pecall_dev_call_records",
+    "pecall_dev_sites_stage_records_guided", "pecall_dev_call_records_guided",
     "pecall_dev_sites_base_text",
 ]
 

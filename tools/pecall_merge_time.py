@@ -6,6 +6,9 @@
           config-4 generator -- a record for nearly every (slot, sample) -- next to pecall_dev_sites_run's kernel_ms on the columns
           they made; medians of `reps` runs after two warm-up runs; the bytes the kernels have to move over their time as a share
           of the 6.3 TB/s a streaming kernel reaches on this part
+  python3 tools/pecall_merge_time.py --guided [--samples 64] [--span-log2 20] [--reps 7]
+      (a) for one guided range (pecall_dev_sites_stage_records_guided): the same records, the columns at the positions of exome-like
+          intervals (100 to 400 positions, about 2 % of the range); mark = the marks from the intervals and the records' check
   python3 tools/pecall_merge_time.py --cli [--columns 1000000] [--samples 64] [--reps 3] [--exe PATH ...]
       (b) pecaller_hip on the files of tools/pecaller_cli_throughput.py, written once: every executable given (default: this tree's;
           name a build of the parent commit as well to compare) with the switch off and on, `reps` times each in turn; the program's
@@ -47,12 +50,39 @@ def kernels(a):
     for r in recs:
         pc.pin_host(r)
     ms, wall = [], []
+    if a.guided:
+        rng = np.random.default_rng(7)
+        first, count, at = [], [], 0
+        while True:
+            at += int(rng.integers(6250, 18251))
+            ln = int(rng.integers(100, 401))
+            if at + ln > span:
+                break
+            first.append(at)
+            count.append(ln)
+            at += ln
+        first, count = np.array(first, np.uint32), np.array(count, np.uint32)
     for k in range(a.reps + 2):
         t0 = time.time()
-        n_cols, _ = pc.sites_stage_records(recs, p0, span, letters)
+        if a.guided:
+            n_cols, _ = pc.sites_stage_records_guided(recs, p0, span, letters, first, count)
+        else:
+            n_cols, _ = pc.sites_stage_records(recs, p0, span, letters)
         wall.append((time.time() - t0) * 1e3)
         ms.append(pc.sites_merge_ms().copy())
     ms = np.median(np.array(ms[2:]), axis=0)
+    if a.guided:
+        # the columns are the intervals' positions; what the kernels move: the marks and chromosome bytes written, the records read for
+        # the check, the marks scanned, and the tile kernel's runs that hold a marked slot
+        slots = np.concatenate([np.arange(f, f + c) for f, c in zip(first, count)])
+        got = pc.sites_gather(np.arange(0, n_cols, max(1, n_cols // 1000), dtype=np.uint32))[0]
+        assert n_cols == len(slots) and np.array_equal(got, reads[slots[::max(1, n_cols // 1000)]])
+        print("guided range: %d samples x %d slots, %d records, %d intervals, %d columns (%.2f %% of the slots)" %
+              (S, span, n_rec, len(first), n_cols, 100.0 * n_cols / span))
+        print("  mark (intervals + check) %.3f ms, scan %.3f ms, tile %.3f ms; merge kernels %.3f ms" % (ms[0], ms[1], ms[2], float(ms.sum())))
+        print("  pecall_dev_sites_stage_records_guided, host wall with the upload from pinned arrays and its two waits: median %.2f ms" % float(np.median(wall[2:])))
+        pc.close()
+        return
     run = [pc.sites_run() for _ in range(a.reps + 2)][2:]
     # the columns the records made are the generator's columns
     got = pc.sites_gather(np.arange(0, n_cols, max(1, n_cols // 1000), dtype=np.uint32))[0]
@@ -114,6 +144,7 @@ def cli(a):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--cli", action="store_true")
+    ap.add_argument("--guided", action="store_true")
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--span-log2", type=int, default=20)
     ap.add_argument("--columns", type=int, default=1000000)

@@ -179,6 +179,46 @@ int pemap_dev_staged_info (pemap_dev * dev, int *n, int *stride, int *paired);
 /* release a device allocation handed out by pemap_dev_synth_genome */
 int pemap_dev_free (pemap_dev * dev, void *d_ptr);
 
+/* ---- read rows made on the device from fastq text ----
+ * What the host program otherwise does before pemap_dev_submit_batch: fill_rows of pemapper_main.c, which follows the reference's read
+ * loop (pemapper.c:649-748 with the trims of pemapper_tsw.c:693-704) -- a search for every line's end and a copy of every sequence.
+ * The rule is pecaller_amd/csrc/pemap_fastq_rule.h (the kernels: pemap_fastq.hip.h).  A line is a run of bytes ended by '\n' ('\r' is
+ * part of it); bytes behind a text's last '\n' are not looked at.  The first line of a stream is skipped, the next is the first
+ * record's sequence; behind a sequence two lines are skipped whatever they hold, then lines up to and including one that begins
+ * with '@', and the line behind that is the next sequence.
+ *   text1/bytes1, text2/bytes2   one piece of each mate file's text, at most 2^30 bytes each; text2 = NULL, 0, 0 in single-end mode
+ *   state1, state2               0: the piece is the beginning of its stream; 1: it begins behind a sequence line
+ *   trim_start, trim_end         bases dropped from either end of every read, as fill_rows does it
+ *   max_records                  records examined per mate at most (the batch's size)
+ *   stride                       of the rows, PEMAP_MAX_READ at least
+ *   res->got[m]                  records of mate m that count: those in front of the first one that stops the mate
+ *   res->end[m]                  0 got == max_records; 1 the text ran out of complete records; 2 (first mate only) a read of 12 bases
+ *                                or fewer; 3 a read shorter than PEMAP_MIN_READ or longer than PEMAP_MAX_READ, its length in bad_len[m]
+ *   res->n                       pairs in the batch: min (got[0], got[1]); got[0] in single-end mode
+ *   res->consumed[m]             offset just behind the '\n' of mate m's n-th sequence line (0 when n == 0): the caller puts the
+ *                                bytes from there on in front of the next piece and passes state 1 (n == 0: the state it passed)
+ * An end of 2 or 3 is a result, not an error; n == 0 is success, nothing is staged or queued and *ticket is not written.  Non-zero is
+ * returned for bad arguments (a NULL pointer, paired mode without text2, stride < PEMAP_MAX_READ, max_records <= 0, a state other
+ * than 0 or 1, a negative trim, a text of more than 2^30 bytes) and for HIP errors.
+ * pemap_dev_stage_fastq is pemap_dev_stage_reads with the rows made on the device: it leaves the object as stage_reads would for the
+ * same rows (the lengths come back to the host, 4 bytes a read), so pemap_dev_run / _run_slice / _collect / _staged_reads /
+ * _staged_info follow unchanged.
+ * pemap_dev_submit_fastq is pemap_dev_submit_batch with the same substitution, under the same threading rules: the text goes up on the
+ * copy stream (by DMA straight out of a range pinned with pemap_dev_pin_host), the parse kernels run there in front of the event the
+ * pipeline waits for, and the call waits only for their control blocks and the lengths while the batches in flight keep the device
+ * busy.  It returns with res filled and batch n queued; m1 / m2 / mapping_type need room for max_records entries.  The result arrays
+ * belong to the library until the batch is delivered; the texts may be reused when the call returns. */
+typedef struct
+{
+  int32_t n, got[2], end[2], bad_len[2];
+  uint64_t consumed[2];
+} pemap_fastq_result;
+int pemap_dev_stage_fastq (pemap_dev * dev, const char *text1, uint64_t bytes1, int state1, const char *text2, uint64_t bytes2, int state2,
+                           int trim_start, int trim_end, int max_records, int stride, pemap_fastq_result * res);
+int pemap_dev_submit_fastq (pemap_dev * dev, const char *text1, uint64_t bytes1, int state1, const char *text2, uint64_t bytes2, int state2,
+                            int trim_start, int trim_end, int max_records, int stride, uint32_t * m1, uint32_t * m2, int *mapping_type,
+                            pemap_fastq_result * res, uint64_t * ticket);
+
 /* counts[genome_size][6] u16 (A,C,G,T,Del,Ins), wrapping as the reference's unsigned short counters do
  * (pemapper.c:53-58); cb (may be NULL) is called once per logged insertion, in unspecified order. */
 int pemap_dev_fetch_pileup (pemap_dev * dev, uint16_t * counts, pemap_ins_cb cb, void *user);

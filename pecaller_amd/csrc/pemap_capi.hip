@@ -16,6 +16,7 @@
 #include "../../include/pemap_hip.h"
 #include "pemap_kernels.hip.h"
 #include "pemap_aux.hip.h"
+#include "pemap_fastq.hip.h"
 #include <rocprim/rocprim.hpp>
 
 static char g_create_err[512] = "";
@@ -157,6 +158,32 @@ static void read_knobs (PmKnobs & k)
   if (k.absorb_chunk < 256) k.absorb_chunk = 256;
 }
 
+// ---- fastq text parsed on the device (pemap_dev_stage_fastq / pemap_dev_submit_fastq; kernels: pemap_fastq.hip.h).  Per mate the text, the
+// scans' arrays and the records' places; they grow on demand and are the object's.  Every call waits for its own kernels before it
+// returns, so one set serves the batches in flight.
+struct PmFastqMate
+{
+  uint8_t *d_text = nullptr;
+  size_t text_cap = 0;
+  unsigned *d_tile_cnt = nullptr;       // per PFQ_TILE bytes
+  size_t tile_cap = 0;
+  unsigned *d_line_start = nullptr;     // n_lines + 1
+  size_t line_cap = 0;
+  PfqTileSum *d_sums = nullptr;         // per PFQ_LINE_TILE lines
+  uint2 *d_tile_in = nullptr;
+  size_t ltile_cap = 0;
+  unsigned *d_rec_off = nullptr, *d_rec_next = nullptr; // max_records
+  int *d_rec_len = nullptr;
+  size_t rec_cap = 0;
+};
+struct PmFastq
+{
+  PmFastqMate mate[2];
+  PfqCtl *d_ctl = nullptr;      // [2]
+  struct Host { PfqCtl ctl[2]; unsigned next[2]; } *h = nullptr;        // pinned
+};
+static void fq_free (PmFastq & F);
+
 struct pemap_dev
 {
   int device = 0;
@@ -237,6 +264,7 @@ struct pemap_dev
   float last_ms[PM_NT] = {};
   std::vector < uint8_t > h_ins;        // host copy of all insertion-log bytes so far
   long summary[13] = {};
+  PmFastq fq;
 };
 
 static inline PmPile pile_of (const pemap_dev * d)
@@ -446,6 +474,7 @@ extern "C" void pemap_dev_destroy (pemap_dev * d)
   hipFree (d->d_cur);
   hipFree (d->d_seed_scratch);
   hipFree (d->d_ins_log);
+  fq_free (d->fq);
   for (int i = 0; i < PM_RING; i++)
     {
       if (d->ring[i].h_len)
@@ -2040,6 +2069,33 @@ static int ring_setup (pemap_dev * d, int n, int stride, std::unique_lock < std:
   return 0;
 }
 
+// the end of a submit: the batch's rows and lengths are on their way into slot r (r.ev_copy recorded behind them, one per slice of
+// chunk_pairs_for); its kernels, the copy of its results, and the slot becomes a batch in flight
+static int ring_queue_run (pemap_dev * d, PmRingSlot & r, int first, int n, uint32_t * m1, uint32_t * m2, int *mapping_type, uint64_t * ticket)
+{
+  TRY (run_slice (d, first, n, 0, r.ev_copy.data ()));
+  // results: on the ALU stream itself, behind the batch's last kernel (every other stream's work for the batch precedes it).
+  // Not on a stream of their own: HIP multiplexes streams onto a few hardware queues, and a copy stream parked on "batch k is
+  // done" held up whichever pipeline stream shared its queue -- 3.5 ms per batch (measured: 45.2 ms per step against 41.7).
+  hipStream_t rs = d->stream;
+  HIPCHK (d, hipMemcpyAsync (r.h_res, d->d_m1 + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
+  if (d->paired)
+    HIPCHK (d, hipMemcpyAsync (r.h_res + d->ring_cap, d->d_m2 + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
+  HIPCHK (d, hipMemcpyAsync (r.h_res + 2 * (size_t) d->ring_cap, d->d_mtype + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
+  HIPCHK (d, hipEventRecord (r.ev_done, rs));
+  // the slot becomes a batch in flight only now that its event is recorded: an error above leaves it free, and nothing stale is
+  // ever "delivered" into the caller's buffers or folded into the summary
+  r.active = true;
+  r.seq = d->ring_seq;
+  r.n = n;
+  r.first = first;
+  r.m1 = m1;
+  r.m2 = m2;
+  r.mt = mapping_type;
+  *ticket = d->ring_seq++;
+  return 0;
+}
+
 extern "C" int pemap_dev_submit_batch (pemap_dev * d, const char *reads1, const int *len1, const char *reads2, const int *len2,
                                        int n, int stride, uint32_t * m1, uint32_t * m2, int *mapping_type, uint64_t * ticket)
 {
@@ -2131,27 +2187,7 @@ extern "C" int pemap_dev_submit_batch (pemap_dev * d, const char *reads1, const 
         HIPCHK (d, hipMemcpyAsync (d->d_reads2 + (size_t) (first + off) * stride, src2, (size_t) m * stride, hipMemcpyHostToDevice, d->stream_h2d));
       HIPCHK (d, hipEventRecord (r.ev_copy[k], d->stream_h2d));
     }
-  TRY (run_slice (d, first, n, 0, r.ev_copy.data ()));
-  // results: on the ALU stream itself, behind the batch's last kernel (every other stream's work for the batch precedes it).
-  // Not on a stream of their own: HIP multiplexes streams onto a few hardware queues, and a copy stream parked on "batch k is
-  // done" held up whichever pipeline stream shared its queue -- 3.5 ms per batch (measured: 45.2 ms per step against 41.7).
-  hipStream_t rs = d->stream;
-  HIPCHK (d, hipMemcpyAsync (r.h_res, d->d_m1 + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
-  if (d->paired)
-    HIPCHK (d, hipMemcpyAsync (r.h_res + d->ring_cap, d->d_m2 + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
-  HIPCHK (d, hipMemcpyAsync (r.h_res + 2 * (size_t) d->ring_cap, d->d_mtype + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
-  HIPCHK (d, hipEventRecord (r.ev_done, rs));
-  // the slot becomes a batch in flight only now that its event is recorded: an error above leaves it free, and nothing stale is
-  // ever "delivered" into the caller's buffers or folded into the summary
-  r.active = true;
-  r.seq = d->ring_seq;
-  r.n = n;
-  r.first = first;
-  r.m1 = m1;
-  r.m2 = m2;
-  r.mt = mapping_type;
-  *ticket = d->ring_seq++;
-  return 0;
+  return ring_queue_run (d, r, first, n, m1, m2, mapping_type, ticket);
 }
 
 extern "C" int pemap_dev_wait_batch (pemap_dev * d, uint64_t ticket)
@@ -2623,4 +2659,256 @@ extern "C" int pemap_dev_staged_info (pemap_dev * d, int *n, int *stride, int *p
   *stride = d->stride;
   *paired = d->staged_paired;
   return 0;
+}
+
+// ---- fastq text -> read rows on the device -----------------------------------------------------------------
+// pemap_dev_stage_fastq and pemap_dev_submit_fastq are pemap_dev_stage_reads and pemap_dev_submit_batch with the rows made by the
+// kernels of pemap_fastq.hip.h instead of fill_rows (pemapper_main.c).  Both are fq_parse (text up, stages 1-3, the control blocks
+// back: the result but for `consumed`) and, when the batch holds a pair at least, fq_rows (stage 4 into the staged arrays, the lengths
+// and `consumed` back); they differ in the stream and in where the rows go.
+struct PmFastqArgs
+{
+  const char *text[2];
+  uint64_t bytes[2];
+  int state[2];
+  int trim_start, trim_end, max_records, stride;
+};
+
+static void fq_free (PmFastq & F)
+{
+  for (PmFastqMate & M : F.mate)
+    {
+      for (void *p : { (void *) M.d_text, (void *) M.d_tile_cnt, (void *) M.d_line_start, (void *) M.d_sums, (void *) M.d_tile_in, (void *) M.d_rec_off,
+                       (void *) M.d_rec_next, (void *) M.d_rec_len })
+        hipFree (p);
+      M = PmFastqMate ();
+    }
+  hipFree (F.d_ctl);
+  if (F.h)
+    hipHostFree (F.h);
+  F.d_ctl = nullptr;
+  F.h = nullptr;
+}
+
+// an array of the parse that holds `need` elements at least (its contents are not kept)
+template < class T > static int fq_grow (pemap_dev * d, T * &p, size_t have, size_t need)
+{
+  if (p && have >= need)
+    return 0;
+  hipFree (p);
+  p = nullptr;
+  return dev_alloc (d, &p, need);
+}
+
+static int fq_check_args (pemap_dev * d, const char *who, const PmFastqArgs & a, const pemap_fastq_result * res)
+{
+  if (!res || !a.text[0])
+    return fail (d, "%s: a required pointer is NULL", who);
+  if (d->paired && !a.text[1])
+    return fail (d, "%s: paired mode needs the second text", who);
+  if (a.stride < PEMAP_MIN_READ || a.stride < PEMAP_MAX_READ)
+    return fail (d, "%s: stride %d is below the longest read a row may hold (%d)", who, a.stride, PEMAP_MAX_READ);
+  if (a.max_records <= 0)
+    return fail (d, "%s: max_records = %d", who, a.max_records);
+  if (a.trim_start < 0 || a.trim_end < 0)
+    return fail (d, "%s: trims %d / %d", who, a.trim_start, a.trim_end);
+  for (int m = 0; m < (d->paired ? 2 : 1); m++)
+    {
+      if (a.state[m] != 0 && a.state[m] != 1)
+        return fail (d, "%s: state %d of text %d (0: the beginning of a stream, 1: behind a sequence line)", who, a.state[m], m + 1);
+      if (a.bytes[m] > PFQ_MAX_TEXT)
+        return fail (d, "%s: text %d has %llu bytes, more than %u a call", who, m + 1, (unsigned long long) a.bytes[m], PFQ_MAX_TEXT);
+    }
+  return 0;
+}
+
+static int fq_parse (pemap_dev * d, hipStream_t st, const PmFastqArgs & a, pemap_fastq_result * res)
+{
+  PmFastq & F = d->fq;
+  const int mates = d->paired ? 2 : 1;
+  if (!F.d_ctl)
+    {
+      TRY (dev_alloc (d, &F.d_ctl, 2));
+      HIPCHK (d, hipHostMalloc ((void **) &F.h, sizeof (*F.h), hipHostMallocDefault));
+    }
+  memset (res, 0, sizeof (*res));
+  HIPCHK (d, hipMemsetAsync (F.d_ctl, 0, 2 * sizeof (PfqCtl), st));
+  // stage 1, first half: the number of lines
+  for (int m = 0; m < mates; m++)
+    {
+      PmFastqMate & M = F.mate[m];
+      const unsigned bytes = (unsigned) a.bytes[m];
+      HIPCHK (d, hipMemsetAsync (&F.d_ctl[m].stop, 0xff, sizeof (F.d_ctl[m].stop), st));
+      if (!bytes)
+        continue;
+      const size_t padded = (((size_t) bytes + 15) & ~(size_t) 15) + 16;        // every 16-byte load that begins inside the text stays inside
+      TRY (fq_grow (d, M.d_text, M.text_cap, padded));
+      M.text_cap = M.text_cap > padded ? M.text_cap : padded;
+      HIPCHK (d, hipMemcpyAsync (M.d_text, a.text[m], bytes, hipMemcpyHostToDevice, st));
+      const unsigned nt = (bytes + PFQ_TILE - 1) / PFQ_TILE;
+      TRY (fq_grow (d, M.d_tile_cnt, M.tile_cap, nt));
+      M.tile_cap = M.tile_cap > nt ? M.tile_cap : nt;
+      hipLaunchKernelGGL (pfq_nl_count_kernel, dim3 (nt), dim3 (PFQ_BLOCK), 0, st, (const uint4 *) M.d_text, bytes, M.d_tile_cnt);
+      hipLaunchKernelGGL (pfq_sum_top_kernel, dim3 (1), dim3 (PFQ_TOP), 0, st, M.d_tile_cnt, nt, &F.d_ctl[m].n_lines);
+    }
+  HIPCHK (d, hipGetLastError ());
+  HIPCHK (d, hipMemcpyAsync (F.h->ctl, F.d_ctl, 2 * sizeof (PfqCtl), hipMemcpyDeviceToHost, st));
+  HIPCHK (d, hipStreamSynchronize (st));
+  // the rest of stage 1, stages 2 and 3
+  unsigned rec_limit[2] = { 0, 0 };
+  for (int m = 0; m < mates; m++)
+    {
+      PmFastqMate & M = F.mate[m];
+      const unsigned bytes = (unsigned) a.bytes[m], nl = F.h->ctl[m].n_lines;
+      if (!nl)
+        continue;
+      if (nl > bytes)
+        return fail (d, "internal: %u lines in %u bytes", nl, bytes);
+      // (a text has no more records than lines: an array of that many serves whatever max_records is)
+      const unsigned lim = rec_limit[m] = nl < (unsigned) a.max_records ? nl : (unsigned) a.max_records;
+      const unsigned nt = (bytes + PFQ_TILE - 1) / PFQ_TILE, nlt = (nl + PFQ_LINE_TILE - 1) / PFQ_LINE_TILE;
+      TRY (fq_grow (d, M.d_line_start, M.line_cap, (size_t) nl + 1));
+      M.line_cap = M.line_cap > (size_t) nl + 1 ? M.line_cap : (size_t) nl + 1;
+      TRY (fq_grow (d, M.d_sums, M.ltile_cap, nlt));
+      TRY (fq_grow (d, M.d_tile_in, M.ltile_cap, nlt));
+      M.ltile_cap = M.ltile_cap > nlt ? M.ltile_cap : nlt;
+      TRY (fq_grow (d, M.d_rec_off, M.rec_cap, lim));
+      TRY (fq_grow (d, M.d_rec_next, M.rec_cap, lim));
+      TRY (fq_grow (d, M.d_rec_len, M.rec_cap, lim));
+      M.rec_cap = M.rec_cap > lim ? M.rec_cap : lim;
+      hipLaunchKernelGGL (pfq_nl_apply_kernel, dim3 (nt), dim3 (PFQ_BLOCK), 0, st, (const uint4 *) M.d_text, bytes, (const unsigned *) M.d_tile_cnt, nl, M.d_line_start);
+      hipLaunchKernelGGL (pfq_role_sum_kernel, dim3 (nlt), dim3 (PFQ_BLOCK), 0, st, (const uint8_t *) M.d_text, bytes, (const unsigned *) M.d_line_start, nl, M.d_sums);
+      hipLaunchKernelGGL (pfq_role_top_kernel, dim3 (1), dim3 (PFQ_TOP), 0, st, (const PfqTileSum *) M.d_sums, nlt, a.state[m], M.d_tile_in, &F.d_ctl[m]);
+      hipLaunchKernelGGL (pfq_records_kernel, dim3 (nlt), dim3 (PFQ_BLOCK), 0, st, (const uint8_t *) M.d_text, bytes, (const unsigned *) M.d_line_start, nl,
+                          (const uint2 *) M.d_tile_in, a.trim_start, a.trim_end, m == 0 ? 1 : 0, lim, M.d_rec_off, M.d_rec_len, M.d_rec_next, &F.d_ctl[m]);
+    }
+  HIPCHK (d, hipGetLastError ());
+  HIPCHK (d, hipMemcpyAsync (F.h->ctl, F.d_ctl, 2 * sizeof (PfqCtl), hipMemcpyDeviceToHost, st));
+  HIPCHK (d, hipStreamSynchronize (st));
+  for (int m = 0; m < mates; m++)
+    {
+      const PfqCtl & c = F.h->ctl[m];
+      const unsigned seen = c.n_records < rec_limit[m] ? c.n_records : rec_limit[m];    // records that were examined
+      if (c.stop != PFQ_NO_STOP)
+        {
+          const unsigned k = (unsigned) (c.stop >> 32);
+          if (k >= seen)
+            return fail (d, "internal: record %u stops text %d, which has %u", k, m + 1, seen);
+          res->got[m] = (int) k;
+          res->end[m] = (c.stop & PFQ_STOP_BAD_LEN) ? PFQ_END_BAD_LEN : PFQ_END_SHORT_FIRST;
+          res->bad_len[m] = res->end[m] == PFQ_END_BAD_LEN ? (int) (c.stop & (PFQ_STOP_BAD_LEN - 1u)) : 0;
+        }
+      else
+        {
+          res->got[m] = (int) seen;
+          res->end[m] = pfq_end_unstopped (res->got[m], a.max_records);
+        }
+    }
+  res->n = pfq_pairs (res->got[0], res->got[1], d->paired);
+  return 0;
+}
+
+// records [0, n) of the last fq_parse into rows / lens on the device (per mate), the lengths into h_len[m] as well; res->consumed
+static int fq_rows (pemap_dev * d, hipStream_t st, const PmFastqArgs & a, int n, uint8_t * const rows[2], int *const lens[2], int *const h_len[2], int *mx, int *mn,
+                    pemap_fastq_result * res)
+{
+  PmFastq & F = d->fq;
+  const int mates = d->paired ? 2 : 1;
+  const unsigned per_block = PFQ_BLOCK / PFQ_ROW_LANES;
+  for (int m = 0; m < mates; m++)
+    {
+      PmFastqMate & M = F.mate[m];
+      if ((size_t) n > M.rec_cap)
+        return fail (d, "internal: %d rows of %zu records", n, M.rec_cap);
+      hipLaunchKernelGGL (pfq_rows_kernel, dim3 (((unsigned) n + per_block - 1) / per_block), dim3 (PFQ_BLOCK), 0, st, (const uint8_t *) M.d_text, (unsigned) a.bytes[m],
+                          (const unsigned *) M.d_rec_off, (const int *) M.d_rec_len, (unsigned) n, (unsigned) a.stride, rows[m], lens[m]);
+      HIPCHK (d, hipGetLastError ());
+      HIPCHK (d, hipMemcpyAsync (h_len[m], lens[m], (size_t) n * sizeof (int), hipMemcpyDeviceToHost, st));
+      HIPCHK (d, hipMemcpyAsync (&F.h->next[m], M.d_rec_next + (n - 1), sizeof (unsigned), hipMemcpyDeviceToHost, st));
+    }
+  HIPCHK (d, hipStreamSynchronize (st));
+  for (int m = 0; m < mates; m++)
+    {
+      res->consumed[m] = F.h->next[m];
+      TRY (check_lengths (d, h_len[m], n, mx, mn));
+    }
+  return 0;
+}
+
+extern "C" int pemap_dev_stage_fastq (pemap_dev * d, const char *text1, uint64_t bytes1, int state1, const char *text2, uint64_t bytes2, int state2, int trim_start,
+                                      int trim_end, int max_records, int stride, pemap_fastq_result * res)
+{
+  HIPCHK (d, hipSetDevice (d->device));
+  const PmFastqArgs a = { { text1, text2 }, { bytes1, bytes2 }, { state1, state2 }, trim_start, trim_end, max_records, stride };
+  TRY (fq_check_args (d, "stage_fastq", a, res));
+  TRY (fq_parse (d, d->stream, a, res));
+  const int n = res->n;
+  if (n == 0)
+    return 0;
+  TRY (ring_leave (d));
+  TRY (pemap_dev_sync (d));
+  TRY (ensure_reads (d, n, stride, d->paired));
+  d->h_len1.assign ((size_t) n, 0);
+  d->h_len2.assign (d->paired ? (size_t) n : 0, 0);
+  uint8_t *const rows[2] = { d->d_reads1, d->d_reads2 };
+  int *const lens[2] = { d->d_len1, d->d_len2 }, *const h_len[2] = { d->h_len1.data (), d->h_len2.data () };
+  int mx = 0, mn = 1 << 30;
+  TRY (fq_rows (d, d->stream, a, n, rows, lens, h_len, &mx, &mn, res));
+  d->n_staged = n;
+  d->staged_paired = d->paired;
+  d->max_len_staged = mx;
+  d->min_len_staged = mn;
+  return 0;
+}
+
+extern "C" int pemap_dev_submit_fastq (pemap_dev * d, const char *text1, uint64_t bytes1, int state1, const char *text2, uint64_t bytes2, int state2, int trim_start,
+                                       int trim_end, int max_records, int stride, uint32_t * m1, uint32_t * m2, int *mapping_type, pemap_fastq_result * res,
+                                       uint64_t * ticket)
+{
+  std::unique_lock < std::mutex > sub (d->submit_mu);
+  std::unique_lock < std::mutex > lk (d->mu);
+  HIPCHK (d, hipSetDevice (d->device));
+  if (!d->index_ready)
+    return fail (d, "submit_fastq: no index loaded");
+  const PmFastqArgs a = { { text1, text2 }, { bytes1, bytes2 }, { state1, state2 }, trim_start, trim_end, max_records, stride };
+  TRY (fq_check_args (d, "submit_fastq", a, res));
+  if (!m1 || !mapping_type || !ticket || (d->paired && !m2))
+    return fail (d, "submit_fastq: a required pointer is NULL");
+  if (!d->stream_h2d)
+    HIPCHK (d, hipStreamCreateWithFlags (&d->stream_h2d, hipStreamNonBlocking));
+  // text and parse kernels on the copy stream: the batches in flight keep the pipeline's streams busy meanwhile
+  TRY (fq_parse (d, d->stream_h2d, a, res));
+  const int n = res->n;
+  if (n == 0)
+    return 0;
+  TRY (ring_setup (d, n, stride, lk));
+  const int slot = (int) (d->ring_seq % PM_RING);
+  PmRingSlot & r = d->ring[slot];
+  TRY (ring_finish (d, slot, lk));
+  const int first = slot * d->ring_cap;
+  uint8_t *const rows[2] = { d->d_reads1 + (size_t) first * stride, d->paired ? d->d_reads2 + (size_t) first * stride : nullptr };
+  int *const lens[2] = { d->d_len1 + first, d->paired ? d->d_len2 + first : nullptr }, *const h_len[2] = { r.h_len, r.h_len + d->ring_cap };
+  int mx = 0, mn = 1 << 30;
+  TRY (fq_rows (d, d->stream_h2d, a, n, rows, lens, h_len, &mx, &mn, res));
+  if (mx > d->max_len_staged)
+    d->max_len_staged = mx;
+  if (mn < d->min_len_staged)
+    d->min_len_staged = mn;
+  memcpy (&d->h_len1[first], r.h_len, (size_t) n * sizeof (int));
+  if (d->paired)
+    memcpy (&d->h_len2[first], r.h_len + d->ring_cap, (size_t) n * sizeof (int));
+  if (!d->stream2)
+    TRY (ensure_pipeline (d, 0));
+  // the rows are on the device already: every slice's event is the same point of the copy stream
+  const int slice = chunk_pairs_for (d, n, d->max_len_staged);
+  const int n_slices = (n + slice - 1) / slice;
+  while ((int) r.ev_copy.size () < n_slices)
+    {
+      hipEvent_t e;
+      HIPCHK (d, hipEventCreateWithFlags (&e, hipEventDisableTiming));
+      r.ev_copy.push_back (e);
+    }
+  for (int k = 0; k < n_slices; k++)
+    HIPCHK (d, hipEventRecord (r.ev_copy[k], d->stream_h2d));
+  return ring_queue_run (d, r, first, n, m1, m2, mapping_type, ticket);
 }

@@ -19,6 +19,9 @@
  * PEMAP_DEVICES=a,b,... (1 to 16 device ids; unset: one object on PEMAP_DEVICE, as ever) maps on several device objects: the first
  * builds the index and hands it on (pemap_dev_index_share), the batches are dealt round robin, and before an output set is written
  * the objects' pileups are summed into the first (pemap_dev_absorb).  An id may repeat: several objects on one GPU, a rehearsal.
+ * PEMAPPER_DEVICE_PARSE=1 (off by default): the read files' text goes to the device as it is and the read rows are made there
+ * (pemap_dev_submit_fastq; map_one_file_parse below) instead of by fill_rows, a line at a time, on the host.  Every output file is
+ * the same; the number of "We have read" lines may differ.  PEMAPPER_PARSE_BYTES: the text buffer per mate (default 384 bytes per pair of a batch).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -32,11 +35,16 @@
 #include "../../include/pemap_hip.h"
 #include "host_io.h"
 
+/* (weak: the program links against a library without this entry too, and PEMAPPER_DEVICE_PARSE=1 then ends the run with a message) */
+extern __typeof__ (pemap_dev_submit_fastq) pemap_dev_submit_fastq __attribute__ ((weak));
+
 #define MAX_FILES 2000
 #define BATCH_PAIRS (1 << 20)
 #define ROW_STRIDE 288
 #define MAX_DEVS 16
 #define MAX_SETS 5              /* batch-buffer sets a file worker owns at most */
+#define PARSE_BYTES_PER_PAIR 384 /* PEMAPPER_DEVICE_PARSE: the text buffer per mate holds this for every pair of a batch; a record of 2 x 150 has about 345 */
+#define PARSE_BYTES_MAX ((size_t) 1 << 30)      /* what pemap_dev_submit_fastq takes per mate and call */
 
 static void
 die (const char *msg, const char *arg)
@@ -159,6 +167,33 @@ lr_close (lreader * r)
   free (r->buf);
 }
 
+/* the block at hand is used up: hand it back and take the next one; 0 at the end of data */
+static int
+lr_next_block (lreader * r)
+{
+  if (r->eof)
+    return 0;
+  pthread_mutex_lock (&r->mu);
+  if (r->len > 0)
+    {
+      r->head = (r->head + 1) % LR_RING;
+      r->count--;
+      r->len = r->pos = 0;
+      pthread_cond_broadcast (&r->cv);
+    }
+  while (r->count == 0 && !r->done)
+    pthread_cond_wait (&r->cv, &r->mu);
+  if (r->count == 0)
+    r->eof = 1;
+  else
+    {
+      r->len = (size_t) r->ring_len[r->head];
+      r->pos = 0;
+    }
+  pthread_mutex_unlock (&r->mu);
+  return !r->eof;
+}
+
 /* next line (its '\n' not counted; a '\r' stays, as in the reference; NOT 0-terminated unless it was put together in r->buf) and its
    length, NULL at end of data.  A line that lies inside one
    block of the ring is returned where it is (valid until the next call); only a line that straddles blocks is put together in
@@ -198,28 +233,33 @@ lr_gets (lreader * r, size_t *len_out)
               return r->buf;
             }
         }
-      if (r->eof)
+      if (!lr_next_block (r))
         return NULL;            /* an unterminated last line is dropped, pemapper.c:2466-2481 */
-      /* the block is used up: hand it back and take the next one */
-      pthread_mutex_lock (&r->mu);
-      if (r->len > 0)
-        {
-          r->head = (r->head + 1) % LR_RING;
-          r->count--;
-          r->len = r->pos = 0;
-          pthread_cond_broadcast (&r->cv);
-        }
-      while (r->count == 0 && !r->done)
-        pthread_cond_wait (&r->cv, &r->mu);
-      if (r->count == 0)
-        r->eof = 1;
-      else
-        {
-          r->len = (size_t) r->ring_len[r->head];
-          r->pos = 0;
-        }
-      pthread_mutex_unlock (&r->mu);
     }
+}
+
+/* PEMAPPER_DEVICE_PARSE: the stream's bytes as they come, up to `room` of them; fewer only at the end of data.  (Not to be mixed
+   with lr_gets on one reader.) */
+static size_t
+lr_take (lreader * r, char *dst, size_t room)
+{
+  size_t got = 0;
+  while (got < room)
+    {
+      if (r->pos < r->len)
+        {
+          size_t n = r->len - r->pos;
+          if (n > room - got)
+            n = room - got;
+          memcpy (dst + got, r->ring[r->head] + r->pos, n);
+          r->pos += n;
+          got += n;
+          continue;
+        }
+      if (!lr_next_block (r))
+        break;
+    }
+  return got;
 }
 
 /* ---- one mate file's share of a batch: the records of the reference's read loop (pemapper.c:649-748: the first record is the line
@@ -534,6 +574,8 @@ typedef struct
   char **names1, **names2;
   int next, last;               /* files [next, last) of the output set are still to be taken */
   long tot_pairs;
+  int device_parse;             /* PEMAPPER_DEVICE_PARSE=1 */
+  size_t parse_bytes;
   pthread_mutex_t mu;
 } file_pool;
 
@@ -542,6 +584,8 @@ typedef struct
   file_pool *P;
   char *r1s[MAX_SETS], *r2s[MAX_SETS];
   int *l1s[MAX_SETS], *l2s[MAX_SETS], *mts[MAX_SETS];
+  char *text[2];                /* PEMAPPER_DEVICE_PARSE: a page-locked text buffer per mate (the library is done with a text when the submit returns) */
+  size_t text_cap[2];
 } file_worker;
 
 /* the object the pool's next batch goes to */
@@ -560,6 +604,21 @@ static void
 worker_alloc (file_worker * w, file_pool * P)
 {
   w->P = P;
+  if (P->device_parse)
+    {
+      /* no row buffers: the rows are made on the device.  The mapping classes still come back per batch in flight. */
+      for (int k = 0; k < P->n_sets; k++)
+        if (!(w->mts[k] = (int *) malloc (sizeof (int) * (size_t) P->batch_pairs)))
+          die ("\n pemapper_hip: out of memory for %s", "the batch buffers");
+      for (int m = 0; m < (P->paired ? 2 : 1); m++)
+        {
+          w->text_cap[m] = P->parse_bytes;
+          if (!(w->text[m] = (char *) malloc (w->text_cap[m])))
+            die ("\n pemapper_hip: out of memory for %s", "the text buffers");
+          (void) pemap_dev_pin_host (P->dev, w->text[m], (uint64_t) w->text_cap[m]);
+        }
+      return;
+    }
   for (int k = 0; k < P->n_sets; k++)
     {
       w->r1s[k] = (char *) malloc ((size_t) P->batch_pairs * ROW_STRIDE);
@@ -575,12 +634,222 @@ worker_alloc (file_worker * w, file_pool * P)
     }
 }
 
+/* the end of a file pair: the rate line, the .mfile of either mate, the readers closed, the pool's count */
+static void
+file_done (file_pool * P, int iter, uint32_t * maps1, uint32_t * maps2, size_t current_read, const struct timespec *ts0, lreader * in1, lreader * in2)
+{
+  const int paired = P->paired;
+  char path[4200];
+  struct timespec ts1;
+  clock_gettime (CLOCK_MONOTONIC, &ts1);
+  {
+    const double sec = (double) (ts1.tv_sec - ts0->tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0->tv_nsec);
+    printf ("\n pemapper_hip: %ld %s read and mapped in %.3f s (%.2f M reads/s, input parsing included) \n", (long) current_read,
+            paired ? "pairs" : "reads", sec, (paired ? 2.0 : 1.0) * (double) current_read / (sec > 0 ? sec : 1) / 1e6);
+  }
+  printf ("\n Made it out alive, and have started cleanup \n\n");
+  snprintf (path, sizeof path, "%s.mfile", P->names1[iter]);
+  FILE *m = fopen (path, "wb");
+  if (!m)
+    die ("\n Can not open file %s", path);
+  fwrite (maps1, sizeof (uint32_t), current_read, m);
+  fclose (m);
+  if (paired)
+    {
+      snprintf (path, sizeof path, "%s.mfile", P->names2[iter]);
+      m = fopen (path, "wb");
+      if (!m)
+        die ("\n Can not open file %s", path);
+      fwrite (maps2, sizeof (uint32_t), current_read, m);
+      fclose (m);
+      lr_close (in2);
+    }
+  lr_close (in1);
+  free (maps1);
+  free (maps2);
+  pthread_mutex_lock (&P->mu);
+  P->tot_pairs += (long) current_read;
+  pthread_mutex_unlock (&P->mu);
+}
+
+
+/* ---- PEMAPPER_DEVICE_PARSE=1: map_one_file without fill_rows.  The reader's blocks (inflated, or plain text) are moved as they come
+        into the worker's page-locked text buffer of either mate, behind the tail the last batch left unconsumed; the device finds the
+        lines, takes the records and makes the rows (pemap_dev_submit_fastq, which returns with the counts of either mate: `res` is
+        what fill_rows leaves in its two fill_jobs, and lines 636-655 of map_one_file are applied to it as they stand).  A batch may
+        come back short because the buffer held fewer records than it takes: the run ends only when a mate's stream has ended, or a
+        length ends it. */
+typedef struct
+{
+  lreader *in;
+  char *buf;
+  size_t len, cap;
+  int eof;                      /* the stream has ended: the buffer holds all that is left of it */
+} text_job;
+
+static void *
+fill_text (void *arg)
+{
+  text_job *t = (text_job *) arg;
+  if (!t->eof && t->len < t->cap)
+    {
+      const size_t room = t->cap - t->len;
+      const size_t got = lr_take (t->in, t->buf + t->len, room);
+      t->len += got;
+      if (got < room)
+        t->eof = 1;
+    }
+  return NULL;
+}
+
+static void
+map_one_file_parse (file_worker * w, int iter)
+{
+  file_pool *P = w->P;
+  const int paired = P->paired, n_sets = P->n_sets, mates = paired ? 2 : 1;
+  int cur_set = 0, have_pending[MAX_SETS] = { 0 };
+  uint64_t pending[MAX_SETS] = { 0 };
+  pemap_dev *pending_dev[MAX_SETS] = { NULL };
+  lreader in1, in2;
+  lr_open (&in1, P->names1[iter]);
+  if (paired)
+    lr_open (&in2, P->names2[iter]);
+  size_t cap = 1 << 20, current_read = 0;
+  uint32_t *maps1 = (uint32_t *) calloc (cap, sizeof (uint32_t)), *maps2 = paired ? (uint32_t *) calloc (cap, sizeof (uint32_t)) : NULL;
+  struct timespec ts0;
+  clock_gettime (CLOCK_MONOTONIC, &ts0);
+  text_job tj[2];
+  memset (tj, 0, sizeof tj);
+  tj[0].in = &in1;
+  tj[1].in = &in2;
+  for (int m = 0; m < mates; m++)
+    {
+      tj[m].buf = w->text[m];
+      tj[m].cap = w->text_cap[m];
+    }
+  int state[2] = { 0, 0 };
+  int not_done = 1;
+  printf ("\n Ready to map \n");
+  while (not_done)
+    {
+      long want = P->batch_pairs;
+      if ((long) current_read + want > P->max_reads)
+        want = P->max_reads - (long) current_read;
+      if (want <= 0)
+        break;
+      pthread_t t2;
+      int threaded = 0;
+      if (paired)
+        threaded = pthread_create (&t2, NULL, fill_text, &tj[1]) == 0;
+      fill_text (&tj[0]);
+      if (paired)
+        {
+          if (threaded)
+            pthread_join (t2, NULL);
+          else
+            fill_text (&tj[1]);
+        }
+      if (current_read + (size_t) want > cap)
+        {
+          /* the results of up to `want` pairs land behind current_read; the batches in flight write into the arrays about to move */
+          for (int k = 0; k < n_sets; k++)
+            {
+              const int s = (cur_set + k) % n_sets;
+              if (have_pending[s])
+                ck (pending_dev[s], pemap_dev_wait_batch (pending_dev[s], pending[s]));
+              have_pending[s] = 0;
+            }
+          size_t ncap = cap;
+          while (ncap < current_read + (size_t) want)
+            ncap *= 2;
+          maps1 = (uint32_t *) realloc (maps1, ncap * sizeof (uint32_t));
+          if (paired)
+            maps2 = (uint32_t *) realloc (maps2, ncap * sizeof (uint32_t));
+          cap = ncap;
+        }
+      pemap_fastq_result res;
+      uint64_t ticket = 0;
+      pemap_dev *dev = deal_dev (P);
+      ck (dev, pemap_dev_submit_fastq (dev, tj[0].buf, tj[0].len, state[0], paired ? tj[1].buf : NULL, paired ? tj[1].len : 0, paired ? state[1] : 0, P->trim_s,
+                                       P->trim_e, (int) want, ROW_STRIDE, maps1 + current_read, paired ? maps2 + current_read : NULL, w->mts[cur_set], &res,
+                                       &ticket));
+      const int nb = res.n;
+      /* (map_one_file's rules, with res for j1 and j2) */
+      if (res.end[0] == 3 && res.got[0] == nb)
+        {
+          printf ("\n Read %ld of %s has length %d: supported range is %d..%d \n", (long) current_read + nb, P->names1[iter], res.bad_len[0], PEMAP_MIN_READ,
+                  PEMAP_MAX_READ);
+          exit (1);
+        }
+      if (paired && res.end[1] == 3 && res.got[1] == nb && !(res.end[0] == 2 && res.got[0] == nb))
+        {
+          printf ("\n Read %ld of %s has length %d: supported range is %d..%d \n", (long) current_read + nb, P->names2[iter], res.bad_len[1], PEMAP_MIN_READ,
+                  PEMAP_MAX_READ);
+          exit (1);
+        }
+      current_read += (size_t) nb;
+      /* short of `want`: the end of the run if the mate that fell short was stopped by a length, or ran out of text with its stream at
+         its end; otherwise its buffer merely held no more complete records */
+      if (nb < want)
+        for (int m = 0; m < mates; m++)
+          if (res.got[m] == nb && (res.end[m] == 2 || res.end[m] == 3 || (res.end[m] == 1 && tj[m].eof)))
+            not_done = 0;
+      if ((long) current_read >= P->max_reads)
+        not_done = 0;
+      if (nb > 0)
+        {
+          pending[cur_set] = ticket;
+          pending_dev[cur_set] = dev;
+          have_pending[cur_set] = 1;
+          cur_set = (cur_set + 1) % n_sets;
+          if (have_pending[cur_set])
+            ck (pending_dev[cur_set], pemap_dev_wait_batch (pending_dev[cur_set], pending[cur_set]));
+          have_pending[cur_set] = 0;
+          /* the unconsumed tail goes to the front; the next piece continues behind a sequence line */
+          for (int m = 0; m < mates; m++)
+            {
+              const size_t used = (size_t) res.consumed[m];
+              memmove (tj[m].buf, tj[m].buf + used, tj[m].len - used);
+              tj[m].len -= used;
+              state[m] = 1;
+            }
+          printf ("\n We have read %ld reads \n\n", (long) current_read);
+        }
+      else if (not_done)
+        {
+          /* not one record: a mate whose full buffer holds no complete record has a line (or the lines between two records) longer
+             than the buffer, which grows */
+          for (int m = 0; m < mates; m++)
+            if (res.got[m] == 0 && tj[m].len == tj[m].cap)
+              {
+                if (tj[m].cap >= PARSE_BYTES_MAX)
+                  die ("\n pemapper_hip: %s holds more than 2^30 bytes without a complete record", m ? P->names2[iter] : P->names1[iter]);
+                size_t ncap = tj[m].cap * 2 < PARSE_BYTES_MAX ? tj[m].cap * 2 : PARSE_BYTES_MAX;
+                (void) pemap_dev_unpin_host (P->dev, tj[m].buf);
+                char *nbuf = (char *) realloc (tj[m].buf, ncap);
+                if (!nbuf)
+                  die ("\n pemapper_hip: out of memory for %s", "the text buffers");
+                (void) pemap_dev_pin_host (P->dev, nbuf, (uint64_t) ncap);
+                w->text[m] = tj[m].buf = nbuf;
+                w->text_cap[m] = tj[m].cap = ncap;
+              }
+        }
+    }
+  for (int k = 0; k < n_sets; k++)
+    {
+      const int s = (cur_set + k) % n_sets;
+      if (have_pending[s])
+        ck (pending_dev[s], pemap_dev_wait_batch (pending_dev[s], pending[s]));
+      have_pending[s] = 0;
+    }
+  file_done (P, iter, maps1, maps2, current_read, &ts0, &in1, paired ? &in2 : NULL);
+}
+
 static void
 map_one_file (file_worker * w, int iter)
 {
   file_pool *P = w->P;
   const int paired = P->paired, n_sets = P->n_sets;
-  char path[4200];
   /* per set: the batch in flight from it, if any -- its object and ticket */
   int cur_set = 0, have_pending[MAX_SETS] = { 0 };
   uint64_t pending[MAX_SETS] = { 0 };
@@ -595,7 +864,7 @@ map_one_file (file_worker * w, int iter)
       lr_open (&in2, P->names2[iter]);
     size_t cap = 1 << 20, current_read = 0;
     uint32_t *maps1 = (uint32_t *) calloc (cap, sizeof (uint32_t)), *maps2 = paired ? (uint32_t *) calloc (cap, sizeof (uint32_t)) : NULL;
-    struct timespec ts0, ts1;
+    struct timespec ts0;
     clock_gettime (CLOCK_MONOTONIC, &ts0);
     fill_job j1, j2;
     memset (&j1, 0, sizeof j1);
@@ -713,35 +982,7 @@ map_one_file (file_worker * w, int iter)
         ck (dev, pemap_dev_map_batch (dev, r1, l1, r2, l2, nb, ROW_STRIDE, maps1 + (current_read - (size_t) nb),
                                       paired ? maps2 + (current_read - (size_t) nb) : NULL, mt));
       }
-    clock_gettime (CLOCK_MONOTONIC, &ts1);
-    {
-      const double sec = (double) (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0.tv_nsec);
-      printf ("\n pemapper_hip: %ld %s read and mapped in %.3f s (%.2f M reads/s, input parsing included) \n", (long) current_read,
-              paired ? "pairs" : "reads", sec, (paired ? 2.0 : 1.0) * (double) current_read / (sec > 0 ? sec : 1) / 1e6);
-    }
-    printf ("\n Made it out alive, and have started cleanup \n\n");
-    snprintf (path, sizeof path, "%s.mfile", P->names1[iter]);
-    FILE *m = fopen (path, "wb");
-    if (!m)
-      die ("\n Can not open file %s", path);
-    fwrite (maps1, sizeof (uint32_t), current_read, m);
-    fclose (m);
-    if (paired)
-      {
-        snprintf (path, sizeof path, "%s.mfile", P->names2[iter]);
-        m = fopen (path, "wb");
-        if (!m)
-          die ("\n Can not open file %s", path);
-        fwrite (maps2, sizeof (uint32_t), current_read, m);
-        fclose (m);
-        lr_close (&in2);
-      }
-    lr_close (&in1);
-    free (maps1);
-    free (maps2);
-  pthread_mutex_lock (&P->mu);
-  P->tot_pairs += (long) current_read;
-  pthread_mutex_unlock (&P->mu);
+    file_done (P, iter, maps1, maps2, current_read, &ts0, &in1, paired ? &in2 : NULL);
 }
 
 static void *
@@ -756,7 +997,10 @@ file_worker_main (void *arg)
       pthread_mutex_unlock (&P->mu);
       if (iter < 0)
         return NULL;
-      map_one_file (w, iter);
+      if (P->device_parse)
+        map_one_file_parse (w, iter);
+      else
+        map_one_file (w, iter);
     }
 }
 
@@ -1142,6 +1386,19 @@ main (int argc, char *argv[])
     const char *e = getenv ("PEMAPPER_BATCH_PAIRS");
     if (e && atoi (e) >= 1 && atoi (e) <= BATCH_PAIRS)
       pool.batch_pairs = atoi (e);
+  }
+  {
+    /* PEMAPPER_DEVICE_PARSE=1: the rows are made on the device from the files' text.  PEMAPPER_PARSE_BYTES: the text buffer per mate
+       (tests: small enough that pieces end inside records and batches come back short) */
+    const char *e = getenv ("PEMAPPER_DEVICE_PARSE");
+    pool.device_parse = e && atoi (e) == 1;
+    if (pool.device_parse && !pemap_dev_submit_fastq)
+      die ("\n pemapper_hip: PEMAPPER_DEVICE_PARSE=1 needs %s, which this library lacks", "pemap_dev_submit_fastq");
+    pool.parse_bytes = (size_t) PARSE_BYTES_PER_PAIR * (size_t) pool.batch_pairs;
+    if (pool.parse_bytes < ((size_t) 1 << 20))
+      pool.parse_bytes = (size_t) 1 << 20;
+    if ((e = getenv ("PEMAPPER_PARSE_BYTES")) && atol (e) >= 1 && (size_t) atol (e) <= PARSE_BYTES_MAX)
+      pool.parse_bytes = (size_t) atol (e);
   }
   pthread_mutex_init (&pool.mu, NULL);
   file_worker *workers = (file_worker *) calloc ((size_t) n_workers, sizeof (file_worker));

@@ -29,7 +29,24 @@ SYMBOLS = [
     "pecall_dev_sites_stage_records", "pecall_dev_sites_gather", "pecall_dev_sites_merge_ms", "pecall_dev_call_records",
     "pecall_dev_sites_stage_records_guided", "pecall_dev_call_records_guided",
     "pecall_dev_sites_base_text",
+    "pemap_dev_stage_fastq", "pemap_dev_submit_fastq",
 ]
+
+# pemap_fastq.hip.h: bytes of text a block of the line-end scan takes, lines a block of the role and record scans takes, and how
+# many tile counts the one top-level block takes at a time (tests place their inputs at these edges)
+FASTQ_TILE = 4096
+FASTQ_LINE_TILE = 1024
+FASTQ_TOP = 1024
+FASTQ_MAX_TEXT = 1 << 30
+
+
+class FastqResult(C.Structure):
+    """pemap_fastq_result"""
+    _fields_ = [("n", C.c_int32), ("got", C.c_int32 * 2), ("end", C.c_int32 * 2), ("bad_len", C.c_int32 * 2), ("consumed", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        return dict(n=self.n, got=list(self.got), end=list(self.end), bad_len=list(self.bad_len), consumed=list(self.consumed))
+
 
 PILE_DT = np.dtype([("pos", "<u4"), ("c", "<u2", (6,))])
 
@@ -89,6 +106,9 @@ def load_library():
         L.pemap_dev_debug_hits.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.pemap_dev_index_share.argtypes = [vp, vp]
         L.pemap_dev_absorb.argtypes = [vp, vp]
+        fq = [vp, C.c_char_p, u64, i, C.c_char_p, u64, i, i, i, i, i]
+        L.pemap_dev_stage_fastq.argtypes = fq + [C.POINTER(FastqResult)]
+        L.pemap_dev_submit_fastq.argtypes = fq + [vp, vp, vp, C.POINTER(FastqResult), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -214,6 +234,32 @@ class PemapDev:
         self._ck(self.L.pemap_dev_wait_batch(self.h, ticket))
         m1, m2, mt = self._inflight.pop(ticket)[:3]
         return m1, m2, mt
+
+    def stage_fastq(self, text1, text2=None, state1=0, state2=0, trim_start=0, trim_end=0, max_records=1 << 20, stride=288):
+        """stage_reads with the rows made on the device from fastq text (bytes); -> the pemap_fastq_result as a dict"""
+        res = FastqResult()
+        self._ck(self.L.pemap_dev_stage_fastq(self.h, text1, len(text1), state1, text2, 0 if text2 is None else len(text2), state2,
+                                              trim_start, trim_end, max_records, stride, C.byref(res)))
+        if res.n:
+            self._n = res.n
+        return res.as_dict()
+
+    def submit_fastq(self, text1, text2=None, state1=0, state2=0, trim_start=0, trim_end=0, max_records=1 << 20, stride=288):
+        """submit_batch with the same substitution; -> (result dict, ticket), ticket None when the batch holds no pair"""
+        m1 = np.zeros(max_records, np.uint32)
+        m2 = np.zeros(max_records, np.uint32) if self.paired else None
+        mt = np.zeros(max_records, np.int32)
+        res = FastqResult()
+        t = C.c_uint64()
+        self._ck(self.L.pemap_dev_submit_fastq(self.h, text1, len(text1), state1, text2, 0 if text2 is None else len(text2), state2,
+                                               trim_start, trim_end, max_records, stride, _p(m1), _p(m2), _p(mt), C.byref(res), C.byref(t)))
+        if not res.n:
+            return res.as_dict(), None
+        if not hasattr(self, "_inflight"):
+            self._inflight = {}
+        n = res.n
+        self._inflight[t.value] = (m1[:n], None if m2 is None else m2[:n], mt[:n], m1, m2, mt, text1, text2)
+        return res.as_dict(), t.value
 
     def pin_host(self, a):
         self._ck(self.L.pemap_dev_pin_host(self.h, a.ctypes.data, a.nbytes))

@@ -102,6 +102,11 @@ int pemap_dev_index_share (pemap_dev * dst, pemap_dev * src);
 int pemap_dev_set_lookup_replicas (pemap_dev * dev, int n);
 /* how many replicas serve the look-ups now (0 or 8), and the bytes of the multi-position records */
 int pemap_dev_lookup_replicas (pemap_dev * dev, int *n_replicas, uint64_t * record_bytes);
+/* The last launch of the fused seed kernel's first tier (host only, zeros before the first run): persistent one-wave workgroups
+ * per CU asked for (PEMAP_LOOKUP_WAVES or its default), how many the runtime keeps resident on a CU for the launched form with its
+ * dynamic LDS (hipOccupancyMaxActiveBlocksPerMultiprocessor), how many were launched (the smaller of the two, at most four per
+ * SIMD's register bound) and the LDS bytes of one. */
+int pemap_dev_seed_launch (pemap_dev * dev, int *asked, int *resident, int *launched, int *lds_bytes);
 
 /* Device pointers and sizes of the resident arrays: which = 0 pos_index (u32[2^32+1]), 1 mers (u32[n_mers]),
  * 2 genome (u8[genome_size]), 3 contig_starts (u32[n_contigs+1]), 4 pileup counters (six planes A C G T Del Ins of 16-bit

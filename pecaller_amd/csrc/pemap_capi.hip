@@ -112,6 +112,7 @@ struct PmKnobs
   int chunk_pairs;
   int gapless_blocks_per_cu;
   int band, band_waves_per_cu;  // the banded DP (pm_band_kernel) for the problems it is exact for; its waves per CU
+  int first_tier;               // 0 (tests): every end of a chunk goes to the second tier's list, the first tier is not launched
   int tier2_waves;              // persistent waves per CU of the fused seed kernel's second tier (the first tier's big-end list)
   int absorb_staged;            // pemap_dev_absorb: 1 = through the staging buffers even when both objects sit on one device
   size_t absorb_chunk;          // bytes of a staging piece (PEMAP_ABSORB_CHUNK is in KiB): a multiple of 256, at least 256
@@ -137,6 +138,7 @@ static void read_knobs (PmKnobs & k)
   k.lookup_prio = env_int ("PEMAP_LOOKUP_PRIO", 0);
   k.tier2_waves = env_int ("PEMAP_TIER2_WAVES", 3);
   if (k.tier2_waves < 1) k.tier2_waves = 1;
+  k.first_tier = env_int ("PEMAP_FIRST_TIER", 1);
   k.vote_prio = env_int ("PEMAP_VOTE_PRIO", 0);
   k.sw_prio = env_int ("PEMAP_SW_PRIO", 0);
   k.vote_waves = env_int ("PEMAP_VOTE_WAVES", 1024);
@@ -244,6 +246,10 @@ struct pemap_dev
   // two-stream pipeline: the look-up kernel of chunk k+1 (memory stream) runs beside vote/SW/walk of chunk k
   hipStream_t stream2 = nullptr;
   int n_cus = 0;
+  // the fused seed kernel's first tier: workgroups of the form for S segments that the runtime keeps resident on a CU with the
+  // form's LDS (0 = not asked yet), and what the last launch used: the knob, the runtime's answer, workgroups per CU, LDS bytes
+  int seed_resident[32] = { };
+  int seed_launch[4] = { };
   PmChunkCtr *d_chunk_ctr = nullptr;
   std::vector < hipEvent_t > evs;
   int big_grid = 0;
@@ -666,6 +672,15 @@ extern "C" int pemap_dev_lookup_replicas (pemap_dev * d, int *n_replicas, uint64
   *n_replicas = d->n_rep;
   if (record_bytes)
     *record_bytes = d->n_rep ? d->multi_units * 16ull : 0ull;
+  return 0;
+}
+
+extern "C" int pemap_dev_seed_launch (pemap_dev * d, int *asked, int *resident, int *launched, int *lds_bytes)
+{
+  *asked = d->seed_launch[0];
+  *resident = d->seed_launch[1];
+  *launched = d->seed_launch[2];
+  *lds_bytes = d->seed_launch[3];
   return 0;
 }
 
@@ -1167,6 +1182,16 @@ __global__ void pm_nop_kernel ()
 {
 }
 
+// PEMAP_FIRST_TIER=0: the list the first tier would leave had it passed over every end of the chunk
+__global__ void pm_all_big_kernel (uint32_t * list, unsigned *n_list, int n_ends)
+{
+  const int i = (int) (blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < n_ends)
+    list[i] = (uint32_t) i;
+  if (i == 0)
+    *n_list = (unsigned) n_ends;
+}
+
 struct RunCtx
 {
   PmIndex ix;
@@ -1208,6 +1233,10 @@ template < class F > static void with_seg_template (int L, F f)
     }
 }
 
+#ifndef PM_LOOKUP_WAVES_DEFAULT
+#define PM_LOOKUP_WAVES_DEFAULT 12
+#endif
+
 // is the seed stage of this run the fused kernel (pm_seed4_kernel: look-ups and vote of a read-end in one wave)?
 static bool pm_fused (const pemap_dev * d)
 {
@@ -1237,29 +1266,40 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
   // kernel makes the stamp the moment the look-up kernel can start, so that LOOKUP_BEGIN..LOOKUP_END is the kernel's own duration)
   hipLaunchKernelGGL (pm_nop_kernel, dim3 (1), dim3 (1), 0, st);
   hipEventRecord (ev[PM_EV_LOOKUP_BEGIN], st);
-  // PEMAP_LOOKUP_WAVES=n: n persistent one-wave workgroups per CU (pm_seed4_kernel: 14.6 KB of LDS and 128 VGPRs a wave).  The kernel
-  // itself keeps gaining with n (5.06 / 4.53 / 4.05 / 3.84 ms per launch with 7 / 8 / 9 / 10, profiles/r04_ab_sweeps.txt) while the other
-  // stream's DP kernels lose the SIMDs' registers to it.  Default 10 since the pileup's plane 0 is kept as differences: with the long
-  // pile stage 10 was the slower setting (round 4: 21.3 ms per step against 20.7; the parent of round 9: 19.74 against 19.35), behind
-  // the short one, launched with four blocks per CU, it is the faster one (18.57 against 19.3, profiles/r09_ab_sweeps.txt)
-  int lw = d->kn.lookup_waves > 0 ? d->kn.lookup_waves : 10;
+  // PEMAP_LOOKUP_WAVES=n: n persistent one-wave workgroups per CU (pm_seed4_kernel: 12,784 bytes of LDS and 128 VGPRs a wave).  The
+  // kernel itself keeps gaining with n (5.06 / 4.53 / 4.05 / 3.84 ms per launch with 7 / 8 / 9 / 10, profiles/r04_ab_sweeps.txt) while the
+  // other stream's DP kernels lose the SIMDs' registers to it.  Ten was the most 14,976 bytes admitted; twelve is what
+  // profiles/r13_ab_sweeps.txt found with the smaller struct (10: 110.0 M reads/s; 11 and 12: 115.4 and 115.3 .. 116.0, not told apart)
+  const int lw_asked = d->kn.lookup_waves > 0 ? d->kn.lookup_waves : PM_LOOKUP_WAVES_DEFAULT;
+  int lw = lw_asked;
   if (pm_fused (d))
     {
       // (no more workgroups than are resident at once: a workgroup owns its first ends by its number, and one that starts when
-      // another ends -- at the launch's end -- would be the launch's tail)
+      // another ends -- at the launch's end -- would be the launch's tail.  How many are is the runtime's answer for the form and
+      // its dynamic LDS, asked once per form)
       size_t lds = 0;
-      int per_simd = 2;
+      int per_simd = 2, fit = 0;
       with_seg_template (c.L, [&] (auto sm)
       {
         lds = sizeof (PmSeed4Shared < sm.value, 0 >);
         if (sm.value <= 10)
           per_simd = PM_S4_WAVES_PER_EU;
+        int &res = d->seed_resident[sm.value];
+        if (res <= 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor (&res, pm_seed4_kernel < sm.value, 0 >, 64, lds) != hipSuccess)
+          res = 0;
+        fit = res;
       });
-      const int fit = (int) ((size_t) 160 * 1024 / lds);
+      if (fit < 1)
+        fit = 1;
+      const int resident = fit;
       if (lw > fit)
         lw = fit;
       if (lw > 4 * per_simd)
         lw = 4 * per_simd;
+      d->seed_launch[0] = lw_asked;
+      d->seed_launch[1] = resident;
+      d->seed_launch[2] = lw;
+      d->seed_launch[3] = (int) lds;
     }
   int lgrid = lw * d->n_cus;
   if (lgrid > c.b.n_ends)
@@ -1285,8 +1325,11 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
   const int grid2 = d->kn.tier2_waves * d->n_cus;
   with_seg_template (c.L, [&] (auto sm)
   {
-    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed4_kernel < sm.value, 0 >), dim3 (lgrid), dim3 (64), sizeof (PmSeed4Shared < sm.value, 0 >), st, c.ix, c.b,
-                        c.prm, H, L, (const uint32_t *) nullptr, (const unsigned *) nullptr, lprio);
+    if (d->kn.first_tier)
+      hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed4_kernel < sm.value, 0 >), dim3 (lgrid), dim3 (64), sizeof (PmSeed4Shared < sm.value, 0 >), st, c.ix, c.b,
+                          c.prm, H, L, (const uint32_t *) nullptr, (const unsigned *) nullptr, lprio);
+    else if (c.b.n_ends > 0)    // (a chunk's ends fit the list: run_slice sizes it by the chunk)
+      hipLaunchKernelGGL (pm_all_big_kernel, dim3 ((unsigned) (c.b.n_ends + 255) / 256), dim3 (256), 0, st, L.big_list, L.n_big, c.b.n_ends);
     hipEventRecord (ev[PM_EV_LOOKUP_END], st);
     hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed4_kernel < sm.value, 1 >), dim3 (grid2), dim3 (64), sizeof (PmSeed4Shared < sm.value, 1 >), st, c.ix, c.b,
                         c.prm, H, L2, (const uint32_t *) L.big_list, (const unsigned *) L.n_big, lprio);
@@ -1406,9 +1449,9 @@ template < int W, int LPA, bool DIRS > static auto launch_cascade (pemap_dev * d
   if (DIRS)
     {
       // The rule's kernel and the NEXT chunk's seed kernel are launched at the same moment (both wait for this chunk's seed kernel), and
-      // whichever gets its waves onto the SIMDs first keeps them: the seed kernel's persistent waves (pm_seed4_kernel < 10, 0 >, ten per
-      // CU) take 128 registers and 15,360 bytes of LDS each, this kernel's 109 to 115 registers (four fill a SIMD's 512) and 1 KB of LDS
-      // with short rows.  Beside all ten seed waves a CU has room for six of these waves by registers (1 + 1 + 2 + 2) and for eight
+      // whichever gets its waves onto the SIMDs first keeps them: the seed kernel's persistent waves (pm_seed4_kernel < 10, 0 >, twelve per
+      // CU) take 128 registers and 12,800 bytes of LDS each, this kernel's 109 to 115 registers (four fill a SIMD's 512) and 1 KB of LDS
+      // with short rows.  Beside ten seed waves (the default up to round 12; twelve leave a wave per SIMD) a CU has room for six of these waves by registers (1 + 1 + 2 + 2) and for eight
       // to ten by LDS (allocated in units of 1,280 or of 512 bytes); where these come first, sixteen of them hold a CU's registers
       // until they end.  (Until round 10 the kernel had one form, compiled for six waves per SIMD -- 80 registers and 96 to 112 bytes
       // of scratch per lane -- whose 1.7 KB of LDS admitted four or five beside ten seed waves.)

@@ -6,10 +6,11 @@
 // proportion to its waves per CU (a wave waits in half of its cycles), but 19.6 KB of LDS admit 8 waves and 168 VGPRs leave a SIMD that
 // hosts two of them room for ONE wave of the other stream's DP kernels (120-128 VGPRs each) -- the two streams traded time one for
 // one.  This form is built for footprint first:
-//   * ONE list for both strands (the strand is a bit of the position's tag): 1,536 positions for reads of up to 160 bases where the
+//   * ONE list for both strands (the strand is a bit of the position's tag): 1,424 positions for reads of up to 160 bases where the
 //     third form held 2 x 1,024, and a read-end overflows when the two strands TOGETHER do -- a repeat usually fills one strand;
-//   * the vote's tables overlay one another (the survivors' list lies in the bin table it was made from), 2-bit bases packed;
-//     13.6 KB per wave where the third form took 19.6;
+//   * the vote's tables overlay one another (the survivors' list lies in the bin table it was made from), the hit list and the
+//     per-segment counts lie in their back, the read's 2-bit codes are bit planes in registers (no byte array): 12,784 bytes per
+//     wave where the third form took 19.6 KB -- twelve waves on a CU's 160 KB;
 //   * at most 128 VGPRs (__launch_bounds__ (64, 4)) and no scratch: three seed waves and a DP wave fit a SIMD;
 //   * the bin table is indexed by the diagonal bin itself (mod its size; strand 1 half a table further), not by a hash of it:
 //     the three bins around a position are three neighbouring cells, read with one LDS instruction where the third form made three
@@ -35,7 +36,7 @@
 #include "pemap_wave.hip.h"
 
 #ifndef PM_S4_KCAP
-#define PM_S4_KCAP 1536         // positions of BOTH strands the list holds (reads of up to 160 bases, first tier)
+#define PM_S4_KCAP 1424         // positions of BOTH strands the list holds (reads of up to 160 bases, first tier): 12,784 bytes a wave, 12 waves per CU (1,536: 13,344 and 11)
 #endif
 #ifndef PM_S4_KCAP_LONG
 #define PM_S4_KCAP_LONG 2048    // ... for reads of more than 160 bases (3,072: 28 KB of LDS and 5 waves per CU at 16 segments; 2,048: 22.9 KB and 7 -- 2 x 245 bases 44.4 -> 41.3 ms per step, a quarter more ends for the second tier)
@@ -54,6 +55,9 @@
 #define PM_S4_SEG(t) ((t) & 31u)
 #define PM_S4_STRAND(t) (((t) >> 5) & 1u)
 
+// v[lane] = s, the other lanes of v as they were (s wave-uniform, lane a constant)
+#define pm_s4_writelane(v, s, lane) asm ("v_writelane_b32 %0, %1, %2" : "+v" (v) : "s" (s), "n" (lane))
+
 template < int SMAX, int TIER > struct __align__ (16) PmSeed4Shared
 {
   static constexpr int NSEG = 2 * SMAX;
@@ -66,45 +70,77 @@ template < int SMAX, int TIER > struct __align__ (16) PmSeed4Shared
   static constexpr int CELL_WORDS = ((CELL16 ? NH / 2 : NH) + 2 + 3) & ~3;       // cell c is stored at index c + 1: a pad cell either side
   static constexpr int CAND_WORDS = (NH / 32 + 1 + 3) & ~3;
   static_assert (KCAP >= 2 * 49 * SMAX + 64, "the list holds an end's look-ups while they are decoded");
+  struct Vote                           // the vote's tables
+  {
+    union
+    {
+      uint32_t cell[CELL_WORDS];        // bit s of cell c: a position of segment s has its diagonal bin = c (mod NH; strand 1: + NH / 2)
+      struct                            // once the anchors' counts are known the cells are dead: the surviving anchors lie here
+      {
+        uint2 sv[RCAP];                 // x = key, y = segment | tot_found << 8 (strand 0 from the front, 1 from the back)
+        uint16_t order[RCAP];
+      } w;
+    } c;
+    uint32_t candbit[CAND_WORDS];       // bit c + 1: a candidate anchor's bin
+    uint2 r[RCAP];                      // positions next to candidates: x = key, y = segment | strand << 5 | candidate << 6
+  };
+  struct Tails                          // while the records are read: the work list of their tails
+  {
+    uint32_t src[128];                  // per record with more than 3 positions: word in `multi` ...
+    int32_t dst[128];                   // ... and list slot of its 4th position, both minus the record's place in the flattened tail
+    uint8_t sg[128];                    // its tag (segment | strand << 5)
+    uint8_t mark[KCAP];                 // flattened tail: record number + 1 at the record's first element, 0 elsewhere
+  };
+  // What outlives an end's vote lies in the vote's tables from byte LIVE on, beyond the lines and the tails' work list: the walk's
+  // hits (carried to flush_out in the middle of the next iteration, whose phases A to C touch only `lines` and `x`) and, beside
+  // them, the per-segment counts of phases B and C.  Which table that is differs by form -- the back of r[] for < 10, 0 >, cells
+  // and candidate bits where the list of the tails is the larger (< 10, 1 >: from byte 6,848, inside the cells) -- and what holds
+  // for every form is this: the walk, the only writer of the hits, reads of the tables only the anchors (sv and order, the
+  // first ANCHORS bytes, below LIVE by the static_assert on Over); the vote writes cells, candidate bits and r[] only after
+  // flush_out has emptied the hits; the counts are dead before the vote starts.  NKEEP hits fit there -- all PM_MAX_HITS of
+  // them in every form but the first tier for reads of up to 160 bases (76); the hits beyond NKEEP of an end with more tied
+  // hits wait, during its walk only, behind the anchors and below LIVE (Over) and leave for HBM at the walk's end.
+  static constexpr int LIVE = (int) (sizeof (uint32_t) * SMAX * 128 > sizeof (Tails) ? sizeof (uint32_t) * SMAX * 128 : sizeof (Tails));
+  static constexpr int KEEP_ROOM = ((int) sizeof (Vote) - LIVE - (int) sizeof (int) * (NSEG + 2)) / 6;
+  static constexpr int NKEEP = KEEP_ROOM < PM_MAX_HITS ? KEEP_ROOM : PM_MAX_HITS;
+  static constexpr int NOVER = PM_MAX_HITS - NKEEP;
+  static constexpr int ANCHORS = (int) (sizeof (uint2) + sizeof (uint16_t)) * RCAP;
+  static_assert (NKEEP >= 64, "the back of the vote's tables holds a useful share of the hit list");
+  struct Keep
+  {
+    uint8_t live[LIVE];
+    int seg_cnt[NSEG + 2];
+    uint32_t hits[NKEEP];
+    uint16_t hits_off[NKEEP];           // segment offset | strand << 15
+  };
+  struct Over
+  {
+    uint8_t anchors[ANCHORS];
+    uint32_t hits[NOVER + 1];
+    uint16_t hits_off[NOVER + 1];
+  };
   union
   {
     uint32_t lines[SMAX * 128];         // ONE strand's SMAX x 8 lines of 16 entries (the other strand's wait in registers) ...
-    struct                              // ... the vote's tables afterwards
-    {
-      union
-      {
-        uint32_t cell[CELL_WORDS];      // bit s of cell c: a position of segment s has its diagonal bin = c (mod NH; strand 1: + NH / 2)
-        struct                          // once the anchors' counts are known the cells are dead: the surviving anchors lie here
-        {
-          uint2 sv[RCAP];               // x = key, y = segment | tot_found << 8 (strand 0 from the front, 1 from the back)
-          uint16_t order[RCAP];
-        } w;
-      } c;
-      uint32_t candbit[CAND_WORDS];     // bit c + 1: a candidate anchor's bin
-      uint2 r[RCAP];                    // positions next to candidates: x = key, y = segment | strand << 5 | candidate << 6
-    } v;
-    struct                              // ... and in between, while the records are read: the work list of their tails
-    {
-      uint32_t src[128];                // per record with more than 3 positions: word in `multi` ...
-      int32_t dst[128];                 // ... and list slot of its 4th position, both minus the record's place in the flattened tail
-      uint8_t sg[128];                  // its tag (segment | strand << 5)
-      uint8_t mark[KCAP];               // flattened tail: record number + 1 at the record's first element, 0 elsewhere
-    } x;
+    Vote v;                             // ... the vote's tables afterwards ...
+    Tails x;                            // ... and in between, while the records are read
+    Keep k;
+    Over o;
   } a;
+  static_assert (sizeof (Keep) <= sizeof (Vote), "the kept hits lie inside the vote's tables");
+  static_assert (ANCHORS % 4 == 0 && sizeof (Over) <= LIVE, "the hits beyond NKEEP lie between the anchors and the kept ones");
   // diagonal keys m + PM_DIAG_BIAS - offset(segment), from the front; while the entries are decoded the entries that point to a
   // record wait at the back (an end has at most 2 x 49 x S look-ups, each of them one or the other)
   uint32_t key[KCAP];
   uint8_t tag[KCAP];
-  uint32_t hits[PM_MAX_HITS];
-  uint16_t hits_off[PM_MAX_HITS];       // segment offset | strand << 15
-  int seg_cnt[NSEG + 2];
-  uint8_t seq[2][16 * SMAX + 8];        // 2-bit codes of the end whose k-mers are being formed, a byte each
 };
 
 static_assert (sizeof (PmSeed4Shared < 19, 1 >) <= 65536, "dynamic LDS of a launch without an attribute");
-// a first-tier wave's LDS for reads of up to 160 bases: allocated as 15,360 bytes, so ten waves leave 10,240 of a CU's 163,840 bytes
-// to the other stream's kernels (tests/test_kernel_resources_cpu.py reads this constant: the struct does not grow unnoticed)
-#define PM_S4_SHARED_10_0_BYTES 14976
+// a first-tier wave's LDS for reads of up to 160 bases: the tables (5,664 bytes) and the list (5 bytes a position).  A build with
+// another PM_S4_KCAP names its own size (tests/test_kernel_resources_cpu.py reads this constant: the struct does not grow unnoticed)
+#ifndef PM_S4_SHARED_10_0_BYTES
+#define PM_S4_SHARED_10_0_BYTES 12784
+#endif
 static_assert (sizeof (PmSeed4Shared < 10, 0 >) == PM_S4_SHARED_10_0_BYTES, "the first tier's LDS per wave");
 extern __shared__ __align__ (16) uint8_t pm_seed4_lds[];
 
@@ -187,19 +223,32 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
     len_out = len;
     end_out = __builtin_amdgcn_readfirstlane (rend);
     int isn = 0;
+    // fill_cv_mat / convert_ct (pemapper.c:2375-2383, 2292-2300) of the read and of its reverse complement as bit planes, lane =
+    // base: the low and the high bit of pm_code_flat (c) and of pm_code_flat (pm_rc_flat (c)) -- the complement's code at the
+    // base's own place -- by ballot.  Lower case counts for the read (pm_code_flat folds it) and not for the complement
+    // (pm_rc_flat answers 'N' to it); the bisulfite C -> T applies to an upper-case C of either, so on the complement to a G of the
+    // read; every other letter is code 0.  Word w of plane q goes to lane 16 q + w of pv (q = 0 / 1: the read's low / high bit,
+    // 2 / 3: the complement's), no LDS.
+    uint32_t pv = 0u;
 #pragma unroll
     for (int t = 0; t < NBT; t++)
       {
         const int i = lane + 64 * t;
-        const uint8_t c = rb[t];
-        if (i < len)
-          {
-            // fill_cv_mat / convert_ct (pemapper.c:2375-2383, 2292-2300) of the read and of its reverse complement
-            sh.seq[0][i] = (uint8_t) pm_code_flat (c, prm.bisulfite);
-            sh.seq[1][len - 1 - i] = (uint8_t) pm_code_flat (pm_rc_flat (c), prm.bisulfite);
-          }
+        const uint32_t c = rb[t], lc = c | 0x20u;
+        const bool bis = prm.bisulfite != 0;
+        const unsigned long long f_lo = __ballot (lc == 'c' || lc == 't'), f_hi = __ballot (lc == 'g' || lc == 't' || (bis && c == 'C'));
+        const unsigned long long r_lo = __ballot (c == 'A' || c == 'G'), r_hi = __ballot (c == 'A' || c == 'C' || (bis && c == 'G'));
+        pm_s4_writelane (pv, (uint32_t) f_lo, 2 * t);
+        pm_s4_writelane (pv, (uint32_t) (f_lo >> 32), 2 * t + 1);
+        pm_s4_writelane (pv, (uint32_t) f_hi, 16 + 2 * t);
+        pm_s4_writelane (pv, (uint32_t) (f_hi >> 32), 16 + 2 * t + 1);
+        pm_s4_writelane (pv, (uint32_t) r_lo, 32 + 2 * t);
+        pm_s4_writelane (pv, (uint32_t) (r_lo >> 32), 32 + 2 * t + 1);
+        pm_s4_writelane (pv, (uint32_t) r_hi, 48 + 2 * t);
+        pm_s4_writelane (pv, (uint32_t) (r_hi >> 32), 48 + 2 * t + 1);
         isn += (int) __popcll (__ballot (i < len && c == 'N'));
       }
+    static_assert (2 * NBT < 16, "a plane's words and a zero word behind them fit 16 lanes");
     int cuts = len / idepth;    // pemapper.c:1573-1587
     if (len % idepth == 0)
       cuts--;
@@ -207,21 +256,33 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
       cuts = SMAX - 1;
     cuts = __builtin_amdgcn_readfirstlane (cuts);       // (integer division is done by the vector unit)
     const int S = cuts + 1;
-    pm_wave_sync ();
     between ();
     if (isn >= __builtin_amdgcn_readfirstlane (1 + len / 10))
       return 0;
-    if (lane < 2 * S)
-      {
-        const int strand = lane >= S ? 1 : 0, seg = lane - strand * S;
-        const int off = (seg < cuts || cuts == 0) ? seg * idepth : len - idepth;
-        const uint8_t *p = &sh.seq[strand][off];
-        uint32_t k = 0;
-#pragma unroll
-        for (int i = 0; i < 16; i++)
-          k = (k << 2) + p[i];
-        kmer_out = k;
-      }
+    {
+      // lane (strand, segment): the 16 bases of its k-mer are 16 neighbouring bits of its strand's planes, from bit `from` on -- the
+      // segment's offset in the read, or, on the reverse strand, the place of the window's LAST base (base n of the window is base
+      // len - 1 - off - n of the read: already most significant first, the forward strand's window is bit-reversed).  The two words
+      // around `from` come from pv's lanes (every lane takes part: a permute reads only active lanes), the planes' 16 bits each are
+      // interleaved by a perfect shuffle
+      const int strand = (lane >= S && lane < 2 * S) ? 1 : 0, seg = lane < 2 * S ? lane - strand * S : 0;
+      const int off = (seg < cuts || cuts == 0) ? seg * idepth : len - idepth;
+      const int from = min (max (strand ? len - 16 - off : off, 0), 64 * NBT - 16);
+      const int at = 4 * (32 * strand + (from >> 5));
+      const uint32_t a0 = (uint32_t) __builtin_amdgcn_ds_bpermute (at, (int) pv), a1 = (uint32_t) __builtin_amdgcn_ds_bpermute (at + 4, (int) pv);
+      const uint32_t b0 = (uint32_t) __builtin_amdgcn_ds_bpermute (at + 64, (int) pv), b1 = (uint32_t) __builtin_amdgcn_ds_bpermute (at + 68, (int) pv);
+      const uint32_t lo = __builtin_amdgcn_alignbit (a1, a0, (uint32_t) from & 31u) & 0xFFFFu, hi = __builtin_amdgcn_alignbit (b1, b0, (uint32_t) from & 31u) & 0xFFFFu;
+      uint32_t x = strand ? (lo | (hi << 16)) : __brev (hi | (lo << 16));
+      uint32_t t = (x ^ (x >> 8)) & 0x0000FF00u;
+      x ^= t ^ (t << 8);
+      t = (x ^ (x >> 4)) & 0x00F000F0u;
+      x ^= t ^ (t << 4);
+      t = (x ^ (x >> 2)) & 0x0C0C0C0Cu;
+      x ^= t ^ (t << 2);
+      t = (x ^ (x >> 1)) & 0x22222222u;
+      x ^= t ^ (t << 1);
+      kmer_out = lane < 2 * S ? x : kmer_out;
+    }
     // register r holds the lines of (strand, segment) 2 r (lanes 0..31) and 2 r + 1 (lanes 32..63), 8 each: wanted iff r < S
     const int p = (lane >> 2) & 7;
     const uint32_t *rep_lane = ix.rep + ((size_t) p << 32) + (size_t) ((lane & 3) * 4);
@@ -265,13 +326,14 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
       {
         if (lane == 0)
           h.n_hits[e_out] = tot_out;
-        for (int t = lane; t < tot_out; t += 64)
+        // (the hits beyond NKEEP left at the end of the walk: put_over)
+        for (int t = lane; t < min (tot_out, SH::NKEEP); t += 64)
           {
             // (a 32-bit index -- task ids are end * 200 + hit in 32 bits everywhere -- added to the arrays' scalar bases: with a 64-bit
             // one the compiler kept per-lane base addresses alive around the whole loop, in scratch)
             const uint32_t o = (uint32_t) e_out * (uint32_t) PM_MAX_HITS + (uint32_t) t;
-            const uint32_t m = sh.hits_off[t];
-            h.spot[o] = sh.hits[t];
+            const uint32_t m = sh.a.k.hits_off[t];
+            h.spot[o] = sh.a.k.hits[t];
             h.nn[o] = (int16_t) (m & 0x7FFFu);
             h.orient[o] = (uint8_t) (m >> 15);
           }
@@ -378,7 +440,7 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
           PM_S4_T (2);
           decode_strand (std::integral_constant < int, 1 > { });
           if (lane < SH::NSEG + 2)
-            sh.seg_cnt[lane] = cntv;
+            sh.a.k.seg_cnt[lane] = cntv;
           pm_wave_sync ();
           PM_S4_T (3);
           // ---- C: the records: {count, positions...} in 16-byte units; the first unit answers for buckets of up to 3 positions.
@@ -405,7 +467,7 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
             const uint32_t bias = (uint32_t) (PM_DIAG_BIAS - off);
             if (wr)
               {
-                atomicAdd (&sh.seg_cnt[(int) PM_S4_STRAND (tg) * S + seg], (int) c);
+                atomicAdd (&sh.a.k.seg_cnt[(int) PM_S4_STRAND (tg) * S + seg], (int) c);
                 uint32_t *kk = &sh.key[dst];
                 uint8_t *tt = &sh.tag[dst];
                 kk[0] = hdr.y + bias;
@@ -531,7 +593,7 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
 #endif
           // pemapper.c:2200-2207: a strand is not searched when every one of its segments holds more than max_hits positions
           {
-            const int c = lane < 2 * S ? sh.seg_cnt[lane] : 10000;
+            const int c = lane < 2 * S ? sh.a.k.seg_cnt[lane] : 10000;
             cmin0 = pm_wave_min (lane < S ? c : 10000);
             cmin1 = pm_wave_min (lane >= S ? c : 10000);
           }
@@ -763,6 +825,26 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
                 }
               pm_wave_sync ();
               PM_S4_T (9);
+              // hit t of the walk: in the back of the tables, or (first tier, reads of up to 160 bases) behind the anchors from NKEEP on
+              auto put_hit = [&] (int t, uint32_t ml, uint32_t off_strand)
+              {
+                if (SH::NOVER == 0 || t < SH::NKEEP)
+                  {
+                    sh.a.k.hits[t] = ml;
+                    sh.a.k.hits_off[t] = (uint16_t) off_strand;
+                  }
+                else
+                  {
+                    sh.a.o.hits[t - SH::NKEEP] = ml;
+                    sh.a.o.hits_off[t - SH::NKEEP] = (uint16_t) off_strand;
+                  }
+              };
+              auto hit_diag = [&] (int t)->uint32_t
+              {
+                if (SH::NOVER == 0 || t < SH::NKEEP)
+                  return sh.a.k.hits[t] - (uint32_t) (sh.a.k.hits_off[t] & 0x7FFFu);
+                return sh.a.o.hits[t - SH::NKEEP] - (uint32_t) (sh.a.o.hits_off[t - SH::NKEEP] & 0x7FFFu);
+              };
               bool go_on = true;
               for (int strand = 0; strand < 2 && go_on; strand++)
                 {
@@ -830,10 +912,7 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
                             {
                               min_match = tfl;
                               if (lane == 0)
-                                {
-                                  sh.hits[0] = ml;
-                                  sh.hits_off[0] = (uint16_t) (off_a | (strand << 15));
-                                }
+                                put_hit (0, ml, (uint32_t) (off_a | (strand << 15)));
                               tot = 1;
                               pm_wave_sync ();
                               cnd &= __ballot (tf >= min_match);     // candidates below the new best would fall through both tests
@@ -845,15 +924,12 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
                                   const uint32_t diag = ml - (uint32_t) off_a;        // unsigned, pemapper.c:2268
                                   bool dup = false;
                                   for (int k = lane; k < tot; k += 64)
-                                    if (sh.hits[k] - (uint32_t) (sh.hits_off[k] & 0x7FFFu) == diag)
+                                    if (hit_diag (k) == diag)
                                       dup = true;
                                   if (!__any (dup))
                                     {
                                       if (lane == 0)
-                                        {
-                                          sh.hits[tot] = ml;
-                                          sh.hits_off[tot] = (uint16_t) (off_a | (strand << 15));
-                                        }
+                                        put_hit (tot, ml, (uint32_t) (off_a | (strand << 15)));
                                       tot++;
                                       pm_wave_sync ();
                                     }
@@ -872,6 +948,17 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
                   go_on = more;
                   pm_wave_sync ();
                 }
+              // put_over: an end with more tied hits than the back of the tables holds (rare) stores the rest here; flush_out
+              // writes its first NKEEP and its count as for every end
+              if constexpr (SH::NOVER > 0)
+                for (int t = SH::NKEEP + lane; t < tot; t += 64)
+                  {
+                    const uint32_t o = (uint32_t) e * (uint32_t) PM_MAX_HITS + (uint32_t) t;
+                    const uint32_t m = sh.a.o.hits_off[t - SH::NKEEP];
+                    h.spot[o] = sh.a.o.hits[t - SH::NKEEP];
+                    h.nn[o] = (int16_t) (m & 0x7FFFu);
+                    h.orient[o] = (uint8_t) (m >> 15);
+                  }
             }
         }
       PM_S4_T (10);

@@ -29,7 +29,7 @@ SYMBOLS = [
     "pecall_dev_sites_stage_records", "pecall_dev_sites_gather", "pecall_dev_sites_merge_ms", "pecall_dev_call_records",
     "pecall_dev_sites_stage_records_guided", "pecall_dev_call_records_guided",
     "pecall_dev_sites_base_text",
-    "pemap_dev_stage_fastq", "pemap_dev_submit_fastq",
+    "pemap_dev_stage_fastq", "pemap_dev_submit_fastq", "pemap_dev_seed_launch",
 ]
 
 # pemap_fastq.hip.h: bytes of text a block of the line-end scan takes, lines a block of the role and record scans takes, and how
@@ -78,6 +78,8 @@ def load_library():
         L.pemap_dev_index_commit.argtypes = [vp]
         L.pemap_dev_set_lookup_replicas.argtypes = [vp, i]
         L.pemap_dev_lookup_replicas.argtypes = [vp, C.POINTER(i), C.POINTER(u64)]
+        if hasattr(L, "pemap_dev_seed_launch"):     # (PEMAP_LIB may name an older build, for A/B runs)
+            L.pemap_dev_seed_launch.argtypes = [vp] + [C.POINTER(i)] * 4
         L.pemap_dev_buffer.argtypes = [vp, i, C.POINTER(vp), C.POINTER(u64)]
         L.pemap_dev_index_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i), C.POINTER(i)]
         L.pemap_dev_read_buffer.argtypes = [vp, i, u64, vp, u64]
@@ -183,6 +185,12 @@ class PemapDev:
         b = C.c_uint64(0)
         self._ck(self.L.pemap_dev_lookup_replicas(self.h, C.byref(n), C.byref(b)))
         return n.value, b.value
+
+    def seed_launch(self):
+        """the fused seed kernel's last first-tier launch: dict(asked, resident, launched, lds_bytes), waves per CU"""
+        v = [C.c_int(0) for _ in range(4)]
+        self._ck(self.L.pemap_dev_seed_launch(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("asked", "resident", "launched", "lds_bytes"), (x.value for x in v)))
 
     def index_info(self):
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_int()

@@ -245,6 +245,10 @@ int pemap_dev_absorb (pemap_dev * dst, pemap_dev * src);
 /* out13: total_reads, total_bases, total_dist, no_dists, mate_counts[0..8] */
 int pemap_dev_summary (pemap_dev * dev, long *out13);
 
+/* Persistent waves of a launch of the full DP (CUs x PEMAP_SW_WAVES_PER_CU), each of which works on 64 / lanes-per-alignment problems
+ * at a time.  Without PEMAP_BAND_GATE a chunk of no more read-ends than one pass of this grid takes problems is routed by x <= 6 alone. */
+int pemap_dev_sw_grid (pemap_dev * dev);
+
 /* Counters the reference does not have, summed over the last run --
  * stats[0] = read-ends, [1] = positions gathered from .mdx (P), [2] = SW problems scored (H), [3] = SW problems
  * scored with direction nibbles (single-hit ends + re-scored winners), [4] = DP cells without nibbles, [5] = DP cells
@@ -258,11 +262,14 @@ int pemap_dev_summary (pemap_dev * dev, long *out13);
  *        for the single-hit ends, of [3]; [14] = band cells computed (not part of [4], [5]).
  * [16] = of [8], the alignments whose traceback was followed cell by cell; the others are known to be plain diagonals (decided
  *        without the DP, or banded with a traceback that never leaves the start cell's diagonal) and go to the pileup as such.
+ * [17] = of [13], the problems without a diagonal of at most 6 mismatches that two diagonals and one gap admit to the band
+ *        (PEMAP_BAND_GATE: 1 in every chunk, 0 in none -- they are scored by the full DP as before; unset, in the chunks that hold
+ *        more read-ends than one pass of the full DP's grid takes problems, see pemap_dev_sw_grid).
  * times_ms[0..7] = seed stage (look-up + vote), SW single-hit (with nibbles), SW multi-hit, select, SW re-score,
  * walk+pileup, look-up kernel alone, vote kernel alone (the list-mode remainder of the big read-ends and the emit kernel count
  * towards [0] only): kernel durations from HIP events on the object's streams, summed over the run's chunks (the streams of
  * the pipeline overlap in time, so their sum exceeds the wall time). */
-int pemap_dev_run_stats (pemap_dev * dev, uint64_t * stats17, float *times_ms8);
+int pemap_dev_run_stats (pemap_dev * dev, uint64_t * stats18, float *times_ms8);
 
 /* Debug/parity taps: per read-end hit lists and per-hit SW results of the last run.
  * n_hits[n_ends]; the other arrays are [n_ends][PEMAP_MAX_HITS]. Any pointer may be NULL. end = 2*pair + mate in paired mode. */

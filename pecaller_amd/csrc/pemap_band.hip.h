@@ -24,9 +24,16 @@
 //     the band (else, again, a path outside would tie the optimum).  Every comparison the traceback makes along the optimal path
 //     comes out the same.
 // Cells outside the band that this kernel happens to compute (its rectangle of 32 diagonals is a superset of [-K, D + K] when the
-// window is clipped) only add real paths; cells it does not compute count as -infinity.  pm_gapless_kernel sends a problem here
-// when its rule cannot decide it, the whole read lies inside the window on at least one diagonal, and the best diagonal has at
-// most PM_BAND_MAXX mismatches; everything else (reads with a real indel, mostly) goes to the full DP (pm_sw_kernel).
+// window is clipped) only add real paths; cells it does not compute count as -infinity.
+// The argument above uses the diagonal with x mismatches for one thing only, the PREMISE "the optimum is at least mm - 8": any
+// alignment inside the matrix that loses at most 8 against a perfect one gives it, with the same margin of 5/36 to every path that
+// leaves the band.  pm_gapless_kernel sends a problem here when its rule cannot decide it and one of two lower bounds reaches the
+// premise: (i) the best diagonal that holds the whole read has at most PM_BAND_MAXX mismatches (4 x / 3 <= 8); (ii) an explicit
+// alignment with one gap -- a prefix of the read on diagonal d1 with at most i mismatches, a deletion of d2 - d1 reference bases or
+// an insertion of d1 - d2 <= K read bases, the rest of the read on diagonal d2 with at most j mismatches, d1 and d2 in 0 .. D --
+// loses at most 8: 2 + (b-1)/36 + 4 (i+j)/3 for the deletion, b more for the insertion (the integer form and what the kernel knows
+// of a diagonal: beside PM_BAND_MAXX_ in pemap_sw.hip.h).  Such a path lies on diagonals 0 .. D, inside the band.  Everything else
+// (long insertions, two gaps, gaps beside many mismatches, reads that hang over the window) goes to the full DP (pm_sw_kernel).
 //
 // State per diagonal b = d + K at the column just finished: M3[b] = max (S0, S1, S2) of its cell (the diagonal predecessor of
 // the next column's cell), E2[b] = max (S0 - go, S2 - ge) of its cell = S2 of the cell to its right (one diagonal down).  S1
@@ -43,8 +50,8 @@
 // A quarter of the chain per wave, four times the waves (~4 per SIMD), 70 registers instead of 256.  The arithmetic of a cell,
 // the order of the last column's scan (rows ascending: lane 0's cells, then lane 1's ...) and the slab's layout are unchanged.
 //
-// When the traceback is the diagonal (DIRS only).  A problem is sent here because the read lies whole on one diagonal with a few
-// mismatches, and its traceback is almost always mm diagonal steps in plane 0 -- which pm_pile_kernel can apply without a recorded
+// When the traceback is the diagonal (DIRS only).  A problem sent here by bound (i) lies whole on one diagonal with a few
+// mismatches (one sent by bound (ii) holds a gap and is walked), and its traceback is almost always mm diagonal steps in plane 0 -- which pm_pile_kernel can apply without a recorded
 // walk, as it does for the problems pm_gapless_kernel decides (PM_GAPLESS).  This kernel can tell: diagonal b = 8 q + c is nibble
 // 7 - c of lane q's direction dword in EVERY column, so the OR of a lane's dwords over its columns holds, per diagonal, the OR of
 // the nibbles of all its cells (one instruction per step).  pm_walk_kernel, started in plane k = 0 at (i_b, mm), steps to

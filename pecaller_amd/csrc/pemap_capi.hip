@@ -112,6 +112,8 @@ struct PmKnobs
   int chunk_pairs;
   int gapless_blocks_per_cu;
   int band, band_waves_per_cu;  // the banded DP (pm_band_kernel) for the problems it is exact for; its waves per CU
+  int band_gate;                // one-gap reads reach the band by the two-diagonal bound (PM_BAND_MAXX_, pemap_sw.hip.h): 1 always, 0 never
+                                // (by x <= 6 alone), -1 (unset) in chunks that hold more read-ends than one pass of the full DP's grid
   int first_tier;               // 0 (tests): every end of a chunk goes to the second tier's list, the first tier is not launched
   int tier2_waves;              // persistent waves per CU of the fused seed kernel's second tier (the first tier's big-end list)
   int absorb_staged;            // pemap_dev_absorb: 1 = through the staging buffers even when both objects sit on one device
@@ -150,6 +152,7 @@ static void read_knobs (PmKnobs & k)
   k.pipeline = env_int ("PEMAP_PIPELINE", 1);
   k.chunk_pairs = env_int ("PEMAP_CHUNK_PAIRS", 262144);
   k.band = env_int ("PEMAP_BAND", 1);
+  k.band_gate = getenv ("PEMAP_BAND_GATE") ? (env_int ("PEMAP_BAND_GATE", 1) ? 1 : 0) : -1;
   k.gapless_blocks_per_cu = env_int ("PEMAP_GAPLESS_BLOCKS_PER_CU", -1);     // one-wave workgroups of pm_gapless_kernel launched per CU at most; -1: by read length
   if (k.gapless_blocks_per_cu == 0) k.gapless_blocks_per_cu = 1;
   k.band_waves_per_cu = env_int ("PEMAP_BAND_WAVES_PER_CU", 16);
@@ -684,6 +687,11 @@ extern "C" int pemap_dev_seed_launch (pemap_dev * d, int *asked, int *resident, 
   return 0;
 }
 
+extern "C" int pemap_dev_sw_grid (pemap_dev * d)
+{
+  return d->sw_grid;
+}
+
 extern "C" int pemap_dev_index_commit (pemap_dev * d)
 {
   if (!d->d_pos_index)
@@ -1028,8 +1036,10 @@ static size_t dir_budget_bytes (const pemap_dev * d)
 #define PM_TASK_QUARTERS 4
 struct PmTaskList
 {
-  uint32_t *all, *dp, *band, *c3;       // band: null with PEMAP_BAND=0; c3: null below PEMAP_GAPLESS=3
+  uint32_t *all, *dp, *band, *c3;       // band: null with PEMAP_BAND=0; c3: null below PEMAP_GAPLESS=3 unless the band's gate needs it
   unsigned *n_all, *n_dp, *n_band, *n_c3, *dp_next, *band_next; // the lists' lengths; the work counters of the full and the banded DP
+  unsigned *n_gate;             // problems the second launch admits to the band by the two-diagonal bound; null with PEMAP_BAND_GATE=0
+                                // (launch_cascade passes it on for the chunks in which the bound is tested)
 };
 
 static size_t task_quarter_words (int n_ends, bool multi)
@@ -1048,7 +1058,9 @@ static PmTaskList task_list (const pemap_dev * d, const PmChunkSet & S, PmCounte
   l.dp = rule ? t + q : l.all;  // (PEMAP_GAPLESS=0: no rule, the full DP takes the seed stage's list as it is)
   l.n_dp = !rule ? l.n_all : multi ? &ctr->n_tasks_mdp : &ctr->n_tasks_dp;
   l.band = rule && d->kn.band ? t + 2 * q : nullptr;
-  l.c3 = rule && pm_gapless_max_x (d) >= 3 ? t + 3 * q : nullptr;
+  // (the two-diagonal bound is tested in the rule's second launch: its problems travel in case (3)'s list)
+  l.n_gate = l.band && d->kn.band_gate ? &ctr->n_gate[multi] : nullptr;
+  l.c3 = rule && (pm_gapless_max_x (d) >= 3 || l.n_gate) ? t + 3 * q : nullptr;
   l.n_band = &ctr->n_band[multi];
   l.n_c3 = &ctr->n_c3[multi];
   l.dp_next = &ctr->sw_next[multi];
@@ -1432,10 +1444,10 @@ template < bool C3 > static void launch_gapless (pemap_dev * d, bool short_rows,
 {
   if (short_rows)
     hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < C3, true >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, S.hits, tasks, n_tasks,
-                        l.dp, l.n_dp, max_x, l.band, l.n_band, tasks_c3, n_tasks_c3);
+                        l.dp, l.n_dp, max_x, l.band, l.n_band, tasks_c3, n_tasks_c3, l.n_gate);
   else
     hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_gapless_kernel < C3, false >), dim3 (ggrid), dim3 (PM_GL_BLOCK), 0, d->stream, c.ix, c.b, c.prm, S.hits, tasks, n_tasks,
-                        l.dp, l.n_dp, max_x, l.band, l.n_band, tasks_c3, n_tasks_c3);
+                        l.dp, l.n_dp, max_x, l.band, l.n_band, tasks_c3, n_tasks_c3, l.n_gate);
 }
 
 // ---- the DP cascade over one task list, on the ALU stream: the gapless rule, its second launch for case (3), the banded DP, the full
@@ -1444,6 +1456,13 @@ template < bool C3 > static void launch_gapless (pemap_dev * d, bool short_rows,
 template < int W, int LPA, bool DIRS > static auto launch_cascade (pemap_dev * d, const RunCtx & c, const PmChunkSet & S, PmCounters * ctr, const PmTaskList & l)
 {
   const int n_ends = c.b.n_ends, max_x = pm_gapless_max_x (d);
+  // The two-diagonal bound takes work off the full DP where that launch is more than one pass of its grid (sw_grid persistent waves,
+  // 64 / LPA problems each at a time): a list cannot be longer than the chunk has read-ends, so a chunk of no more ends than that
+  // keeps the routing by x <= 6 alone -- its full DP is one pass whatever the band takes, and the problems are spared the second
+  // launch.  PEMAP_BAND_GATE=1 / 0 decide for every chunk.  (The outputs are the same either way.)
+  PmTaskList lg = l;
+  if (d->kn.band_gate < 0 && (long) n_ends <= (long) d->sw_grid * (64 / LPA))
+    lg.n_gate = nullptr;
   // the multi-hit list's rule and band launches fill the device; the single-hit list holds at most one problem per read-end
   int ggrid = d->n_cus * 16, bgrid = d->n_cus * d->kn.band_waves_per_cu;
   if (DIRS)
@@ -1471,10 +1490,11 @@ template < int W, int LPA, bool DIRS > static auto launch_cascade (pemap_dev * d
   // (reads of up to PM_GL_SHORT_MM = 160 bases, the seed stage's class boundary: the kernel's short rows, 1 KB of LDS per workgroup)
   const bool short_rows = seg_template (c.L) <= 10;
   if (pm_gapless_on (d))
-    launch_gapless < false > (d, short_rows, ggrid, c, S, l.all, l.n_all, l, max_x, l.c3, l.n_c3);
-  // case (3) in a launch of its own over the problems it may decide (one in eight; what it refuses joins the DP's lists)
+    launch_gapless < false > (d, short_rows, ggrid, c, S, l.all, l.n_all, lg, max_x, l.c3, l.n_c3);
+  // case (3) in a launch of its own over the problems it may decide (one in eight; what it refuses joins the DP's lists), and with
+  // them the problems without a good diagonal, which it sends to the band if two diagonals and one gap prove the band's premise
   if (l.c3)
-    launch_gapless < true > (d, short_rows, ggrid, c, S, l.c3, l.n_c3, l, max_x, (uint32_t *) nullptr, (unsigned *) nullptr);
+    launch_gapless < true > (d, short_rows, ggrid, c, S, l.c3, l.n_c3, lg, max_x, (uint32_t *) nullptr, (unsigned *) nullptr);
   // the problems the rule left open whose best diagonal has few mismatches: the DP restricted to a band of 32 diagonals,
   // four lanes per problem (pemap_band.hip.h); what is left for pm_sw_kernel are mostly the reads with a real indel
   if (l.band)
@@ -1572,6 +1592,8 @@ static int absorb_run (pemap_dev * d)
       t.n_tasks_mdp += pm_gapless_on (d) ? c.n_tasks_mdp : c.n_tasks_m;
       t.n_band[0] += c.n_band[0];
       t.n_band[1] += c.n_band[1];
+      t.n_gate[0] += c.n_gate[0];
+      t.n_gate[1] += c.n_gate[1];
       t.cells_band += c.cells_band;
       t.n_slots += c.n_slots;
       t.n_redo += c.n_redo;
@@ -2297,6 +2319,7 @@ extern "C" int pemap_dev_run_stats (pemap_dev * d, uint64_t * s, float *t)
       s[14] = c.cells_band;
       s[15] = d->last_big2;
       s[16] = c.n_walks;
+      s[17] = (uint64_t) c.n_gate[0] + c.n_gate[1];
     }
   if (t)
     memcpy (t, d->last_ms, sizeof (d->last_ms));

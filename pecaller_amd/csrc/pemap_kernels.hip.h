@@ -134,6 +134,7 @@ struct PmCounters
   unsigned int n_c3[2];            // problems the gapless rule's first launch leaves to its second (case (3)): single-hit ends, multi-hit ends
   unsigned long long cells_band;   // band cells computed
   unsigned int n_walks;            // of n_wins, the alignments pm_walk_kernel follows (the others are known to be plain diagonals)
+  unsigned int n_gate[2];          // of n_band, the problems admitted by the two-diagonal bound (PEMAP_BAND_GATE): single-hit ends, multi-hit ends
 };
 
 // insertion log cursor: survives runs until the host drains the log

@@ -514,6 +514,22 @@ __device__ __forceinline__ uint64_t pm_rc8 (uint64_t v, int vacated_bits)
 #define PM_BAND_W (22 + 2 * PM_BAND_K)
 #define PM_BAND_MAXX_ (PM_BAND_K >= 5 ? 6 : PM_BAND_K + 1)
 static_assert (PM_BAND_K >= 2 && PM_BAND_K <= 5, "the band holds at most 32 diagonals");
+// What the band needs is "optimum >= mm - 8" (K = 5), and a single diagonal with x <= 6 is one way to know it.  The other, for the
+// problems with xmin > PM_BAND_MAXX_ (reads with one indel away from their ends): an explicit alignment with ONE gap, a prefix of the
+// read on diagonal d1 and the rest on d2, both in 0 .. D.  With p_i[d] / s_j[d] the longest prefix / suffix of diagonal d with at
+// most i / j mismatches (piece_mask's count, as for x):
+//   deletion of b = d2 - d1 >= 1 reference bases:        exists iff p_i[d1] + s_j[d2] >= mm,     loses 2 + (b-1)/36 + 4(i+j)/3
+//   insertion of b = d1 - d2, 1 <= b <= K, read bases:   exists iff p_i[d1] + s_j[d2] >= mm - b, loses b + 2 + (b-1)/36 + 4(i+j)/3
+// (any split point in [mm - b - s_j, p_i] will do; the two parts are disjoint, so they hold at most i + j mismatches).  The problem
+// goes to the band iff one of them loses at most 8, in units of 1/36:
+//   deletion:   72 + (b-1) + 48 (i+j) <= 288          -- every b <= 21 with i + j <= 4
+//   insertion:  36 b + 72 + (b-1) + 48 (i+j) <= 288   -- i + j <= 3, 2, 2, 1, 0 for b = 1 .. 5, never for b >= 6
+// which leaves the margin of the x <= 6 rule, 5/36, to every path outside [-K, D + K].  The kernel knows PM_GATE_Y + 1 = 3 mismatches
+// from each end of a diagonal (i, j <= 2); with fewer known it would refuse more, with more it could admit deletions with i or j = 3, 4.
+// It errs towards the full DP only.  tests/test_band_gate_cpu.py restates the bound and holds it against the full DP.
+#define PM_GATE_Y 2
+#define PM_GATE_LOSS36 (PM_BAND_K >= 5 ? 288 : 0)       // (a narrower band has a smaller bound; not derived: nothing is admitted)
+static_assert (PM_GATE_Y == 2, "pm_gapless_kernel keeps p0..p2 and s0..s2 in named registers");
 // (one-wave workgroups: a wave goes wherever a SIMD has room beside the seed kernel's waves; four to a workgroup waited for room for four)
 #define PM_GL_BLOCK 64
 #define PM_GL_PER_BLOCK (PM_GL_BLOCK / 32)     // problems a workgroup works on at a time: one per half-wave
@@ -554,7 +570,8 @@ static_assert (PM_GL_PER_BLOCK * (PmGlRows < true >::RD + PmGlRows < true >::WIN
 // SHORT: the rows and queues of PmGlRows < true >; the host (launch_gapless) chooses it for reads of up to PM_GL_SHORT_MM bases.
 template < bool C3, bool SHORT > __global__ __launch_bounds__ (PM_GL_BLOCK, PM_GL_WAVES_PER_EU) void pm_gapless_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, const uint32_t * tasks,
                                                           const unsigned *n_tasks_p, uint32_t * tasks_dp, unsigned *n_tasks_dp, int max_x,
-                                                          uint32_t * tasks_band, unsigned *n_tasks_band, uint32_t * tasks_c3, unsigned *n_tasks_c3)
+                                                          uint32_t * tasks_band, unsigned *n_tasks_band, uint32_t * tasks_c3, unsigned *n_tasks_c3,
+                                                          unsigned *n_gate)
 {
   using Rows = PmGlRows < SHORT >;
   constexpr int QN = Rows::QUEUE;       // (a round adds at most PM_GL_PER_BLOCK = 2 problems to a queue: flushed above QN - 2)
@@ -564,6 +581,7 @@ template < bool C3, bool SHORT > __global__ __launch_bounds__ (PM_GL_BLOCK, PM_G
   __shared__ uint32_t q_c3[PM_GL_BLOCK / 64][C3 ? 1 : QN];       // ... and to the second launch
   const int wv = threadIdx.x >> 6;
   int n_qb = 0, n_qd = 0, n_q3 = 0;
+  int n_gated = 0;              // problems this wave sent to the band by the two-diagonal bound (C3 only)
   auto flush_queue = [&] (const uint32_t * q, int &n, uint32_t * dst, unsigned *counter)
   {
     if (n == 0)
@@ -956,10 +974,81 @@ template < bool C3, bool SHORT > __global__ __launch_bounds__ (PM_GL_BLOCK, PM_G
         int xmin = mism;
         for (int s = 16; s; s >>= 1)
           xmin = min (xmin, __shfl_xor (xmin, s));      // (within the half-wave)
+        // The band's second premise (see PM_BAND_MAXX_): no single diagonal holds the read with few mismatches, but a prefix on
+        // diagonal d1 and a suffix on d2, one gap between them, do.  The first launch hands such problems on (n_gate is the host's
+        // switch, PEMAP_BAND_GATE); the second tells them from case (3)'s by xmin.
+        const bool two_diag = n_gate && tasks_band && xmin > PM_BAND_MAXX_ && ndiag >= 2;
+        bool gated = false;
+        if (C3 && two_diag)             // (per half-wave)
+          {
+            // p0 <= p1 <= p2: the longest prefix of diagonal l with at most 0, 1, 2 mismatches; s0 <= s1 <= s2 the same for suffixes
+            int p0 = mm, p1 = mm, p2 = mm, s0 = mm, s1 = mm, s2 = mm;
+            if (mine)
+              {
+                int nf = 0;
+                for (int c = 0; c < nch && nf < PM_GATE_Y + 1; c++)
+                  for (unsigned mk = piece_mask (l, c); mk != 0u && nf < PM_GATE_Y + 1; mk &= mk - 1u, nf++)
+                    {
+                      const int at = 8 * c + __ffs ((int) mk) - 1;
+                      if (nf == 0)
+                        p0 = at;
+                      else if (nf == 1)
+                        p1 = at;
+                      else
+                        p2 = at;
+                    }
+                nf = 0;
+                for (int c = nch - 1; c >= 0 && nf < PM_GATE_Y + 1; c--)
+                  for (unsigned mk = piece_mask (l, c); mk != 0u && nf < PM_GATE_Y + 1; nf++)
+                    {
+                      const int bit = 31 - __clz ((int) mk);
+                      mk &= ~(1u << bit);
+                      const int len = mm - 1 - (8 * c + bit);
+                      if (nf == 0)
+                        s0 = len;
+                      else if (nf == 1)
+                        s1 = len;
+                      else
+                        s2 = len;
+                    }
+              }
+            else
+              p0 = p1 = p2 = s0 = s1 = s2 = 0;
+            const int P[PM_GATE_Y + 1] = { p0, p1, p2 };
+            // a deletion of l - d1 reference bases, d1 < l: every i + j <= 2 PM_GATE_Y passes, so the longest prefix of an earlier diagonal decides
+            constexpr bool del_ok = 72 + 2 * PM_SLOP + 48 * 2 * PM_GATE_Y <= PM_GATE_LOSS36;      // (b - 1 <= D - 1 = 2 PM_SLOP)
+            int pmax = p2;
+            for (int s = 1; s < 32; s <<= 1)
+              {
+                const int v = __shfl_up (pmax, s);
+                if (l >= s)
+                  pmax = max (pmax, v);
+              }
+            int pbefore = __shfl_up (pmax, 1);
+            if (l == 0)
+              pbefore = 0;
+            bool adm = del_ok && mine && pbefore + s2 >= mm;
+            // an insertion of bb read bases: the prefix on diagonal l, the suffix on l - bb
+#pragma unroll
+            for (int bb = 1; bb <= PM_BAND_K; bb++)
+              {
+                const int src = half + (l >= bb ? l - bb : l);
+                const int T[PM_GATE_Y + 1] = { __shfl (s0, src), __shfl (s1, src), __shfl (s2, src) };
+#pragma unroll
+                for (int i = 0; i <= PM_GATE_Y; i++)
+#pragma unroll
+                  for (int j = 0; j <= PM_GATE_Y; j++)
+                    if (36 * bb + 72 + (bb - 1) + 48 * (i + j) <= PM_GATE_LOSS36)
+                      adm |= mine && l >= bb && P[i] + T[j] >= mm - bb;
+              }
+            gated = (unsigned) (__ballot (adm) >> half) != 0u;
+          }
+        if (C3)
+          n_gated += (int) __popcll (__ballot (gated && l == 0));
         // (xmin = 3 with no candidate: no diagonal has fewer)
-        const bool to_c3 = !C3 && valid && cmask == 0u && l == 0 && tasks_c3 && xmin == 3 && ndiag == 2 * PM_SLOP + 2;
+        const bool to_c3 = !C3 && valid && cmask == 0u && l == 0 && tasks_c3 && ((xmin == 3 && ndiag == 2 * PM_SLOP + 2) || two_diag);
         const bool open = valid && cmask == 0u && l == 0 && !to_c3;
-        const bool to_band = open && tasks_band && xmin <= PM_BAND_MAXX_, to_dp = open && !to_band;
+        const bool to_band = open && tasks_band && (xmin <= PM_BAND_MAXX_ || gated), to_dp = open && !to_band;
         const unsigned long long mb = __ballot (to_band), md = __ballot (to_dp);
         if (to_band)
           q_band[wv][n_qb + (int) __popcll (mb & ((1ull << lane) - 1ull))] = (uint32_t) o;
@@ -1015,6 +1104,8 @@ template < bool C3, bool SHORT > __global__ __launch_bounds__ (PM_GL_BLOCK, PM_G
   flush_queue (q_dp[wv], n_qd, tasks_dp, n_tasks_dp);
   if (!C3)
     flush_queue (q_c3[wv], n_q3, tasks_c3, n_tasks_c3);
+  if (C3 && n_gated > 0 && lane == 0)
+    atomicAdd (n_gate, (unsigned) n_gated);
 }
 
 __device__ __forceinline__ int pm_wave_max (int v)

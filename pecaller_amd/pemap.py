@@ -22,7 +22,7 @@ SYMBOLS = [
     "pemap_dev_stage_reads", "pemap_dev_run", "pemap_dev_run_slice", "pemap_dev_collect", "pemap_dev_sync",
     "pemap_dev_synth_genome", "pemap_dev_synth_reads", "pemap_dev_synth_reads_indel", "pemap_dev_staged_reads", "pemap_dev_staged_info",
     "pemap_dev_free", "pemap_dev_fetch_pileup", "pemap_dev_fetch_records", "pemap_dev_reset_pileup", "pemap_dev_summary",
-    "pemap_dev_run_stats", "pemap_dev_debug_hits", "pemap_dev_index_share", "pemap_dev_absorb",
+    "pemap_dev_run_stats", "pemap_dev_sw_grid", "pemap_dev_debug_hits", "pemap_dev_index_share", "pemap_dev_absorb",
     "pecall_dev_create", "pecall_dev_destroy", "pecall_dev_last_error", "pecall_dev_site_like", "pecall_dev_stage",
     "pecall_dev_run", "pecall_dev_collect", "pecall_dev_call_sites", "pecall_dev_call_sites_sparse", "pecall_dev_set_pedigree",
     "pecall_dev_sites_stage", "pecall_dev_sites_run", "pecall_dev_sites_stats", "pecall_dev_sites_collect", "pecall_dev_pin_host", "pecall_dev_unpin_host",
@@ -105,6 +105,8 @@ def load_library():
         L.pemap_dev_reset_pileup.argtypes = [vp]
         L.pemap_dev_summary.argtypes = [vp, vp]
         L.pemap_dev_run_stats.argtypes = [vp, vp, vp]
+        if hasattr(L, "pemap_dev_sw_grid"):         # (an older library under PEMAP_LIB, for an A/B, lacks it)
+            L.pemap_dev_sw_grid.argtypes = [vp]
         L.pemap_dev_debug_hits.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.pemap_dev_index_share.argtypes = [vp, vp]
         L.pemap_dev_absorb.argtypes = [vp, vp]
@@ -191,6 +193,10 @@ class PemapDev:
         v = [C.c_int(0) for _ in range(4)]
         self._ck(self.L.pemap_dev_seed_launch(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("asked", "resident", "launched", "lds_bytes"), (x.value for x in v)))
+
+    def sw_grid(self):
+        """persistent waves of a launch of the full DP"""
+        return int(self.L.pemap_dev_sw_grid(self.h))
 
     def index_info(self):
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_int()
@@ -363,10 +369,10 @@ class PemapDev:
         return out
 
     def run_stats(self):
-        s = np.zeros(17, np.uint64)
+        s = np.zeros(18, np.uint64)
         t = np.zeros(8, np.float32)
         self._ck(self.L.pemap_dev_run_stats(self.h, _p(s), _p(t)))
-        keys = ["ends", "positions", "sw_score", "sw_dirs", "cells_score", "cells_dirs", "pile_incs", "n_ins", "walks", "redo", "big_ends", "chunks", "gapless", "banded", "cells_band", "mono_ends", "walked"]
+        keys = ["ends", "positions", "sw_score", "sw_dirs", "cells_score", "cells_dirs", "pile_incs", "n_ins", "walks", "redo", "big_ends", "chunks", "gapless", "banded", "cells_band", "mono_ends", "walked", "gated"]
         tk = ["seed", "sw_single", "sw_multi", "select", "sw_redo", "walk", "lookup", "vote"]
         return dict(zip(keys, (int(x) for x in s))), dict(zip(tk, (float(x) for x in t)))
 

@@ -514,6 +514,17 @@ static int drain_ins (pemap_dev * d);
 static int ring_leave (pemap_dev * d);
 static void fold_summary (pemap_dev * d, int first, int n, const uint32_t * m1, const uint32_t * m2, const int *mapping_type);
 
+// Zeros in device memory, there when this returns.  hipMemset of device memory returns before the fill has run, and on the null
+// stream it is not ordered against the object's non-blocking streams: the 26 GB pileup of a genome of 2.1 G letters was still being
+// cleared, 4 GiB at a time, when a small batch's conversion of plane 0 -- queued a few milliseconds after reset_pileup -- read the
+// counts of the positions from 2^31 on (byte 2^32 of the plane), and those stale counts came back as a run-on through the plane.
+static int zero_on_stream (pemap_dev * d, void *p, size_t bytes)
+{
+  HIPCHK (d, hipMemsetAsync (p, 0, bytes, d->stream));
+  HIPCHK (d, hipStreamSynchronize (d->stream));
+  return 0;
+}
+
 extern "C" int pemap_dev_index_alloc (pemap_dev * d, uint64_t n_mers, uint64_t genome_size, int n_contigs, int idepth)
 {
   HIPCHK (d, hipSetDevice (d->device));
@@ -540,7 +551,7 @@ extern "C" int pemap_dev_index_alloc (pemap_dev * d, uint64_t n_mers, uint64_t g
   TRY (dev_alloc (d, &d->d_counts, 6 * d->pile_plane_words));
   TRY (dev_alloc (d, &d->d_pile_tiles, (d->pile_plane_words + PD_TILE - 1) / PD_TILE));
   HIPCHK (d, hipMemset (d->d_genome + genome_size, 0, 512));
-  HIPCHK (d, hipMemset (d->d_counts, 0, 6 * d->pile_plane_words * sizeof (uint32_t)));
+  TRY (zero_on_stream (d, d->d_counts, 6 * d->pile_plane_words * sizeof (uint32_t)));
   return 0;
 }
 
@@ -649,6 +660,10 @@ static int build_replicas (pemap_dev * d)
     {
       if (want == 8)
         return fail (d, "look-up replicas: %llu record units do not fit the codes above genome size %llu", total, (unsigned long long) d->gsize);
+      // as when the memory is not there: the reference's layout serves the look-ups
+      fprintf (stderr, "libpemap_hip: device %d: the look-up replicas need %llu record units and a genome of %llu letters leaves codes for %llu; "
+               "the look-ups read the reference's table instead (slower, same results; PEMAP_REPLICAS=0 silences this)\n", d->device, total,
+               (unsigned long long) d->gsize, (unsigned long long) (0xFFFFFFFEu - d->multi_base - 1u));
       return 0;
     }
   d->multi_units = total;
@@ -2378,13 +2393,13 @@ extern "C" int pemap_dev_reset_pileup (pemap_dev * d)
   if (!d->d_counts)
     return fail (d, "reset_pileup: no index");
   HIPCHK (d, hipStreamSynchronize (d->stream));
-  HIPCHK (d, hipMemset (d->d_counts, 0, 6 * d->pile_plane_words * sizeof (uint32_t)));
+  TRY (zero_on_stream (d, d->d_counts, 6 * d->pile_plane_words * sizeof (uint32_t)));
   {
     // a plane of zeros is one in both forms: no conversion, whichever form it had
     std::lock_guard < std::mutex > lk (d->mu);
     d->pile_diff = false;
   }
-  HIPCHK (d, hipMemset (d->d_cur, 0, sizeof (PmInsCursor)));
+  TRY (zero_on_stream (d, d->d_cur, sizeof (PmInsCursor)));
   d->h_ins.clear ();
   memset (d->summary, 0, sizeof (d->summary));
   return 0;

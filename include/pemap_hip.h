@@ -249,6 +249,12 @@ int pemap_dev_summary (pemap_dev * dev, long *out13);
  * at a time.  Without PEMAP_BAND_GATE a chunk of no more read-ends than one pass of this grid takes problems is routed by x <= 6 alone. */
 int pemap_dev_sw_grid (pemap_dev * dev);
 
+/* The full DP's lane geometry for a batch whose longest read has read_len bases, as this object's knobs (read when it was made)
+ * choose it: *lanes lanes share one alignment, each owns *columns read columns; lanes x columns >= read_len.  8 x 13 up to 104 bases,
+ * 16 x 10 / 13 / 16 / 19 up to 160 / 208 / 256 / 278, and with PEMAP_GAPLESS=0 8 x 19 for 105..152.  Host code only; an error for a
+ * length outside PEMAP_MIN_READ .. PEMAP_MAX_READ. */
+int pemap_dev_sw_geom (pemap_dev * dev, int read_len, int *lanes, int *columns);
+
 /* Counters the reference does not have, summed over the last run --
  * stats[0] = read-ends, [1] = positions gathered from .mdx (P), [2] = SW problems scored (H), [3] = SW problems
  * scored with direction nibbles (single-hit ends + re-scored winners), [4] = DP cells without nibbles, [5] = DP cells

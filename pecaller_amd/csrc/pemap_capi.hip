@@ -1010,6 +1010,17 @@ static void pick_geom (const pemap_dev * d, int L, int *lanes, int *w)
   else { *lanes = 16; *w = 19; }
 }
 
+// what a batch whose longest read has read_len bases runs with on this object (host code only: nothing is launched)
+extern "C" int pemap_dev_sw_geom (pemap_dev * d, int read_len, int *lanes, int *columns)
+{
+  if (!lanes || !columns)
+    return fail (d, "sw_geom: lanes and columns must not be NULL");
+  if (read_len < PEMAP_MIN_READ || read_len > PEMAP_MAX_READ)
+    return fail (d, "sw_geom: read length %d: supported range is %d..%d", read_len, PEMAP_MIN_READ, PEMAP_MAX_READ);
+  pick_geom (d, read_len, lanes, columns);
+  return 0;
+}
+
 // f (PmInt < W > {}, PmInt < LPA > {}) for the SW geometry of reads up to L bases: one instantiation per form pick_geom can choose
 template < int N > using PmInt = std::integral_constant < int, N >;
 template < class F > static void with_sw_geom (const pemap_dev * d, int L, F f)

@@ -22,7 +22,7 @@ SYMBOLS = [
     "pemap_dev_stage_reads", "pemap_dev_run", "pemap_dev_run_slice", "pemap_dev_collect", "pemap_dev_sync",
     "pemap_dev_synth_genome", "pemap_dev_synth_reads", "pemap_dev_synth_reads_indel", "pemap_dev_staged_reads", "pemap_dev_staged_info",
     "pemap_dev_free", "pemap_dev_fetch_pileup", "pemap_dev_fetch_records", "pemap_dev_reset_pileup", "pemap_dev_summary",
-    "pemap_dev_run_stats", "pemap_dev_sw_grid", "pemap_dev_debug_hits", "pemap_dev_index_share", "pemap_dev_absorb",
+    "pemap_dev_run_stats", "pemap_dev_sw_grid", "pemap_dev_sw_geom", "pemap_dev_debug_hits", "pemap_dev_index_share", "pemap_dev_absorb",
     "pecall_dev_create", "pecall_dev_destroy", "pecall_dev_last_error", "pecall_dev_site_like", "pecall_dev_stage",
     "pecall_dev_run", "pecall_dev_collect", "pecall_dev_call_sites", "pecall_dev_call_sites_sparse", "pecall_dev_set_pedigree",
     "pecall_dev_sites_stage", "pecall_dev_sites_run", "pecall_dev_sites_stats", "pecall_dev_sites_collect", "pecall_dev_pin_host", "pecall_dev_unpin_host",
@@ -107,6 +107,8 @@ def load_library():
         L.pemap_dev_run_stats.argtypes = [vp, vp, vp]
         if hasattr(L, "pemap_dev_sw_grid"):         # (an older library under PEMAP_LIB, for an A/B, lacks it)
             L.pemap_dev_sw_grid.argtypes = [vp]
+        if hasattr(L, "pemap_dev_sw_geom"):
+            L.pemap_dev_sw_geom.argtypes = [vp, i, C.POINTER(i), C.POINTER(i)]
         L.pemap_dev_debug_hits.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.pemap_dev_index_share.argtypes = [vp, vp]
         L.pemap_dev_absorb.argtypes = [vp, vp]
@@ -197,6 +199,12 @@ class PemapDev:
     def sw_grid(self):
         """persistent waves of a launch of the full DP"""
         return int(self.L.pemap_dev_sw_grid(self.h))
+
+    def sw_geom(self, read_len):
+        """(lanes per alignment, read columns per lane) of the full DP for a batch whose longest read has read_len bases"""
+        lanes, cols = C.c_int(0), C.c_int(0)
+        self._ck(self.L.pemap_dev_sw_geom(self.h, int(read_len), C.byref(lanes), C.byref(cols)))
+        return lanes.value, cols.value
 
     def index_info(self):
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_int()

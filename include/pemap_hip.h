@@ -127,6 +127,10 @@ int pemap_dev_index_info (pemap_dev * dev, uint64_t * n_mers, uint64_t * genome_
 /* copy one of the buffers above (or a byte range of it) to host memory */
 int pemap_dev_read_buffer (pemap_dev * dev, int which, uint64_t byte_offset, void *host_dst, uint64_t n_bytes);
 
+/* The parameters of the batches submitted from here on.  A call that changes a value while a batch is in flight or a run is pending
+ * first delivers every batch (as pemap_dev_wait_batch would, oldest first) and accounts the run, under the values they were
+ * submitted with: the later pemap_dev_wait_batch of such a batch returns 0 and finds it delivered.  It takes the locks of
+ * submit / wait, so it may be called beside them.  A call that changes nothing does nothing. */
 int pemap_dev_set_params (pemap_dev * dev, int paired, int min_dist, int max_dist, double min_align, int bisulfite);
 
 /* One batch.  reads are `stride`-spaced byte rows (not necessarily NUL terminated), len1/len2 their lengths,
@@ -231,6 +235,7 @@ int pemap_dev_fetch_pileup (pemap_dev * dev, uint16_t * counts, pemap_ins_cb cb,
  * returns the number of records through n_records (out may be NULL to count only). */
 int pemap_dev_fetch_records (pemap_dev * dev, uint64_t first, uint64_t count, void *out, uint64_t out_capacity,
                              uint64_t * n_records);
+/* Counters, insertion log and summary start over.  Fails, changing nothing, while a submitted batch was not waited for. */
 int pemap_dev_reset_pileup (pemap_dev * dev);
 /* The end of a run on several objects: afterwards dst is what it would be had it mapped src's batches as well, and src is as
  * after pemap_dev_reset_pileup.  Every 16-bit counter of buffer 4 becomes (dst + src) mod 2^16 -- the arithmetic of the reference's
@@ -254,6 +259,18 @@ int pemap_dev_sw_grid (pemap_dev * dev);
  * 16 x 10 / 13 / 16 / 19 up to 160 / 208 / 256 / 278, and with PEMAP_GAPLESS=0 8 x 19 for 105..152.  Host code only; an error for a
  * length outside PEMAP_MIN_READ .. PEMAP_MAX_READ. */
 int pemap_dev_sw_geom (pemap_dev * dev, int read_len, int *lanes, int *columns);
+
+/* Which way the host pipeline went, counted since the object was made (host integers only: nothing is synchronised, absorbed or
+ * launched, unlike pemap_dev_run_stats, which accounts the pending run first).  A run is one pemap_dev_run / _run_slice or the kernels
+ * of one submitted batch; it is cut into chunks, and a run queued behind a pending one continues its chunk numbering (and its event
+ * chain) unless the pending runs have to be waited for and accounted ("absorbed") first.  out8:
+ *   [0] runs queued                      [1] of them, runs that continued a pending pipeline (first chunk number > 0)
+ *   [2] absorbs because the table of 256 chunks was full
+ *   [3] absorbs because the longest read (the kernels' geometry) changed
+ *   [4] absorbs because the pending runs' arrays are too small for the new chunk, or PEMAP_PIPELINE is 2
+ *   [5] set-ups of the ring of batches in flight (the first submit, another stride or pairing, a batch beyond its capacity)
+ *   [6] chunks of the run queued last    [7] its first chunk's number */
+int pemap_dev_pipeline_stats (pemap_dev * dev, uint64_t * out8);
 
 /* Counters the reference does not have, summed over the last run --
  * stats[0] = read-ends, [1] = positions gathered from .mdx (P), [2] = SW problems scored (H), [3] = SW problems

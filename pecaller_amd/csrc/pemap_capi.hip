@@ -246,6 +246,8 @@ struct pemap_dev
   bool run_pending = false;     // kernels of the last run still in flight / not yet accounted
   int run_chunks = 0, run_L = 0;
   uint64_t run_ends = 0;
+  // which way run_slice and ring_setup went, since the object was made (pemap_dev_pipeline_stats: host integers, guarded by mu)
+  uint64_t pstat[8] = { };
   // two-stream pipeline: the look-up kernel of chunk k+1 (memory stream) runs beside vote/SW/walk of chunk k
   hipStream_t stream2 = nullptr;
   int n_cus = 0;
@@ -512,6 +514,9 @@ extern "C" void pemap_dev_destroy (pemap_dev * d)
 static const uint64_t POS_INDEX_N = (1ull << 32) + 1ull;
 static int drain_ins (pemap_dev * d);
 static int ring_leave (pemap_dev * d);
+static bool ring_busy (pemap_dev * d);
+static int ring_finish_all (pemap_dev * d, std::unique_lock < std::mutex > &lk);
+static int absorb_run (pemap_dev * d);
 static void fold_summary (pemap_dev * d, int first, int n, const uint32_t * m1, const uint32_t * m2, const int *mapping_type);
 
 // Zeros in device memory, there when this returns.  hipMemset of device memory returns before the fill has run, and on the null
@@ -940,13 +945,35 @@ extern "C" int pemap_dev_read_buffer (pemap_dev * d, int which, uint64_t byte_of
   return 0;
 }
 
+// The parameters are read again when a batch is delivered (ring_finish: m2 is copied in paired mode; fold_summary: the second end's
+// length, the distance cut-off), and ring_setup delivers what is in flight when the pairing changed.  So a change first delivers
+// every batch in flight and absorbs the pending run, under the values they were submitted with; a call that changes nothing is free.
 extern "C" int pemap_dev_set_params (pemap_dev * d, int paired, int min_dist, int max_dist, double min_align, int bisulfite)
 {
-  d->paired = paired ? 1 : 0;
+  std::unique_lock < std::mutex > sub (d->submit_mu);   // (the order of ring_leave: no submit slips in while mu is dropped in ring_finish)
+  std::unique_lock < std::mutex > lk (d->mu);
+  paired = paired ? 1 : 0;
+  bisulfite = bisulfite ? 1 : 0;
+  if (d->paired == paired && d->min_dist == min_dist && d->max_dist == max_dist && d->min_align == min_align && d->bisulfite == bisulfite)
+    return 0;
+  bool busy = d->run_pending;
+  for (int i = 0; i < PM_RING; i++)
+    busy = busy || d->ring[i].active;
+  if (busy)
+    {
+      HIPCHK (d, hipSetDevice (d->device));
+      TRY (ring_finish_all (d, lk));
+      if (d->run_pending)
+        {
+          TRY (absorb_run (d));
+          d->run_pending = false;
+        }
+    }
+  d->paired = paired;
   d->min_dist = min_dist;
   d->max_dist = max_dist;
   d->min_align = min_align;
-  d->bisulfite = bisulfite ? 1 : 0;
+  d->bisulfite = bisulfite;
   return 0;
 }
 
@@ -1739,10 +1766,16 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
         k0 = d->run_chunks;
       else
         {
+          // (why, for pemap_dev_pipeline_stats: the chunk table is full; the longest read changed; anything else of `same`)
+          d->pstat[same ? 2 : d->kn.pipeline == 1 && d->run_L != L ? 3 : 4]++;
           TRY (absorb_run (d));
           d->run_pending = false;
         }
     }
+  d->pstat[0]++;
+  d->pstat[1] += k0 > 0;
+  d->pstat[6] = (uint64_t) nch;
+  d->pstat[7] = (uint64_t) k0;
   TRY (ensure_work (d, chunk * per));
   TRY (ensure_pipeline (d, chunk * per));
   // PEMAP_PIPELINE=1 (default): the seed stage on stream2, PM_SETS chunks ahead of the ALU stream; 2: everything on the ALU stream.
@@ -2119,6 +2152,7 @@ static int ring_setup (pemap_dev * d, int n, int stride, std::unique_lock < std:
   if (d->ring_cap >= n && d->stride == stride && d->staged_paired == d->paired && (!d->paired || d->d_reads2))
     return 0;
   // a different geometry: everything in flight is delivered and accounted first
+  d->pstat[5]++;
   TRY (ring_finish_all (d, lk));
   if (d->run_pending)
     {
@@ -2322,6 +2356,16 @@ extern "C" int pemap_dev_summary (pemap_dev * d, long *out13)
   return 0;
 }
 
+// host integers only: no synchronisation, nothing absorbed, no device call (pemap_dev_run_stats would absorb the pending run)
+extern "C" int pemap_dev_pipeline_stats (pemap_dev * d, uint64_t * out8)
+{
+  if (!out8)
+    return fail (d, "pipeline_stats: out8 must not be NULL");
+  std::lock_guard < std::mutex > lk (d->mu);
+  memcpy (out8, d->pstat, sizeof (d->pstat));
+  return 0;
+}
+
 extern "C" int pemap_dev_run_stats (pemap_dev * d, uint64_t * s, float *t)
 {
   TRY (pemap_dev_sync (d));     // a run still in flight is accounted first
@@ -2403,6 +2447,9 @@ extern "C" int pemap_dev_reset_pileup (pemap_dev * d)
   HIPCHK (d, hipSetDevice (d->device));
   if (!d->d_counts)
     return fail (d, "reset_pileup: no index");
+  // (a batch delivered after the reset would be folded into the new totals: the rule of pemap_dev_absorb)
+  if (ring_busy (d))
+    return fail (d, "reset_pileup: the object has a submitted batch that was not waited for");
   HIPCHK (d, hipStreamSynchronize (d->stream));
   TRY (zero_on_stream (d, d->d_counts, 6 * d->pile_plane_words * sizeof (uint32_t)));
   {

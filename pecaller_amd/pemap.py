@@ -29,7 +29,7 @@ SYMBOLS = [
     "pecall_dev_sites_stage_records", "pecall_dev_sites_gather", "pecall_dev_sites_merge_ms", "pecall_dev_call_records",
     "pecall_dev_sites_stage_records_guided", "pecall_dev_call_records_guided",
     "pecall_dev_sites_base_text",
-    "pemap_dev_stage_fastq", "pemap_dev_submit_fastq", "pemap_dev_seed_launch",
+    "pemap_dev_stage_fastq", "pemap_dev_submit_fastq", "pemap_dev_seed_launch", "pemap_dev_pipeline_stats",
 ]
 
 # pemap_fastq.hip.h: bytes of text a block of the line-end scan takes, lines a block of the role and record scans takes, and how
@@ -109,6 +109,8 @@ def load_library():
             L.pemap_dev_sw_grid.argtypes = [vp]
         if hasattr(L, "pemap_dev_sw_geom"):
             L.pemap_dev_sw_geom.argtypes = [vp, i, C.POINTER(i), C.POINTER(i)]
+        if hasattr(L, "pemap_dev_pipeline_stats"):
+            L.pemap_dev_pipeline_stats.argtypes = [vp, vp]
         L.pemap_dev_debug_hits.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.pemap_dev_index_share.argtypes = [vp, vp]
         L.pemap_dev_absorb.argtypes = [vp, vp]
@@ -383,6 +385,13 @@ class PemapDev:
         keys = ["ends", "positions", "sw_score", "sw_dirs", "cells_score", "cells_dirs", "pile_incs", "n_ins", "walks", "redo", "big_ends", "chunks", "gapless", "banded", "cells_band", "mono_ends", "walked", "gated"]
         tk = ["seed", "sw_single", "sw_multi", "select", "sw_redo", "walk", "lookup", "vote"]
         return dict(zip(keys, (int(x) for x in s))), dict(zip(tk, (float(x) for x in t)))
+
+    def pipeline_stats(self):
+        """which way the host pipeline went since the object was made (host counters: nothing is waited for or absorbed):
+        [runs, continued, table absorbs, geometry absorbs, capacity absorbs, ring set-ups, chunks of the last run, its first chunk]"""
+        s = np.zeros(8, np.uint64)
+        self._ck(self.L.pemap_dev_pipeline_stats(self.h, _p(s)))
+        return [int(x) for x in s]
 
     def debug_hits(self, n_ends):
         nh = np.zeros(n_ends, np.int32)

@@ -5,44 +5,13 @@ import pytest
 import fixtures
 import oracle_py
 import refio
+from seam_cases import ragged_reads        # (the plans of tests/seam_cases.py draw from it too)
 
 pytestmark = pytest.mark.gpu
 COMP = np.zeros(256, np.uint8)
 COMP[:] = ord("N")
 for a, b in zip(b"ACGTacgt", b"TGCAtgca"):
     COMP[a] = b
-
-
-def ragged_reads(seed, n, lo, hi):
-    """pairs from the fixture genome with independent random lengths per end, 1 % substitutions, a few indels, some junk"""
-    rng = np.random.default_rng(seed)
-    _, contigs = fixtures.genome()
-    r1, r2 = [], []
-    for k in range(n):
-        c = contigs[int(rng.integers(0, len(contigs)))]
-        la, lb = int(rng.integers(lo, hi + 1)), int(rng.integers(lo, hi + 1))
-        fl = int(rng.integers(max(la, lb) + 20, max(la, lb) + 400))
-        s = int(rng.integers(0, len(c) - fl - 1))
-        a = c[s:s + la].copy()
-        b = COMP[c[s + fl - lb:s + fl]][::-1].copy()
-        for x in (a, b):
-            m = rng.random(len(x)) < 0.01
-            x[m] = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, int(m.sum()))]
-        if k % 50 == 0 and la > 40:
-            a = np.concatenate([a[:20], a[23:]])                      # a 3-base deletion
-        if k % 50 == 1 and lb > 40:
-            b = np.concatenate([b[:25], np.frombuffer(b"AC", np.uint8), b[25:]])[:hi]
-        if k % 97 == 0:
-            a[:] = ord("N")                                          # filtered by the N rule
-        if k % 97 == 1:
-            a[:] = ord("A")                                          # every bucket over the too-many-spots limit
-        if k % 97 == 2:
-            a = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, la)]   # junk
-        if rng.random() < 0.5:
-            a, b = b, a
-        r1.append(a.tobytes())
-        r2.append(b.tobytes())
-    return refio.pack_reads(r1) + refio.pack_reads(r2)
 
 
 # (the longest read of a batch picks the kernels' geometry: 278 -> 19 segments, 16 lanes x 19 columns; 60 -> 7, 8 x 13; 200 -> 13,

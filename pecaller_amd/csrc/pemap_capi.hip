@@ -1621,7 +1621,9 @@ static int absorb_run (pemap_dev * d)
           tot += pr[i];
         if (tot)
           {
-            static const char *nm[16] = { "lines0+wait", "decode0", "lines1", "decode1", "records-end", "stage next", "segmask", "candidates", "relevant", "pairs", "rank+walk", "out", "rec:headers", "rec:scan+3", "-", "rec:tails" };
+            // (marks 0 to 2 -- the lines' copies to LDS and the first strand's decode -- went with the line requests: a lane holds
+            // its own entries, both strands are decoded in one run of rounds, which waits for the entries: mark 3)
+            static const char *nm[16] = { "-", "-", "-", "wait+decode", "records-end", "stage next", "segmask", "candidates", "relevant", "pairs", "rank+walk", "out", "rec:headers", "rec:scan+3", "-", "rec:tails" };
             fprintf (stderr, "[pm_s4_probe]");
             for (int i = 0; i < 16; i++)
               fprintf (stderr, " %s %.1f%%", nm[i], 100.0 * (double) pr[i] / (double) tot);

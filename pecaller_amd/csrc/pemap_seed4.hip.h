@@ -15,10 +15,13 @@
 //   * the bin table is indexed by the diagonal bin itself (mod its size; strand 1 half a table further), not by a hash of it:
 //     the three bins around a position are three neighbouring cells, read with one LDS instruction where the third form made three
 //     hashes and three reads -- twice per position (candidates, positions next to candidates);
-//   * table lines of a read-end are requested under a wave-uniform test (register r holds lines of segments 2r, 2r + 1 of the
-//     2 S: wanted iff r < S), the per-segment counts of the `min_spots` rule travel in a register, not through LDS, round by round.
+//   * a lane requests its OWN table entry (pemap_seed_entry.h: lane j = neighbour j, one 4-byte load per (strand, segment), the 49
+//     lanes of one request touch the 8 lines -- one per replica -- that hold a k-mer's neighbourhood), under a wave-uniform test
+//     (register sg holds the entries of (strand, segment) sg of the 2 S: wanted iff sg < 2 S): no line registers, no copy of the
+//     lines through LDS, no second address computation at decode time; the per-segment counts of the `min_spots` rule travel in a
+//     register, not through LDS, round by round.
 // The method is the third form's, restated:
-//   look-ups  one (strand, segment) per round, lane j = neighbour j of fill_mers' order; a segment with a too-many bucket is
+//   look-ups  one (strand, segment) per round, lane j = neighbour j of fill_mers' order, its entry already in the lane; a segment with a too-many bucket is
 //             dropped whole (pemapper.c:1602-1606); buckets of one position go straight to the front of the list, entries that
 //             point to a record are parked at its back and resolved from their records {count, p1, p2, p3 | p4 ...}: the first units
 //             of the first 128 records requested together, the 4th and later positions of all of them as ONE flattened list;
@@ -27,13 +30,14 @@
 //             segments; the positions in or next to a bin with such a candidate are compacted (at most RCAP; more = a repeat, left
 //             to pm_seed_kernel) and the exact tot_found (pemapper.c:2241-2249) is an all-pairs test among them; the
 //             surviving anchors are ranked (segment, position) per strand and the reference's walk (2251-2284) is replayed;
-//   pipeline  three read-ends in flight per wave: the bytes of end k+2 and the table lines of end k+1 travel while end k is decoded
+//   pipeline  three read-ends in flight per wave: the bytes of end k+2 and the table entries of end k+1 travel while end k is decoded
 //             and voted on; ends are handed out through a counter, PM_S4_GRAB at a time.
 // Output: raw hit lists (h.n_hits / spot / nn = segment offset / orient) for pm_emit_kernel; ends that do not fit go to the big-end list.
 // LIST mode (second tier): the same kernel over a list of read-ends -- the big-end list of the first tier -- with a larger list.
 #pragma once
 #include <type_traits>
 #include "pemap_wave.hip.h"
+#include "pemap_seed_entry.h"
 
 #ifndef PM_S4_KCAP
 #define PM_S4_KCAP 1424         // positions of BOTH strands the list holds (reads of up to 160 bases, first tier): 12,784 bytes a wave, 12 waves per CU (1,536: 13,344 and 11)
@@ -91,8 +95,9 @@ template < int SMAX, int TIER > struct __align__ (16) PmSeed4Shared
     uint8_t sg[128];                    // its tag (segment | strand << 5)
     uint8_t mark[KCAP];                 // flattened tail: record number + 1 at the record's first element, 0 elsewhere
   };
-  // What outlives an end's vote lies in the vote's tables from byte LIVE on, beyond the lines and the tails' work list: the walk's
-  // hits (carried to flush_out in the middle of the next iteration, whose phases A to C touch only `lines` and `x`) and, beside
+  // What outlives an end's vote lies in the vote's tables from byte LIVE on, beyond the tails' work list (and beyond SMAX x 512
+  // bytes, where the table lines lay while the kernel copied them through LDS: the formula, and with it NKEEP, is kept): the walk's
+  // hits (carried to flush_out in the middle of the next iteration, whose phases B and C touch only `x`) and, beside
   // them, the per-segment counts of phases B and C.  Which table that is differs by form -- the back of r[] for < 10, 0 >, cells
   // and candidate bits where the list of the tails is the larger (< 10, 1 >: from byte 6,848, inside the cells) -- and what holds
   // for every form is this: the walk, the only writer of the hits, reads of the tables only the anchors (sv and order, the
@@ -121,9 +126,8 @@ template < int SMAX, int TIER > struct __align__ (16) PmSeed4Shared
   };
   union
   {
-    uint32_t lines[SMAX * 128];         // ONE strand's SMAX x 8 lines of 16 entries (the other strand's wait in registers) ...
-    Vote v;                             // ... the vote's tables afterwards ...
-    Tails x;                            // ... and in between, while the records are read
+    Vote v;                             // the vote's tables ...
+    Tails x;                            // ... and before them, while the records are read, the tails' work list
     Keep k;
     Over o;
   } a;
@@ -145,7 +149,7 @@ static_assert (sizeof (PmSeed4Shared < 10, 0 >) == PM_S4_SHARED_10_0_BYTES, "the
 extern __shared__ __align__ (16) uint8_t pm_seed4_lds[];
 
 #ifdef PEMAP_TIMING_PROBES
-__device__ unsigned long long pm_s4_probe[32];      // 0..15 phases; 16..18 segments decoded / dropped / dropped by the k-mer's own bucket; 20 ends;
+__device__ unsigned long long pm_s4_probe[32];      // 3..15 phases (0..2 unused); 16..18 segments decoded / dropped / dropped by the k-mer's own bucket; 20 ends;
                                                     // 21..23 to the big-end list by the list's room / (unused) / the candidates' capacity
 #define PM_S4_T(i) do { const unsigned long long t_ = __builtin_readcyclecounter (); pacc[i] += t_ - plast; plast = t_; } while (0)
 #else
@@ -169,13 +173,9 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
   const int nb = b.stride < 16 * SMAX ? b.stride : 16 * SMAX;
   unsigned long long n_pos = 0;
   // lane j looks at neighbour j of every segment (fill_mers' order, pm_neighbour): the 2-bit field it replaces, the
-  // alternative's rank, the replica (= 4-bit field) whose line holds the entry
-  const int nb_f = lane > 0 ? (lane - 1) / 3 : 0;
-  const uint32_t nb_a = lane > 0 ? (uint32_t) ((lane - 1) % 3) : 0u;
-  const uint32_t nb_sh = 2u * (uint32_t) (nb_f & 15);
-  const uint32_t nb_keep = lane > 0 ? ~(3u << nb_sh) : 0xFFFFFFFFu;      // lane 0: the k-mer itself
-  const uint32_t nb_alt_on = lane > 0 ? 0xFFFFFFFFu : 0u;
-  const uint32_t nb_p4 = 4u * (uint32_t) ((nb_f >> 1) & 7), nb_pw = 16u * (uint32_t) ((nb_f >> 1) & 7);
+  // alternative's rank, the replica (= 4-bit field) whose line holds the entry (pemap_seed_entry.h), and that replica's base
+  const PmSeedEntryLane nbl = pm_seed_entry_lane (lane);
+  const uint32_t *const nb_rep = ix.rep + ((size_t) pm_seed_entry_replica (nbl) << 32);
 
   // ends are handed out through a counter, two values ahead of their use (the first grid-ful by block index)
   const int grid_n = __builtin_amdgcn_readfirstlane ((int) gridDim.x);
@@ -196,10 +196,12 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
 
   uint8_t rb[NBT];              // the bytes of the end whose k-mers are formed next
   int rlen = 0, rend = 0;       // ... its length and its number (second tier: from the list)
-  uint4 ln[SMAX];               // the table lines of the end decoded next: 4 lanes x 16 bytes per line, 16 lines per register
+  // the table entries of the end decoded next: register sg = (strand, segment) sg, lane j = neighbour j.  Lanes 49..63 never
+  // request anything: they read as empty from here to the kernel's end
+  uint32_t ent[2 * SMAX];
 #pragma unroll
-  for (int r = 0; r < SMAX; r++)
-    ln[r] = make_uint4 (0u, 0u, 0u, 0u);
+  for (int sg = 0; sg < 2 * SMAX; sg++)
+    ent[sg] = 0xFFFFFFFFu;
   auto load_bytes = [&] (int w)
   {
     const int e = TIER ? (int) elist[w] : w;
@@ -213,8 +215,8 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
       }
   };
   // read in registers -> 2-bit codes of both strands, N filter (pemapper.c:1552-1559), segment count, the 2 x S k-mers into
-  // kmer_out (lane = (strand, segment)), and the 2 x S x 8 line requests into ln[].  -> S, or 0 when the N filter drops the read.
-  // (`between` runs after the read's bytes have been consumed and before the line requests are issued: the memory counter is in
+  // kmer_out (lane = (strand, segment)), and the 2 x S entry requests into ent[].  -> S, or 0 when the N filter drops the read.
+  // (`between` runs after the read's bytes have been consumed and before the entry requests are issued: the memory counter is in
   // order, so whatever is issued BEFORE the point that waits for the bytes is waited for as well -- the loop puts the previous end's
   // output and the work counter's atomic there)
   auto stage_p = [&] (uint32_t & kmer_out, int &len_out, int &end_out, auto between)->int
@@ -283,20 +285,18 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
       x ^= t ^ (t << 1);
       kmer_out = lane < 2 * S ? x : kmer_out;
     }
-    // register r holds the lines of (strand, segment) 2 r (lanes 0..31) and 2 r + 1 (lanes 32..63), 8 each: wanted iff r < S
-    const int p = (lane >> 2) & 7;
-    const uint32_t *rep_lane = ix.rep + ((size_t) p << 32) + (size_t) ((lane & 3) * 4);
+    // register sg holds the entries of (strand, segment) sg, lane j its neighbour j's: wanted iff sg < 2 S (the decode looks at
+    // no other).  One request touches 8 lines, one per replica: the lanes of a replica are neighbours
+    if (nbl.on)
+      {
 #pragma unroll
-    for (int r = 0; r < SMAX; r++)
-      if (r < S)
-        {
-          const uint32_t k_lo = (uint32_t) __builtin_amdgcn_readlane ((int) kmer_out, (2 * r) & 63), k_hi = (uint32_t) __builtin_amdgcn_readlane ((int) kmer_out, (2 * r + 1) & 63);
-          const uint32_t ksrc = lane < 32 ? k_lo : k_hi;
-          const uint32_t idx = pm_swap_fields (ksrc, p);
-          ln[r] = *(const uint4 *) (rep_lane + (size_t) (idx & ~15u));
-        }
-      else
-        ln[r] = make_uint4 (0u, 0u, 0u, 0u);
+        for (int sg = 0; sg < 2 * SMAX; sg++)
+          if (sg < 2 * S)
+            {
+              const uint32_t k = (uint32_t) __builtin_amdgcn_readlane ((int) kmer_out, sg & 63);
+              ent[sg] = nb_rep[pm_seed_entry_index (k, nbl)];
+            }
+      }
     return S;
   };
 
@@ -357,88 +357,50 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
       int T = 0, cmin0 = 0, cmin1 = 0;
       if (S > 0)
         {
-          // ---- A: the lines of this end (requested one iteration ago) go from registers to LDS one strand at a time
-          auto lines_to_lds = [&] (int strand)
-          {
-            const int sgA = strand * S, sgB = sgA + S;
-#pragma unroll
-            for (int r = 0; r < SMAX; r++)
-              if (2 * r + 1 >= sgA && 2 * r < sgB)      // (uniform)
-                {
-                  const int sg = 2 * r + (lane >> 5);
-                  if (sg >= sgA && sg < sgB)
-                    *(uint4 *) (&sh.a.lines[(sg - sgA) * 128 + (lane & 31) * 4]) = ln[r];
-                }
-          };
-          lines_to_lds (0);
-          pm_wave_sync ();
-          PM_S4_T (0);
-          // ---- B: one (strand, segment) per round, lane j = neighbour j.  A segment with a bucket of too_many_spots or more is
-          //      dropped whole (pemapper.c:1602-1606: the entry itself says so); buckets of one position go straight to the
-          //      front of the list; entries that point to a record are parked at its back
+          // ---- B: one (strand, segment) per round, lane j = neighbour j, its entry in ent[sg] (requested one iteration ago; the
+          //      rounds are unrolled, so that ent[] stays in registers, each under a wave-uniform test).  A segment with a bucket of
+          //      too_many_spots or more is dropped whole (pemapper.c:1602-1606: the entry itself says so); buckets of one
+          //      position go straight to the front of the list; entries that point to a record are parked at its back
           int nf = 0, nm = 0;
           int cntv = 0;         // lane sg: positions of (strand, segment) sg found in single-position buckets
-          auto decode_strand = [&] (auto ST)
-          {
-            constexpr int strand = decltype (ST)::value;
-            // neighbour `lane` of segment sg: its entry, from the segment's 8 lines
-            auto entry_of = [&] (int sg)->uint32_t
-            {
-              const uint32_t k = (uint32_t) __builtin_amdgcn_readlane ((int) kQ, sg);
-              const uint32_t cur = (k >> nb_sh) & 3u;
-              const uint32_t alt = nb_a + (nb_a >= cur ? 1u : 0u);
-              const uint32_t nbk = (k & nb_keep) | ((alt << nb_sh) & nb_alt_on);
-              return lane < 49 ? sh.a.lines[(sg - strand * S) * 128 + nb_pw + ((nbk >> nb_p4) & 15u)] : 0xFFFFFFFFu;
-            };
-            uint32_t ent_next = entry_of (strand * S);
-#pragma unroll 1
-            for (int seg = 0; seg < S; seg++)
+#pragma unroll
+          for (int sg = 0; sg < 2 * SMAX; sg++)
+            if (sg < 2 * S)
               {
-                const int sg = strand * S + seg;
-                const uint32_t ent = ent_next;
-                if (seg + 1 < S)
-                  ent_next = entry_of (sg + 1);         // (its LDS read flies while this segment is filed)
+                const int strand = sg >= S ? 1 : 0, seg = sg >= S ? sg - S : sg;
+                const uint32_t en = ent[sg];
+                const unsigned long long too_many = __ballot (en == 0xFFFFFFFEu);
 #ifdef PEMAP_TIMING_PROBES
-                {
-                  const unsigned long long tm_ = __ballot (ent == 0xFFFFFFFEu);
-                  pacc[16] += 1ull;
-                  pacc[17] += tm_ != 0ull;
-                  pacc[18] += (tm_ & 1ull) != 0ull;
-                }
+                pacc[16] += 1ull;
+                pacc[17] += too_many != 0ull;
+                pacc[18] += (too_many & 1ull) != 0ull;
 #endif
-                if (__ballot (ent == 0xFFFFFFFEu) != 0ull)
-                  continue;
-                // (one compare each: an entry is the bucket's only position, or -- 0xFFFFFFFE being too many, seen above, and 0xFFFFFFFF
-                // empty -- a record's unit number above multi_base; the two kinds share one pair of stores, front and back of the list)
-                const uint32_t unit = ent - multi_base;
-                const bool single = ent < multi_base, multi = unit < 0xFFFFFFFEu - multi_base;
-                const unsigned long long bs = __ballot (single), bm = __ballot (multi);
-                const int off = (seg < cuts || cuts == 0) ? seg * idepth : last_off;
-                const uint32_t tg = (uint32_t) (seg | (strand << 5));
-                // (both ranks and both values computed by every lane, then selected: no divergent arms)
-                const int rs = pm_lanes_below_here (bs), rm = pm_lanes_below_here (bm);
-                int at = nf + rs;
-                at = multi ? SH::KCAP - 1 - nm - rm : at;
-                uint32_t val = ent + (uint32_t) (PM_DIAG_BIAS - off);
-                val = multi ? unit : val;                       // (a record: its first 16-byte unit)
-                if (single || multi)
+                if (too_many == 0ull)
                   {
-                    sh.key[at] = val;
-                    sh.tag[at] = (uint8_t) tg;
+                    // (one compare each: an entry is the bucket's only position, or -- 0xFFFFFFFE being too many, seen above, and 0xFFFFFFFF
+                    // empty -- a record's unit number above multi_base; the two kinds share one pair of stores, front and back of the list)
+                    const uint32_t unit = en - multi_base;
+                    const bool single = en < multi_base, multi = unit < 0xFFFFFFFEu - multi_base;
+                    const unsigned long long bs = __ballot (single), bm = __ballot (multi);
+                    const int off = (seg < cuts || cuts == 0) ? seg * idepth : last_off;
+                    const uint32_t tg = (uint32_t) (seg | (strand << 5));
+                    // (both ranks and both values computed by every lane, then selected: no divergent arms)
+                    const int rs = pm_lanes_below_here (bs), rm = pm_lanes_below_here (bm);
+                    int at = nf + rs;
+                    at = multi ? SH::KCAP - 1 - nm - rm : at;
+                    uint32_t val = en + (uint32_t) (PM_DIAG_BIAS - off);
+                    val = multi ? unit : val;                       // (a record: its first 16-byte unit)
+                    if (single || multi)
+                      {
+                        sh.key[at] = val;
+                        sh.tag[at] = (uint8_t) tg;
+                      }
+                    const int ns = (int) __popcll (bs);
+                    nf += ns;
+                    nm += (int) __popcll (bm);
+                    pm_s4_writelane (cntv, ns, sg);
                   }
-                const int ns = (int) __popcll (bs);
-                nf += ns;
-                nm += (int) __popcll (bm);
-                cntv = lane == sg ? ns : cntv;
               }
-          };
-          decode_strand (std::integral_constant < int, 0 > { });
-          pm_wave_sync ();
-          PM_S4_T (1);
-          lines_to_lds (1);
-          pm_wave_sync ();
-          PM_S4_T (2);
-          decode_strand (std::integral_constant < int, 1 > { });
           if (lane < SH::NSEG + 2)
             sh.a.k.seg_cnt[lane] = cntv;
           pm_wave_sync ();
@@ -609,15 +571,15 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
         if (lane == 0 && idxR == PM_S4_GRAB - 1)
           raw_next = atomicInc (out.next_end, 0xFFFFFFFFu);
       };
-      // ---- P: the next end's k-mers and line requests (its bytes arrived during the previous iteration); R: the bytes of the end after
+      // ---- P: the next end's k-mers and entry requests (its bytes arrived during the previous iteration); R: the bytes of the end after
       int SP = 0, lenP = 0, endP = 0;
       uint32_t kP = 0;
       // Every load issued so far has landed or is about to be needed (the next end's bytes were requested an iteration ago, behind
-      // this end's lines; the records were consumed above): said HERE, on every path, so that the compiler's wait-count model is
-      // clean before the line requests go out.  Without it the zeroing of rb[] in load_bytes -- registers a load of the previous
-      // iteration MAY still own on the path that skipped stage_p -- carries `s_waitcnt vmcnt(1)` right behind the line requests
+      // this end's entries; the records were consumed above): said HERE, on every path, so that the compiler's wait-count model is
+      // clean before the entry requests go out.  Without it the zeroing of rb[] in load_bytes -- registers a load of the previous
+      // iteration MAY still own on the path that skipped stage_p -- carries `s_waitcnt vmcnt(1)` right behind the entry requests
       // (conditional, so uncounted), and the wave sat out their whole HBM latency: 31 % of its cycles (the third form had the same
-      // wait; the lines were never in flight across the vote as its comments said)
+      // wait; the table lines it then requested were never in flight across the vote as its comments said)
       __builtin_amdgcn_s_waitcnt (0x0F70);      // vmcnt(0)
       if (eP < n_work)
         SP = stage_p (kP, lenP, endP, out_and_next);
@@ -975,7 +937,7 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
           blkR = grid_n + raw_s;
           idxR = 0;
           // (pinned to a scalar register HERE: left alone the compiler defers the read of the atomic's result to eR's first use, which
-          // comes right behind the next line requests -- and the in-order memory counter then waits for those as well)
+          // comes right behind the next entry requests -- and the in-order memory counter then waits for those as well)
           asm volatile ("; work counter read %0"::"s" (raw_s));
         }
       else

@@ -1613,22 +1613,25 @@ static int absorb_run (pemap_dev * d)
 #ifdef PEMAP_TIMING_PROBES
   {
     // the fused seed kernel's phase probes (pemap_seed4.hip.h): cycles summed over waves, printed per run
-    unsigned long long pr[32], z[32] = { 0ull };
-    if (hipMemcpyFromSymbol (pr, HIP_SYMBOL (pm_s4_probe), sizeof pr) == hipSuccess)
+    unsigned long long pr2[2][32], z[2][32] = { { 0ull } };
+    if (hipMemcpyFromSymbol (pr2, HIP_SYMBOL (pm_s4_probe), sizeof pr2) == hipSuccess)
       {
-        unsigned long long tot = 0;
-        for (int i = 0; i < 16; i++)
-          tot += pr[i];
-        if (tot)
+        for (int tier = 0; tier < 2; tier++)
           {
+            const unsigned long long *pr = pr2[tier];
+            unsigned long long tot = 0;
+            for (int i = 0; i < 16; i++)
+              tot += pr[i];
+            if (!tot)
+              continue;
             // (marks 0 to 2 -- the lines' copies to LDS and the first strand's decode -- went with the line requests: a lane holds
             // its own entries, both strands are decoded in one run of rounds, which waits for the entries: mark 3)
             static const char *nm[16] = { "-", "-", "-", "wait+decode", "records-end", "stage next", "segmask", "candidates", "relevant", "pairs", "rank+walk", "out", "rec:headers", "rec:scan+3", "-", "rec:tails" };
-            fprintf (stderr, "[pm_s4_probe]");
+            fprintf (stderr, "[pm_s4_probe tier %d]", tier);
             for (int i = 0; i < 16; i++)
               fprintf (stderr, " %s %.1f%%", nm[i], 100.0 * (double) pr[i] / (double) tot);
             fprintf (stderr, " | total %.3f G wave-cycles | segments %llu, dropped for a too-many bucket %llu, of them by the k-mer's own bucket %llu\n", (double) tot / 1e9, pr[16], pr[17], pr[18]);
-            fprintf (stderr, "[pm_s4_probe] ends decoded %llu; passed over: the list's room %llu, positions next to candidates %llu\n", pr[20], pr[21], pr[23]);
+            fprintf (stderr, "[pm_s4_probe tier %d] ends decoded %llu; passed over: the list's room %llu, positions next to candidates %llu\n", tier, pr[20], pr[21], pr[23]);
           }
         (void) hipMemcpyToSymbol (HIP_SYMBOL (pm_s4_probe), z, sizeof z);
       }
@@ -1783,7 +1786,8 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
   // PEMAP_PIPELINE=1 (default): the seed stage on stream2, PM_SETS chunks ahead of the ALU stream; 2: everything on the ALU stream.
   // The reference layout's vote runs on the ALU stream (it was slower beside its look-ups).  The fused layout's emit kernel
   // runs on the ALU stream for reads of up to 160 bases (where the seed kernel is the longer side: 29.8 ms per step against
-  // 31.4), behind the seed kernel for longer ones (2 x 245: 56.9 ms against 58.6).
+  // 31.4; measured again behind the shorter second tier, profiles/r16_ab_sweeps.txt: 15.4 against 16.0 at 2 x 150, 16.0 against
+  // 16.3 at 2 x 160, 11.1 against 11.3 at 2 x 100), behind the seed kernel for longer ones (2 x 245: 56.9 ms against 58.6).
   PmSchedule s;
   s.ahead = d->kn.pipeline == 1;
   s.seed = s.ahead ? d->stream2 : d->stream;

@@ -31,9 +31,13 @@
 //             to pm_seed_kernel) and the exact tot_found (pemapper.c:2241-2249) is an all-pairs test among them; the
 //             surviving anchors are ranked (segment, position) per strand and the reference's walk (2251-2284) is replayed;
 //   pipeline  three read-ends in flight per wave: the bytes of end k+2 and the table entries of end k+1 travel while end k is decoded
-//             and voted on; ends are handed out through a counter, PM_S4_GRAB at a time.
+//             and voted on; ends are handed out through a counter, PM_S4_GRAB at a time (second tier: one at a time).
 // Output: raw hit lists (h.n_hits / spot / nn = segment offset / orient) for pm_emit_kernel; ends that do not fit go to the big-end list.
 // LIST mode (second tier): the same kernel over a list of read-ends -- the big-end list of the first tier -- with a larger list.
+// Its ends are few (some ten a wave and launch) and long (1,425 to 5,696 positions, nearly all of them 4th-and-later positions of
+// records) and it runs one wave a SIMD, where nothing hides a trip to memory: it takes its ends one per fetch, walks the records'
+// tails 512 elements a trip and requests a round's record headers one round ahead (PM_S4_*_T2 below; every difference is
+// `if constexpr` on TIER or a per-tier constant: the first tier's code is what it was).
 #pragma once
 #include <type_traits>
 #include "pemap_wave.hip.h"
@@ -54,6 +58,20 @@
 #ifndef PM_S4_GRAB
 #define PM_S4_GRAB 4            // consecutive read-ends a wave takes per fetch of the work counter (a single address returns ~85 M atomics/s)
 #endif
+// the second tier's own: some ten ends a wave and launch, each of 1,425 to 5,696 positions, one wave a SIMD
+#ifndef PM_S4_GRAB_T2
+#define PM_S4_GRAB_T2 1         // ... ends per fetch (some 8 K atomics a launch)
+#endif
+#ifndef PM_S4_TAIL_DEPTH_T2
+#define PM_S4_TAIL_DEPTH_T2 8   // ... loads of 64 tail elements requested before the first is stored (first tier: 2; 16 here: 684 us a launch against 580)
+#endif
+#ifndef PM_S4_AHEAD_T2
+#define PM_S4_AHEAD_T2 2        // ... ends reserved ahead of the one in work (1: the next end's bytes are requested where its entries are, and waited for:
+                                // 518 us a launch against 580 in one kernel trace each, profiles/r16_ab_sweeps.txt; the step's A/B is not taken, 2 stays)
+#endif
+#ifndef PM_S4_HDR_AHEAD_T2
+#define PM_S4_HDR_AHEAD_T2 1    // ... the record headers of round r + 1 are requested before round r's tails are walked
+#endif
 
 // tag of a position: segment (5 bits) | strand << 5 | candidate anchor << 7
 #define PM_S4_SEG(t) ((t) & 31u)
@@ -71,6 +89,7 @@ template < int SMAX, int TIER > struct __align__ (16) PmSeed4Shared
   static constexpr int NH_LOG2 = TIER ? (SMAX <= 10 ? 12 : CELL16 ? 13 : 12) : (SMAX <= 10 ? 11 : PM_S4_NH_LOG2_LONG);
   static constexpr int NH = 1 << NH_LOG2;
   static constexpr int RCAP = (SMAX <= 10 ? 160 : 256) * (TIER ? 2 : 1);
+  static constexpr int TAIL_DEPTH = TIER ? PM_S4_TAIL_DEPTH_T2 : 2;                              // loads of 64 tail elements in flight together (`tails`)
   static constexpr int CELL_WORDS = ((CELL16 ? NH / 2 : NH) + 2 + 3) & ~3;       // cell c is stored at index c + 1: a pad cell either side
   static constexpr int CAND_WORDS = (NH / 32 + 1 + 3) & ~3;
   static_assert (KCAP >= 2 * 49 * SMAX + 64, "the list holds an end's look-ups while they are decoded");
@@ -149,7 +168,7 @@ static_assert (sizeof (PmSeed4Shared < 10, 0 >) == PM_S4_SHARED_10_0_BYTES, "the
 extern __shared__ __align__ (16) uint8_t pm_seed4_lds[];
 
 #ifdef PEMAP_TIMING_PROBES
-__device__ unsigned long long pm_s4_probe[32];      // 3..15 phases (0..2 unused); 16..18 segments decoded / dropped / dropped by the k-mer's own bucket; 20 ends;
+__device__ unsigned long long pm_s4_probe[2][32];   // per tier: 3..15 phases (0..2 unused); 16..18 segments decoded / dropped / dropped by the k-mer's own bucket; 20 ends;
                                                     // 21..23 to the big-end list by the list's room / (unused) / the candidates' capacity
 #define PM_S4_T(i) do { const unsigned long long t_ = __builtin_readcyclecounter (); pacc[i] += t_ - plast; plast = t_; } while (0)
 #else
@@ -178,21 +197,26 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
   const uint32_t *const nb_rep = ix.rep + ((size_t) pm_seed_entry_replica (nbl) << 32);
 
   // ends are handed out through a counter, two values ahead of their use (the first grid-ful by block index)
+  // (second tier: ONE end per fetch.  A launch has some ten ends a wave, of 1,425 to 5,696 positions each: handed out in fours, a
+  // wave that drew a long end held up to five more while others had run out -- the launch's tail was several ends long)
+  constexpr int GRAB = TIER ? PM_S4_GRAB_T2 : PM_S4_GRAB;
   const int grid_n = __builtin_amdgcn_readfirstlane ((int) gridDim.x);
   int blkR = blockIdx.x, idxR = 0;
   auto next_end = [&] ()->int
   {
-    const int e = blkR * PM_S4_GRAB + idxR;
-    if (++idxR == PM_S4_GRAB)
+    const int e = blkR * GRAB + idxR;
+    if (++idxR == GRAB)
       {
         idxR = 0;
         blkR = grid_n + (int) __builtin_amdgcn_readfirstlane ((int) (lane == 0 ? atomicAdd (out.next_end, 1u) : 0u));
       }
     return e;
   };
+  constexpr bool ONE_AHEAD = TIER && PM_S4_AHEAD_T2 == 1;
+  static_assert (!ONE_AHEAD || GRAB == 1, "one end ahead: one end per fetch");
   int eQ = next_end ();
-  int eP = next_end ();
-  int eR = blkR * PM_S4_GRAB + idxR;
+  int eP = ONE_AHEAD ? blkR : next_end ();
+  int eR = blkR * GRAB + idxR;
 
   uint8_t rb[NBT];              // the bytes of the end whose k-mers are formed next
   int rlen = 0, rend = 0;       // ... its length and its number (second tier: from the list)
@@ -307,7 +331,7 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
       load_bytes (eQ);
       SQ = stage_p (kQ, lenQ, endQ, [] () { });
     }
-  if (eP < n_work)
+  if (!ONE_AHEAD && eP < n_work)
     load_bytes (eP);
 
   // the end whose hits are still in LDS (written out one iteration later, see O below)
@@ -477,14 +501,17 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
                 sh.a.x.sg[64 + lane] = (uint8_t) tgB;
               }
             pm_wave_sync ();
+            // (TAIL_DEPTH loads of 64 elements are requested before the first is stored.  Second tier: an end has 1,425 to 5,696
+            // positions, nearly all of them tail elements, and one wave a SIMD: at two loads a trip every trip's latency lay open)
+            constexpr int TD = SH::TAIL_DEPTH;
             int carry = 0;
 #pragma unroll 1
-            for (int t0 = 0; t0 < M; t0 += 128)
+            for (int t0 = 0; t0 < M; t0 += 64 * TD)
               {
-                uint32_t val[2];
-                int own[2];
+                uint32_t val[TD];
+                int own[TD];
 #pragma unroll
-                for (int j = 0; j < 2; j++)
+                for (int j = 0; j < TD; j++)
                   {
                     const int t = t0 + 64 * j + lane;
                     const int m = t < M ? (int) sh.a.x.mark[t] : 0;
@@ -496,7 +523,7 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
                       val[j] = ix.multi[(size_t) (sh.a.x.src[o - 1] + (uint32_t) t)];
                   }
 #pragma unroll
-                for (int j = 0; j < 2; j++)
+                for (int j = 0; j < TD; j++)
                   {
                     const int t = t0 + 64 * j + lane;
                     if (t < M)
@@ -512,23 +539,59 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
                   }
               }
           };
+          // the first units of the 128 records of the round that starts at record i0, lane = record (two a lane): requested here
+          auto headers = [&] (const int i0, uint4 & hA, uint4 & hB, uint32_t & uA, uint32_t & uB, uint32_t & tgA, uint32_t & tgB)
+          {
+            hA = make_uint4 (0u, 0u, 0u, 0u);
+            hB = make_uint4 (0u, 0u, 0u, 0u);
+            uA = uB = tgA = tgB = 0u;
+            if (i0 + lane < nm)
+              {
+                uA = sh.key[SH::KCAP - 1 - (i0 + lane)];
+                tgA = sh.tag[SH::KCAP - 1 - (i0 + lane)];
+                hA = *(const uint4 *) (ix.multi + (size_t) uA * 4);
+              }
+            if (i0 + 64 + lane < nm)
+              {
+                uB = sh.key[SH::KCAP - 1 - (i0 + 64 + lane)];
+                tgB = sh.tag[SH::KCAP - 1 - (i0 + 64 + lane)];
+                hB = *(const uint4 *) (ix.multi + (size_t) uB * 4);
+              }
+          };
+          // (second tier: the headers of round r + 1 are requested before round r's records are scanned and their tails walked.  Their
+          // units lie at the list's back, which no round but the last may reach: `limit` below)
+          uint4 hA_n, hB_n;     // (written by `headers` before they are read)
+          uint32_t uA_n, uB_n, tgA_n, tgB_n;
+          constexpr bool HDR_AHEAD = TIER && PM_S4_HDR_AHEAD_T2;
+          if constexpr (HDR_AHEAD)
+            if (nm > 0)
+              headers (0, hA_n, hB_n, uA_n, uB_n, tgA_n, tgB_n);
 #pragma unroll 1
           for (int i0 = 0; i0 < nm && !big; i0 += 128)
             {
               uint4 hA = make_uint4 (0u, 0u, 0u, 0u), hB = make_uint4 (0u, 0u, 0u, 0u);
               uint32_t uA = 0, uB = 0, tgA = 0, tgB = 0;
               const bool vA = i0 + lane < nm, vB = i0 + 64 + lane < nm;
-              if (vA)
+              if constexpr (HDR_AHEAD)
                 {
-                  uA = sh.key[SH::KCAP - 1 - (i0 + lane)];
-                  tgA = sh.tag[SH::KCAP - 1 - (i0 + lane)];
-                  hA = *(const uint4 *) (ix.multi + (size_t) uA * 4);
+                  hA = hA_n, hB = hB_n, uA = uA_n, uB = uB_n, tgA = tgA_n, tgB = tgB_n;
+                  if (i0 + 128 < nm)
+                    headers (i0 + 128, hA_n, hB_n, uA_n, uB_n, tgA_n, tgB_n);
                 }
-              if (vB)
+              else
                 {
-                  uB = sh.key[SH::KCAP - 1 - (i0 + 64 + lane)];
-                  tgB = sh.tag[SH::KCAP - 1 - (i0 + 64 + lane)];
-                  hB = *(const uint4 *) (ix.multi + (size_t) uB * 4);
+                  if (vA)
+                    {
+                      uA = sh.key[SH::KCAP - 1 - (i0 + lane)];
+                      tgA = sh.tag[SH::KCAP - 1 - (i0 + lane)];
+                      hA = *(const uint4 *) (ix.multi + (size_t) uA * 4);
+                    }
+                  if (vB)
+                    {
+                      uB = sh.key[SH::KCAP - 1 - (i0 + 64 + lane)];
+                      tgB = sh.tag[SH::KCAP - 1 - (i0 + 64 + lane)];
+                      hB = *(const uint4 *) (ix.multi + (size_t) uB * 4);
+                    }
                 }
 #ifdef PEMAP_TIMING_PROBES
               { const uint32_t w_ = hA.x + hB.x; asm volatile ("" :: "v" (w_)); }      // (the loads have landed)
@@ -568,7 +631,7 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
       auto out_and_next = [&] ()
       {
         flush_out ();
-        if (lane == 0 && idxR == PM_S4_GRAB - 1)
+        if (lane == 0 && idxR == GRAB - 1)
           raw_next = atomicInc (out.next_end, 0xFFFFFFFFu);
       };
       // ---- P: the next end's k-mers and entry requests (its bytes arrived during the previous iteration); R: the bytes of the end after
@@ -582,10 +645,14 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
       // wait; the table lines it then requested were never in flight across the vote as its comments said)
       __builtin_amdgcn_s_waitcnt (0x0F70);      // vmcnt(0)
       if (eP < n_work)
-        SP = stage_p (kP, lenP, endP, out_and_next);
+        {
+          if constexpr (ONE_AHEAD)
+            load_bytes (eP);
+          SP = stage_p (kP, lenP, endP, out_and_next);
+        }
       else
         out_and_next ();
-      if (eR < n_work)
+      if (!ONE_AHEAD && eR < n_work)
         load_bytes (eR);
       PM_S4_T (5);
       // ---- V: find_matches (pemapper.c:2189-2289) on the list in LDS
@@ -931,7 +998,7 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
       PM_S4_T (11);
       eQ = eP;
       eP = eR;
-      if (idxR == PM_S4_GRAB - 1)
+      if (idxR == GRAB - 1)
         {
           const int raw_s = __builtin_amdgcn_readfirstlane ((int) raw_next);
           blkR = grid_n + raw_s;
@@ -942,7 +1009,9 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
         }
       else
         idxR++;
-      eR = blkR * PM_S4_GRAB + idxR;
+      eR = blkR * GRAB + idxR;
+      if constexpr (ONE_AHEAD)
+        eP = eR;
       SQ = SP;
       lenQ = lenP;
       endQ = endP;
@@ -952,7 +1021,7 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
 #ifdef PEMAP_TIMING_PROBES
   if (lane == 0)
     for (int i = 0; i < 32; i++)
-      atomicAdd (&pm_s4_probe[i], pacc[i]);
+      atomicAdd (&pm_s4_probe[TIER][i], pacc[i]);
 #endif
   if (lane == 0 && n_pos)
     atomicAdd (out.positions, n_pos);

@@ -432,7 +432,7 @@ int pecall_dev_call_records (pecall_dev * dev, const void *const *recs, const ui
  * kernel runs, because they become addresses: iv_count[k] >= 1, iv_first[k] + iv_count[k] <= span, and
  * iv_first[k] + iv_count[k] <= iv_first[k + 1] (ascending, disjoint; adjacent is fine).  A violation is a non-zero return with a
  * message, never PECALL_RC_UNORDERED.  n_iv == 0: 0, *n_cols = 0, nothing staged.  Limits as above.  pecall_dev_sites_gather,
- * _sites_run / _collect, _sites_base_text and _sites_merge_ms (mark = the marks from the intervals and the records' check) follow a
+ * _sites_run / _collect, _sites_base_text / _gz and _sites_merge_ms (mark = the marks from the intervals and the records' check) follow a
  * guided stage unchanged.  pecall_dev_call_records_guided is the one-call form, as pecall_dev_call_records. */
 int pecall_dev_sites_stage_records_guided (pecall_dev * dev, const void *const *recs, const uint64_t * n_recs, int indiv, uint32_t p0,
                                            uint32_t span, const char *ref_letters, uint32_t ref_len, const uint32_t * iv_first,
@@ -467,6 +467,25 @@ int pecall_dev_sites_base_text (pecall_dev * dev, const char *names, const uint3
                                 const int32_t * contig, const uint32_t * pos, const char *ref_char /* [columns of the last call] */ ,
                                 char *text, uint64_t text_cap, uint64_t * n_text, uint32_t * hole_site, uint64_t * hole_at,
                                 uint64_t hole_cap, uint64_t * n_holes, float *kernel_ms3 /* may be NULL: length, scan, fill */ );
+/* ---- PECaller: the same rows as gzip members, deflated on the device ----
+ * Same inputs and the same validity window as pecall_dev_sites_base_text.  The text that call returns stays on the device and is
+ * deflated there by the rule of pecaller_amd/csrc/pecall_gz_rule.h: the text between two holes (or a text end and a hole) is cut into
+ * pieces of at most PCG_PIECE bytes, a piece becomes one complete gzip member (fixed Huffman codes, or a stored block where that is
+ * no longer), no member reaches across a hole.
+ *   gz[gz_cap], *n_gz                the members in text order: inflating gz[0 .. *n_gz) gives exactly the bytes
+ *                                    pecall_dev_sites_base_text returns for the same arguments.  An empty text gives *n_gz = 0 and no
+ *                                    member.  They arrive in pieces of 16 MB, directly where pecall_dev_pin_host page-locked the
+ *                                    buffer, else through a page-locked block.
+ *   hole_site[hole_cap], hole_gz_at[], *n_holes   ascending: the host's row of column hole_site[k], as a member or members of the
+ *                                    host's making, belongs at byte hole_gz_at[k] of gz, which is a member boundary or *n_gz
+ *   *n_text                          the inflated length
+ *   kernel_ms5 (may be NULL)         HIP-event durations in ms: length, scan, fill, deflate, pack
+ * Fails as pecall_dev_sites_base_text does; when gz_cap or hole_cap is too small *n_gz and *n_holes say what is needed. */
+int pecall_dev_sites_base_gz (pecall_dev * dev, const char *names, const uint32_t * name_off /* [n_contigs + 1] */ , int n_contigs,
+                              const int32_t * contig, const uint32_t * pos, const char *ref_char /* [columns of the last call] */ ,
+                              unsigned char *gz, uint64_t gz_cap, uint64_t * n_gz, uint32_t * hole_site, uint64_t * hole_gz_at,
+                              uint64_t hole_cap, uint64_t * n_holes, uint64_t * n_text,
+                              float *kernel_ms5 /* may be NULL: length, scan, fill, deflate, pack */ );
 /* use_pedfile = y (pecaller.c:376-392, 561-604): parents as sample indices (-1 = not sampled), sex (1 male, 2 female), and each
  * sample's kids in ped-file order: kids of i = kid_list[kid_off[i] .. kid_off[i + 1]).  denovo_rate = argv[11] (<= theta).
  * The configuration prior then carries no_denovo * ln(denovo_rate) (add_denovo, 2396-2445, tables of main 312-374).

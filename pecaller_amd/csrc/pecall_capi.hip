@@ -13,6 +13,7 @@
 #include "pecall_site.hip.h"
 #include "pecall_merge.hip.h"
 #include "pecall_rows.hip.h"
+#include "pecall_gz.hip.h"
 
 static char g_pc_err[512] = "";
 #define PCS_SLOTS 3             // staging buffers of the seam's pipeline (chunks in flight between the two host copies)
@@ -218,6 +219,30 @@ static void pcr_free (PcrState & w)
       *e = nullptr;
 }
 
+// pecall_dev_sites_base_gz (pecall_gz.hip.h): the runs' piece counts and their scan; per piece its first byte, its length and its member's
+// length (scanned: its place in the packed array); the slots; the packed members; the holes' places among them
+struct PcgState
+{
+  unsigned long long *d_run = nullptr, *d_run_sum = nullptr, *d_piece_at = nullptr, *d_member = nullptr, *d_member_sum = nullptr, *d_hole_gz_at = nullptr;
+  unsigned *d_piece_len = nullptr;
+  unsigned char *d_slots = nullptr, *d_gz = nullptr;
+  PcgCtl *d_ctl = nullptr;
+  size_t cap_runs = 0, cap_pieces = 0, cap_slots = 0, cap_holes = 0;       // cap_runs, cap_pieces: padded to PCG_SCAN_TILE
+  char *h_stage = nullptr;      // [PcgCtl][hole columns][hole places]
+  size_t h_stage_bytes = 0;
+  hipEvent_t ev[3] = { };       // around the deflate (runs, scan, table, deflate kernel) and the pack (scan, pack, holes)
+};
+
+static void pcg_free (PcgState & g)
+{
+  pc_free (g.d_run, g.d_run_sum, g.d_piece_at, g.d_member, g.d_member_sum, g.d_hole_gz_at, g.d_piece_len, g.d_slots, g.d_gz, g.d_ctl);
+  pc_host_free (g.h_stage);
+  g.cap_runs = g.cap_pieces = g.cap_slots = g.cap_holes = g.h_stage_bytes = 0;
+  for (hipEvent_t & e : g.ev)
+    if (e && hipEventDestroy (e) == hipSuccess)
+      e = nullptr;
+}
+
 struct PcsChunk
 {
   hipEvent_t h2d, fast, call, d2h, heavy;       // a chunk's columns in, shortcut kernel done, beam search and what follows it done, results out, early beam search done
@@ -237,6 +262,7 @@ struct pecall_dev
   PcsSparse sp;
   PcmState mg;
   PcrState rows;
+  PcgState gz;
   // pedigree
   int ped_indiv = 0, ped_haploid = 0;
   double denovo_rate = 0;
@@ -375,6 +401,7 @@ extern "C" void pecall_dev_destroy (pecall_dev * d)
   pcs_sparse_free (d->sp);
   pcm_free (d->mg);
   pcr_free (d->rows);
+  pcg_free (d->gz);
   pc_free (d->d_chunk_ctr, d->d_heavy_ctr);
   pc_host_free (d->h_ctrs);
   for (int i = 0; i < PCS_SLOTS; i++)
@@ -1776,15 +1803,15 @@ static int pcr_upload (pecall_dev * d, void *dev, const void *host, char *stage,
   return 0;
 }
 
-// the text back, PCR_PIECE at a time on the device-to-host stream, behind event `filled`
-static int pcr_text_back (pecall_dev * d, hipEvent_t filled, char *text, size_t total)
+// the text (or the members made of it) back, PCR_PIECE at a time on the device-to-host stream, behind event `filled`
+static int pcr_text_back (pecall_dev * d, hipEvent_t filled, const char *d_text, char *text, size_t total)
 {
   PcrState & w = d->rows;
   PCCHK (d, hipStreamWaitEvent (d->stream_d2h, filled, 0));
   if (pm_host_pin_lookup (text, total))
     {
       for (size_t at = 0; at < total; at += PCR_PIECE)
-        PCCHK (d, hipMemcpyAsync (text + at, w.d_text + at, std::min (PCR_PIECE, total - at), hipMemcpyDeviceToHost, d->stream_d2h));
+        PCCHK (d, hipMemcpyAsync (text + at, d_text + at, std::min (PCR_PIECE, total - at), hipMemcpyDeviceToHost, d->stream_d2h));
       PCCHK (d, hipStreamSynchronize (d->stream_d2h));
       return 0;
     }
@@ -1797,7 +1824,7 @@ static int pcr_text_back (pecall_dev * d, hipEvent_t filled, char *text, size_t 
     {
       if (k < pieces)
         {
-          PCCHK (d, hipMemcpyAsync (w.h_text[k & 1], w.d_text + k * PCR_PIECE, std::min (PCR_PIECE, total - k * PCR_PIECE), hipMemcpyDeviceToHost, d->stream_d2h));
+          PCCHK (d, hipMemcpyAsync (w.h_text[k & 1], d_text + k * PCR_PIECE, std::min (PCR_PIECE, total - k * PCR_PIECE), hipMemcpyDeviceToHost, d->stream_d2h));
           PCCHK (d, hipEventRecord (w.ev_piece[k & 1], d->stream_d2h));
         }
       if (k > 0)
@@ -1813,9 +1840,10 @@ static int pcr_text_back (pecall_dev * d, hipEvent_t filled, char *text, size_t 
 // Replaces the .base half of the row formatting (emit_rows of pecaller_main.c; the per-sample gzprintf loop of pecaller.c:1760-1775)
 // for the columns whose posteriors are all exactly 1.  The host waits twice: for the text's length and the number of holes (the
 // caller's buffers are checked against them, the device text is sized by it), and for the end.
-extern "C" int pecall_dev_sites_base_text (pecall_dev * d, const char *names, const uint32_t * name_off, int n_contigs, const int32_t * contig, const uint32_t * pos,
-                                           const char *ref_char, char *text, uint64_t text_cap, uint64_t * n_text, uint32_t * hole_site, uint64_t * hole_at,
-                                           uint64_t hole_cap, uint64_t * n_holes, float *kernel_ms3)
+// want_text false (pecall_dev_sites_base_gz): the text and the holes' offsets stay on the device, the capacities are the caller's to check.
+static int pcr_base_impl (pecall_dev * d, const char *who, bool want_text, const char *names, const uint32_t * name_off, int n_contigs, const int32_t * contig,
+                          const uint32_t * pos, const char *ref_char, char *text, uint64_t text_cap, uint64_t * n_text, uint32_t * hole_site, uint64_t * hole_at,
+                          uint64_t hole_cap, uint64_t * n_holes, float *kernel_ms3)
 {
   PCCHK (d, hipSetDevice (d->device));
   if (n_text)
@@ -1827,25 +1855,25 @@ extern "C" int pecall_dev_sites_base_text (pecall_dev * d, const char *names, co
   const long n = d->result_sites;
   const int N = d->staged_indiv;
   if (n <= 0)
-    return pc_fail (d, "sites_base_text: no call's results are on the device (call_sites, call_sites_sparse, call_records or sites_run first)");
+    return pc_fail (d, "%s: no call's results are on the device (call_sites, call_sites_sparse, call_records or sites_run first)", who);
   if (!names || !name_off || n_contigs < 1 || !contig || !pos || !ref_char || !n_text || !n_holes)
-    return pc_fail (d, "sites_base_text: names, name_off, at least one contig, contig, pos, ref_char, n_text and n_holes are required");
+    return pc_fail (d, "%s: names, name_off, at least one contig, contig, pos, ref_char, n_text and n_holes are required", who);
   if ((text_cap && !text) || (hole_cap && (!hole_site || !hole_at)))
-    return pc_fail (d, "sites_base_text: a capacity without its array");
+    return pc_fail (d, "%s: a capacity without its array", who);
   // ---- the small things, before a kernel turns them into addresses
   unsigned max_name = 0;
   for (int c = 0; c < n_contigs; c++)
     {
       if (name_off[c + 1] < name_off[c] || name_off[c + 1] - name_off[c] > PCR_MAX_NAME)
-        return pc_fail (d, "sites_base_text: name_off[%d..%d] = %u, %u: the offsets ascend and a name has at most %u bytes", c, c + 1, name_off[c], name_off[c + 1], PCR_MAX_NAME);
+        return pc_fail (d, "%s: name_off[%d..%d] = %u, %u: the offsets ascend and a name has at most %u bytes", who, c, c + 1, name_off[c], name_off[c + 1], PCR_MAX_NAME);
       max_name = std::max (max_name, name_off[c + 1] - name_off[c]);
     }
   for (long s = 0; s < n; s++)
     {
       if (contig[s] < 0 || contig[s] >= n_contigs)
-        return pc_fail (d, "sites_base_text: contig[%ld] = %d, there are %d contigs", s, contig[s], n_contigs);
+        return pc_fail (d, "%s: contig[%ld] = %d, there are %d contigs", who, s, contig[s], n_contigs);
       if (pos[s] > PCR_MAX_POS)
-        return pc_fail (d, "sites_base_text: pos[%ld] = %u is beyond %u (the rows print (int) pos)", s, pos[s], PCR_MAX_POS);
+        return pc_fail (d, "%s: pos[%ld] = %u is beyond %u (the rows print (int) pos)", who, s, pos[s], PCR_MAX_POS);
     }
   const size_t S = (size_t) n, pad = (S + 1 + PCR_SCAN_TILE - 1) / PCR_SCAN_TILE * PCR_SCAN_TILE, names_bytes = name_off[n_contigs] - name_off[0];
   const unsigned nb = (unsigned) (pad / PCR_SCAN_TILE);
@@ -1887,8 +1915,8 @@ extern "C" int pecall_dev_sites_base_text (pecall_dev * d, const char *names, co
   const size_t total = (size_t) ctl.n_text, holes = (size_t) ctl.n_holes;
   *n_text = ctl.n_text;
   *n_holes = ctl.n_holes;
-  if (ctl.n_text > text_cap || ctl.n_holes > hole_cap)
-    return pc_fail (d, "sites_base_text: the text has %llu bytes and %llu rows are left to the host, the arrays hold %llu and %llu (n_text and n_holes say what is needed)",
+  if (want_text && (ctl.n_text > text_cap || ctl.n_holes > hole_cap))
+    return pc_fail (d, "%s: the text has %llu bytes and %llu rows are left to the host, the arrays hold %llu and %llu (n_text and n_holes say what is needed)", who,
                     ctl.n_text, ctl.n_holes, (unsigned long long) text_cap, (unsigned long long) hole_cap);
   float ms[3] = { 0.0f, 0.0f, 0.0f }, a = 0.0f;
   PCCHK (d, hipEventElapsedTime (&ms[0], w.ev[0], w.ev[1]));
@@ -1918,15 +1946,15 @@ extern "C" int pecall_dev_sites_base_text (pecall_dev * d, const char *names, co
           PCCHK (d, hipGetLastError ());
         }
       PCCHK (d, hipEventRecord (w.ev[5], d->stream));
-      if (holes)
+      if (holes && want_text)
         {
           PCCHK (d, hipMemcpyAsync (st + at_hsite, w.d_hole_site, holes * 4, hipMemcpyDeviceToHost, d->stream));
           PCCHK (d, hipMemcpyAsync (st + at_hat, w.d_hole_at, holes * 8, hipMemcpyDeviceToHost, d->stream));
         }
-      if (total)
-        PCTRY (pcr_text_back (d, w.ev[5], text, total));
+      if (total && want_text)
+        PCTRY (pcr_text_back (d, w.ev[5], w.d_text, text, total));
       PCCHK (d, hipStreamSynchronize (d->stream));
-      if (holes)
+      if (holes && want_text)
         {
           memcpy (hole_site, st + at_hsite, holes * 4);
           memcpy (hole_at, st + at_hat, holes * 8);
@@ -1937,6 +1965,172 @@ extern "C" int pecall_dev_sites_base_text (pecall_dev * d, const char *names, co
     }
   if (kernel_ms3)
     memcpy (kernel_ms3, ms, sizeof ms);
+  return 0;
+}
+
+extern "C" int pecall_dev_sites_base_text (pecall_dev * d, const char *names, const uint32_t * name_off, int n_contigs, const int32_t * contig, const uint32_t * pos,
+                                           const char *ref_char, char *text, uint64_t text_cap, uint64_t * n_text, uint32_t * hole_site, uint64_t * hole_at,
+                                           uint64_t hole_cap, uint64_t * n_holes, float *kernel_ms3)
+{
+  return pcr_base_impl (d, "sites_base_text", true, names, name_off, n_contigs, contig, pos, ref_char, text, text_cap, n_text, hole_site, hole_at, hole_cap, n_holes,
+                        kernel_ms3);
+}
+
+// ---- the same rows as gzip members (pecall_gz.hip.h)
+
+static int pcg_ensure (pecall_dev * d, size_t pad_runs, size_t pad_pieces, size_t slot_bytes, size_t holes)
+{
+  PcgState & g = d->gz;
+  if (!g.d_ctl)
+    {
+      for (hipEvent_t & e : g.ev)
+        if (!e)
+          PCCHK (d, hipEventCreate (&e));
+      PCCHK (d, hipMalloc ((void **) &g.d_ctl, sizeof (PcgCtl)));
+    }
+  if (pad_runs > g.cap_runs)
+    {
+      pc_free (g.d_run, g.d_run_sum);
+      g.cap_runs = 0;
+      PCCHK (d, hipMalloc ((void **) &g.d_run, pad_runs * sizeof (unsigned long long)));
+      PCCHK (d, hipMalloc ((void **) &g.d_run_sum, pad_runs / PCG_SCAN_TILE * sizeof (unsigned long long)));
+      g.cap_runs = pad_runs;
+    }
+  if (pad_pieces > g.cap_pieces)
+    {
+      pc_free (g.d_piece_at, g.d_member, g.d_member_sum, g.d_piece_len);
+      g.cap_pieces = 0;
+      PCCHK (d, hipMalloc ((void **) &g.d_piece_at, pad_pieces * sizeof (unsigned long long)));
+      PCCHK (d, hipMalloc ((void **) &g.d_member, pad_pieces * sizeof (unsigned long long)));
+      PCCHK (d, hipMalloc ((void **) &g.d_member_sum, pad_pieces / PCG_SCAN_TILE * sizeof (unsigned long long)));
+      PCCHK (d, hipMalloc ((void **) &g.d_piece_len, pad_pieces * sizeof (unsigned)));
+      g.cap_pieces = pad_pieces;
+    }
+  if (slot_bytes > g.cap_slots)
+    {
+      pc_free (g.d_slots, g.d_gz);
+      g.cap_slots = 0;
+      PCCHK (d, hipMalloc ((void **) &g.d_slots, slot_bytes + slot_bytes / 8));
+      PCCHK (d, hipMalloc ((void **) &g.d_gz, slot_bytes + slot_bytes / 8));
+      g.cap_slots = slot_bytes + slot_bytes / 8;
+    }
+  if (holes + 1 > g.cap_holes)
+    {
+      pc_free (g.d_hole_gz_at);
+      pc_host_free (g.h_stage);
+      g.cap_holes = g.h_stage_bytes = 0;
+      const size_t cap = holes + holes / 4 + 1;
+      PCCHK (d, hipMalloc ((void **) &g.d_hole_gz_at, cap * sizeof (unsigned long long)));
+      PCCHK (d, hipHostMalloc ((void **) &g.h_stage, 64 + pcm_up64 (cap * 4) + cap * 8, hipHostMallocDefault));
+      g.cap_holes = cap;
+      g.h_stage_bytes = 64 + pcm_up64 (cap * 4) + cap * 8;
+    }
+  return 0;
+}
+
+// exclusive prefix sum of val[0 .. pad) in place, pad a multiple of PCG_SCAN_TILE; the sum of all goes to *total
+static int pcg_scan (pecall_dev * d, unsigned long long *val, unsigned long long *sum, size_t pad, unsigned long long *total)
+{
+  const unsigned nb = (unsigned) (pad / PCG_SCAN_TILE);
+  hipLaunchKernelGGL (pcg_scan_reduce_kernel, dim3 (nb), dim3 (PCG_BLOCK), 0, d->stream, (const ulonglong4 *) val, sum);
+  PCCHK (d, hipGetLastError ());
+  hipLaunchKernelGGL (pcg_scan_top_kernel, dim3 (1), dim3 (PCG_TOP), 0, d->stream, sum, nb, total);
+  PCCHK (d, hipGetLastError ());
+  hipLaunchKernelGGL (pcg_scan_apply_kernel, dim3 (nb), dim3 (PCG_BLOCK), 0, d->stream, (ulonglong4 *) val, (const unsigned long long *) sum);
+  PCCHK (d, hipGetLastError ());
+  return 0;
+}
+
+// The text of pecall_dev_sites_base_text for the same arguments, deflated where it lies: complete gzip members in text order, none
+// across a hole.  The host waits where that call waits, and once more for the packed length.
+extern "C" int pecall_dev_sites_base_gz (pecall_dev * d, const char *names, const uint32_t * name_off, int n_contigs, const int32_t * contig, const uint32_t * pos,
+                                         const char *ref_char, unsigned char *gz, uint64_t gz_cap, uint64_t * n_gz, uint32_t * hole_site, uint64_t * hole_gz_at,
+                                         uint64_t hole_cap, uint64_t * n_holes, uint64_t * n_text, float *kernel_ms5)
+{
+  PCCHK (d, hipSetDevice (d->device));
+  if (n_gz)
+    *n_gz = 0;
+  if (kernel_ms5)
+    kernel_ms5[0] = kernel_ms5[1] = kernel_ms5[2] = kernel_ms5[3] = kernel_ms5[4] = 0.0f;
+  if (!n_gz)
+    {
+      if (n_text)
+        *n_text = 0;
+      if (n_holes)
+        *n_holes = 0;
+      return pc_fail (d, "sites_base_gz: n_gz is required");
+    }
+  if ((gz_cap && !gz) || (hole_cap && (!hole_site || !hole_gz_at)))
+    {
+      if (n_text)
+        *n_text = 0;
+      if (n_holes)
+        *n_holes = 0;
+      return pc_fail (d, "sites_base_gz: a capacity without its array");
+    }
+  float ms[5] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+  PCTRY (pcr_base_impl (d, "sites_base_gz", false, names, name_off, n_contigs, contig, pos, ref_char, nullptr, 0, n_text, nullptr, nullptr, 0, n_holes, ms));
+  const size_t total = (size_t) * n_text, holes = (size_t) * n_holes;
+  if (total || holes)
+    {
+      PcrState & w = d->rows;
+      const size_t max_pieces = total / PCG_PIECE + holes + 1;
+      const size_t pad_runs = (holes + 2 + PCG_SCAN_TILE - 1) / PCG_SCAN_TILE * PCG_SCAN_TILE, pad_pieces = (max_pieces + 1 + PCG_SCAN_TILE - 1) / PCG_SCAN_TILE * PCG_SCAN_TILE;
+      PCTRY (pcg_ensure (d, pad_runs, pad_pieces, pcg_slot_bytes (total, max_pieces), holes));
+      PcgState & g = d->gz;
+      PCCHK (d, hipEventRecord (g.ev[0], d->stream));
+      hipLaunchKernelGGL (pcg_runs_kernel, dim3 ((unsigned) (pad_runs / PCG_BLOCK)), dim3 (PCG_BLOCK), 0, d->stream, (const unsigned long long *) w.d_hole_at,
+                          (unsigned long long) holes, (unsigned long long) total, (unsigned long long) pad_runs, g.d_run);
+      PCCHK (d, hipGetLastError ());
+      PCTRY (pcg_scan (d, g.d_run, g.d_run_sum, pad_runs, &g.d_ctl->n_pieces));
+      hipLaunchKernelGGL (pcg_table_kernel, dim3 ((unsigned) ((max_pieces + PCG_BLOCK - 1) / PCG_BLOCK)), dim3 (PCG_BLOCK), 0, d->stream,
+                          (const unsigned long long *) w.d_hole_at, (unsigned long long) holes, (unsigned long long) total, (const unsigned long long *) g.d_run,
+                          (const PcgCtl *) g.d_ctl, (unsigned long long) max_pieces, g.d_piece_at, g.d_piece_len);
+      PCCHK (d, hipGetLastError ());
+      PCCHK (d, hipMemsetAsync (g.d_member, 0, pad_pieces * sizeof (unsigned long long), d->stream));
+      hipLaunchKernelGGL (pcg_deflate_kernel, dim3 ((unsigned) max_pieces), dim3 (PCG_BLOCK), 0, d->stream, (const char *) w.d_text, (unsigned long long) total,
+                          (unsigned long long) (w.cap_text & ~(size_t) 15), (const unsigned long long *) g.d_piece_at, (const unsigned *) g.d_piece_len, (const PcgCtl *) g.d_ctl,
+                          g.d_slots, (unsigned long long) g.cap_slots, g.d_member);
+      PCCHK (d, hipGetLastError ());
+      PCCHK (d, hipEventRecord (g.ev[1], d->stream));
+      PCTRY (pcg_scan (d, g.d_member, g.d_member_sum, pad_pieces, &g.d_ctl->n_gz));
+      hipLaunchKernelGGL (pcg_pack_kernel, dim3 ((unsigned) max_pieces), dim3 (PCG_BLOCK), 0, d->stream, (const unsigned char *) g.d_slots, (unsigned long long) g.cap_slots,
+                          (const unsigned long long *) g.d_piece_at, (const unsigned long long *) g.d_member, (const PcgCtl *) g.d_ctl, g.d_gz,
+                          (unsigned long long) g.cap_slots);
+      PCCHK (d, hipGetLastError ());
+      if (holes)
+        {
+          hipLaunchKernelGGL (pcg_holes_kernel, dim3 ((unsigned) ((holes + PCG_BLOCK - 1) / PCG_BLOCK)), dim3 (PCG_BLOCK), 0, d->stream, (const unsigned long long *) g.d_run,
+                              (const unsigned long long *) g.d_member, (unsigned long long) holes, (unsigned long long) max_pieces, g.d_hole_gz_at);
+          PCCHK (d, hipGetLastError ());
+        }
+      PCCHK (d, hipEventRecord (g.ev[2], d->stream));
+      char *st = g.h_stage;
+      const size_t at_site = 64, at_place = at_site + pcm_up64 (g.cap_holes * 4);
+      PCCHK (d, hipMemcpyAsync (st, g.d_ctl, sizeof (PcgCtl), hipMemcpyDeviceToHost, d->stream));
+      if (holes)
+        {
+          PCCHK (d, hipMemcpyAsync (st + at_site, w.d_hole_site, holes * 4, hipMemcpyDeviceToHost, d->stream));
+          PCCHK (d, hipMemcpyAsync (st + at_place, g.d_hole_gz_at, holes * 8, hipMemcpyDeviceToHost, d->stream));
+        }
+      PCCHK (d, hipStreamSynchronize (d->stream));
+      const PcgCtl ctl = *(const PcgCtl *) st;
+      *n_gz = ctl.n_gz;
+      PCCHK (d, hipEventElapsedTime (&ms[3], g.ev[0], g.ev[1]));
+      PCCHK (d, hipEventElapsedTime (&ms[4], g.ev[1], g.ev[2]));
+      if (ctl.n_gz > gz_cap || holes > hole_cap)
+        return pc_fail (d, "sites_base_gz: the members have %llu bytes and %llu rows are left to the host, the arrays hold %llu and %llu (n_gz and n_holes say what is needed)",
+                        ctl.n_gz, (unsigned long long) holes, (unsigned long long) gz_cap, (unsigned long long) hole_cap);
+      if (holes)
+        {
+          memcpy (hole_site, st + at_site, holes * 4);
+          memcpy (hole_gz_at, st + at_place, holes * 8);
+        }
+      if (ctl.n_gz)
+        PCTRY (pcr_text_back (d, g.ev[2], (const char *) g.d_gz, (char *) gz, (size_t) ctl.n_gz));
+    }
+  if (kernel_ms5)
+    memcpy (kernel_ms5, ms, sizeof ms);
   return 0;
 }
 

@@ -35,10 +35,13 @@
 #include "../../include/pemap_hip.h"
 #include "host_io.h"
 #include "pecall_row_len.h"
+#include "pecall_gz_rule.h"
 
 /* (weak: the program links against a library without this entry too -- an older build, or the tests' host-only stand-in -- and
    PECALLER_DEVICE_ROWS=1 then ends the run with a message) */
 extern __typeof__ (pecall_dev_sites_base_text) pecall_dev_sites_base_text __attribute__ ((weak));
+/* (weak for the same reason: PECALLER_DEVICE_GZ=1 ends the run with a message where the library lacks the entry) */
+extern __typeof__ (pecall_dev_sites_base_gz) pecall_dev_sites_base_gz __attribute__ ((weak));
 /* (weak for the same reason: PECALLER_DEVICE_GUIDE=1 ends the run with a message where the library lacks the entry) */
 extern __typeof__ (pecall_dev_call_records_guided) pecall_dev_call_records_guided __attribute__ ((weak));
 
@@ -155,8 +158,10 @@ typedef struct
      -- those of the columns whose posteriors are all 1 -- and the holes: the host's row of column hole_site[k] (= post_site[k])
      belongs at byte hole_at[k] of dtext.  The rows stage notes where its row of hole k lies (hole_off: in the formatting thread's
      buffer; hole_src, hole_len) and how many bytes of host rows lie in front of it (hole_pre, one more entry than holes). */
+  /* PECALLER_DEVICE_GZ=1 on top of it: dtext holds that text as the gzip members the device made of it (pecall_dev_sites_base_gz),
+     n_dtext their bytes, n_inflated the text's; hole_at[k] is a member boundary of dtext, where the host's member of hole k belongs */
   char *dtext;
-  uint64_t dtext_cap, n_dtext;
+  uint64_t dtext_cap, n_dtext, n_inflated;
   int dtext_pinned;
   uint32_t *hole_site, *hole_len;
   uint64_t *hole_at, *hole_off, *hole_pre;
@@ -384,6 +389,10 @@ struct run_s
   uint32_t *name_off;
   size_t max_name;
   long rows_dev, rows_hole;
+  /* device_gz (PECALLER_DEVICE_GZ=1, with device_rows): that text is deflated on the device too and goes to the file as it comes back;
+     the host's rows of the holes go in between as members of stored blocks (gzb: the one being put together) */
+  int device_gz;
+  unsigned long long gz_text, gz_bytes;
   /* set once (start_pipeline).  tile: columns per device call, and genome positions per range of the stream merge -- a call has a fixed
      part (two kernel launches, the transfers' latencies), so tiles are large.  mg_chunk: slots per work item of the column pass.
      guide_range_min: positions of a guide interval left from which the streams are walked in parallel.  post_cap: a tile's first list */
@@ -395,6 +404,7 @@ struct run_s
   FILE *snpfile, *distfile;
   gzFile pilefile;
   sbuf ob;                      /* rows of <outfile>.base.gz on their way to the gz writer */
+  sbuf gzb;
   ref_t ref;
   sample_t *sm;
   int indiv;
@@ -470,7 +480,8 @@ run_jobs (void *(*fn) (void *), emit_job * jobs, int threads)
 }
 
 /* <outfile>.base.gz text of a tile whose template rows came from the device: the device's text with the rows the formatting threads
-   made of the holes put in at their places, appended to r->ob */
+   made of the holes put in at their places, appended to r->ob.  With device_gz: the holes' rows are found and counted, nothing is
+   copied. */
 static void
 splice_tile (run_t * r, const tile_t * t, int threads)
 {
@@ -490,6 +501,16 @@ splice_tile (run_t * r, const tile_t * t, int threads)
       pre += t->hole_len[k];
     }
   t->hole_pre[t->n_holes] = pre;
+  if (r->device_gz)
+    {
+      /* (the members and the holes' rows go to the file one behind the other: write_tile) */
+      long base_rows = 0;
+      for (int k = 0; k < threads; k++)
+        base_rows += jobs[k].base_rows;
+      r->rows_hole += (long) t->n_holes;
+      r->rows_dev += base_rows - (long) t->n_holes;
+      return;
+    }
   const uint64_t total = t->n_dtext + pre;
   char *out = sb_room (&r->ob, (size_t) total);
   for (int k = 0; k < threads; k++)
@@ -942,13 +963,16 @@ tile_holes_alloc (tile_t * t, uint64_t cap)
 static void
 device_text (run_t * r, tile_t * t)
 {
-  t->n_dtext = t->n_holes = 0;
+  t->n_dtext = t->n_holes = t->n_inflated = 0;
   if (t->n <= 0)
     return;
   for (int again = 0;; again++)
     {
-      const int rc = pecall_dev_sites_base_text (r->pc, r->names, r->name_off, r->ref.no_contigs, t->contig, t->pos, t->ref_char, t->dtext, t->dtext_cap, &t->n_dtext,
-                                                 t->hole_site, t->hole_at, t->hole_cap, &t->n_holes, NULL);
+      const int rc = r->device_gz
+        ? pecall_dev_sites_base_gz (r->pc, r->names, r->name_off, r->ref.no_contigs, t->contig, t->pos, t->ref_char, (unsigned char *) t->dtext, t->dtext_cap, &t->n_dtext,
+                                    t->hole_site, t->hole_at, t->hole_cap, &t->n_holes, &t->n_inflated, NULL)
+        : pecall_dev_sites_base_text (r->pc, r->names, r->name_off, r->ref.no_contigs, t->contig, t->pos, t->ref_char, t->dtext, t->dtext_cap, &t->n_dtext,
+                                      t->hole_site, t->hole_at, t->hole_cap, &t->n_holes, NULL);
       if (!rc)
         return;
       if (again || (t->n_dtext <= t->dtext_cap && t->n_holes <= t->hole_cap))
@@ -990,13 +1014,94 @@ call_tile (run_t * r, tile_t * t)
     device_text (r, t);
 }
 
+/* the rows of holes [k0, k1), which belong at one place, as one gzip member of stored blocks (pecall_gz_rule.h's ten bytes in front,
+   zlib's crc32 behind): no deflateInit per hole */
+static void
+hole_member (run_t * r, const tile_t * t, uint64_t k0, uint64_t k1)
+{
+  sbuf *b = &r->gzb;
+  uint64_t bytes = 0;
+  uLong crc = crc32 (0L, Z_NULL, 0);
+  for (uint64_t k = k0; k < k1; k++)
+    bytes += t->hole_len[k];
+  b->n = 0;
+  unsigned char *w = (unsigned char *) sb_room (b, (size_t) (PCG_HEAD + bytes + 5u * (bytes / 65535u + 1u) + PCG_TAIL));
+  for (uint32_t k = 0; k < PCG_HEAD; k++)
+    *w++ = pcg_head_byte (k);
+  /* stored blocks of 65,535 bytes at most, filled from the rows one behind the other */
+  uint64_t left = bytes, k = k0;
+  uint32_t in_row = 0;
+  do
+    {
+      const uint32_t n = left > 65535u ? 65535u : (uint32_t) left;
+      *w++ = left == n;
+      *w++ = (unsigned char) n;
+      *w++ = (unsigned char) (n >> 8);
+      *w++ = (unsigned char) ~n;
+      *w++ = (unsigned char) (~n >> 8);
+      for (uint32_t have = 0; have < n;)
+        {
+          if (in_row == t->hole_len[k])
+            {
+              k++;
+              in_row = 0;
+              continue;
+            }
+          const uint32_t m = t->hole_len[k] - in_row < n - have ? t->hole_len[k] - in_row : n - have;
+          memcpy (w, t->hole_src[k] + in_row, m);
+          crc = crc32 (crc, (const Bytef *) w, m);
+          w += m;
+          in_row += m;
+          have += m;
+        }
+      left -= n;
+    }
+  while (left);
+  for (int x = 0; x < 4; x++)
+    *w++ = (unsigned char) (crc >> (8 * x));
+  for (int x = 0; x < 4; x++)
+    *w++ = (unsigned char) (bytes >> (8 * x));
+  b->n = (size_t) (w - (unsigned char *) b->p);
+  if (fwrite (b->p, 1, b->n, r->outfile.f) != b->n)
+    die ("\n pecaller_hip: write to %s.base.gz failed", r->argv[4]);
+}
+
+/* device_gz: the device's members to the file as they are, the holes' rows as members of the host's making at their places */
+static void
+write_tile_gz (run_t * r, const tile_t * t)
+{
+  uint64_t cur = 0;
+  for (uint64_t k = 0; k < t->n_holes;)
+    {
+      uint64_t k1 = k + 1;
+      while (k1 < t->n_holes && t->hole_at[k1] == t->hole_at[k])
+        k1++;
+      if (t->hole_at[k] < cur || t->hole_at[k] > t->n_dtext)
+        die ("\n pecaller_hip: %s", "a hole's place among the device's members descends or lies beyond them");
+      if (t->hole_at[k] > cur && fwrite (t->dtext + cur, 1, (size_t) (t->hole_at[k] - cur), r->outfile.f) != t->hole_at[k] - cur)
+        die ("\n pecaller_hip: write to %s.base.gz failed", r->argv[4]);
+      cur = t->hole_at[k];
+      hole_member (r, t, k, k1);
+      k = k1;
+    }
+  if (t->n_dtext > cur && fwrite (t->dtext + cur, 1, (size_t) (t->n_dtext - cur), r->outfile.f) != t->n_dtext - cur)
+    die ("\n pecaller_hip: write to %s.base.gz failed", r->argv[4]);
+  if (t->n_dtext || t->n_holes)
+    r->outfile.wrote_any = 1;
+  r->gz_text += t->n_inflated;
+  r->gz_bytes += t->n_dtext;
+}
+
 static void
 write_tile (run_t * r, tile_t * t)
 {
   emit_tile (r, t);
+  /* (with device_gz: the header line, in front of the first tile) */
   if (pgz_write (&r->outfile, r->ob.p, r->ob.n))
     die ("\n pecaller_hip: write to %s.base.gz failed", r->argv[4]);
   r->ob.n = 0;
+  if (r->device_gz && t->dtext)
+    write_tile_gz (r, t);
   r->tot_cols += t->n;
 }
 
@@ -1467,6 +1572,11 @@ start_pipeline (run_t * r)
   r->device_rows = (e = getenv ("PECALLER_DEVICE_ROWS")) && atoi (e) == 1;
   if (r->device_rows && !pecall_dev_sites_base_text)
     die ("\n pecaller_hip: PECALLER_DEVICE_ROWS=1 needs %s, which this library lacks", "pecall_dev_sites_base_text");
+  r->device_gz = (e = getenv ("PECALLER_DEVICE_GZ")) && atoi (e) == 1;
+  if (r->device_gz && !r->device_rows)
+    die ("\n pecaller_hip: PECALLER_DEVICE_GZ=1 needs %s", "PECALLER_DEVICE_ROWS=1: it deflates the rows the device made");
+  if (r->device_gz && !pecall_dev_sites_base_gz)
+    die ("\n pecaller_hip: PECALLER_DEVICE_GZ=1 needs %s, which this library lacks", "pecall_dev_sites_base_gz");
   if (r->device_rows)
     {
       const ref_t *g = &r->ref;
@@ -1919,6 +2029,8 @@ close_outputs (run_t * r)
     printf (" pecaller_hip: device guide merge: %ld columns of %ld intervals in %ld ranges\n", r->dg_cols, r->dg_ivs, r->dg_ranges);
   if (r->device_rows && !r->unordered)
     printf (" pecaller_hip: device rows: %ld rows from the device, %ld holes formatted by the host\n", r->rows_dev, r->rows_hole);
+  if (r->device_gz && !r->unordered)
+    printf (" pecaller_hip: device gz: %llu bytes of text deflated on the device into %llu bytes of gz\n", r->gz_text, r->gz_bytes);
 }
 
 /* everything the run holds is given back (the stages' threads ended in walk); page-locked ranges before their memory and the device */
@@ -1936,6 +2048,7 @@ teardown (run_t * r)
   for (int k = 0; k < MAX_MT; k++)
     free (r->jobs[k].ob.p), free (r->jobs[k].sb.p), free (r->jobs[k].pb.p);
   free (r->ob.p);
+  free (r->gzb.p);
   free (r->names);
   free (r->name_off);
   free (r->sm);

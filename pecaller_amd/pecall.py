@@ -1,5 +1,7 @@
 """ctypes mirror of the pecall_dev_* entry points of include/pemap_hip.h (PECaller per-site genotype likelihoods)."""
 import ctypes as C
+import os
+import re
 import numpy as np
 from .pemap import load_library, PemapError
 
@@ -8,6 +10,9 @@ ALLELES = 6
 RC_UNORDERED = 3  # PECALL_RC_UNORDERED
 # a pileup record: the 16 bytes of the pileup file
 RECORD = np.dtype([("pos", "<u4"), ("counts", "<u2", (6,))])
+# bytes of text a gzip member of base_gz holds at most (csrc/pecall_gz_rule.h, which states the whole rule)
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "pecall_gz_rule.h")) as _f:
+    PCG_PIECE = int(re.search(r"#define\s+PCG_PIECE\s+(\d+)u", _f.read()).group(1))
 
 
 class PecallUnordered(PemapError):
@@ -51,6 +56,7 @@ class PecallDev:
         L.pecall_dev_call_records_guided.argtypes = [vp, vp, vp, i, u32, u32, vp, u32, vp, vp, vp, u32, C.POINTER(C.c_long), vp,
                                                      i, dbl, dbl, vp, vp, vp, u64, vp, vp, vp, vp, vp]
         L.pecall_dev_sites_base_text.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp]
+        L.pecall_dev_sites_base_gz.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), C.POINTER(u64), vp]
         self.L = L
         h = vp()
         if L.pecall_dev_create(C.byref(h), device_id):
@@ -301,6 +307,44 @@ class PecallDev:
         self.text_needed, self.holes_needed, self.rows_ms = int(n_text.value), int(n_holes.value), ms
         self._ck(rc)
         return text[:n_text.value].tobytes(), site[:n_holes.value], at[:n_holes.value]
+
+    def base_gz(self, names, contig, pos, ref_char, gz_cap=None, hole_cap=None, pin=False):
+        """the same rows as gzip members deflated on the device (pecall_dev_sites_base_gz), arguments as base_text ->
+        (gz bytes, hole_site, hole_gz_at): inflating gz gives base_text's text; the caller's own row of column hole_site[k], as a
+        member of its own, belongs at byte hole_gz_at[k] of gz, a member boundary.  gz_cap defaults to the bound (every column a
+        row of the longest form, each piece of PCG_PIECE bytes stored, a piece more per column).  A failure for want of room leaves
+        what is needed in self.gz_needed / self.holes_needed.  self.text_needed = the inflated length; self.gz_ms = the kernels'
+        durations (length, scan, fill, deflate, pack)"""
+        nm = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+        blob = np.frombuffer(b"".join(nm) + b"\0", np.uint8)
+        name_off = np.concatenate([[0], np.cumsum([len(x) for x in nm])]).astype(np.uint32)
+        contig = np.ascontiguousarray(contig, np.int32)
+        pos = np.ascontiguousarray(pos, np.uint32)
+        ref = np.frombuffer(ref_char.encode() if isinstance(ref_char, str) else bytes(ref_char), np.uint8) if not isinstance(ref_char, np.ndarray) else np.ascontiguousarray(ref_char).view(np.uint8)
+        n = len(contig)
+        if len(pos) != n or ref.size != n:
+            raise ValueError("contig, pos and ref_char have one entry per column")
+        indiv = getattr(self, "_rindiv", 0) or 512          # (samples of the last call)
+        if gz_cap is None:
+            text_cap = n * (14 + max([len(x) for x in nm] + [0]) + 4 * indiv)
+            gz_cap = text_cap + 23 * (text_cap // PCG_PIECE + n + 1)
+        if hole_cap is None:
+            hole_cap = n
+        gz = np.zeros(max(int(gz_cap), 1), np.uint8)
+        site, at = np.zeros(max(int(hole_cap), 1), np.uint32), np.zeros(max(int(hole_cap), 1), np.uint64)
+        n_gz, n_holes, n_text = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        ms = np.zeros(5, np.float32)
+        if pin:
+            self.pin_host(gz)
+        try:
+            rc = self.L.pecall_dev_sites_base_gz(self.h, _p(blob), _p(name_off), len(nm), _p(contig), _p(pos), _p(ref), _p(gz), int(gz_cap),
+                                                 C.byref(n_gz), _p(site), _p(at), int(hole_cap), C.byref(n_holes), C.byref(n_text), _p(ms))
+        finally:
+            if pin:
+                self.unpin_host(gz)
+        self.gz_needed, self.holes_needed, self.text_needed, self.gz_ms = int(n_gz.value), int(n_holes.value), int(n_text.value), ms
+        self._ck(rc)
+        return gz[:n_gz.value].tobytes(), site[:n_holes.value], at[:n_holes.value]
 
     def pin_host(self, a):
         self._ck(self.L.pecall_dev_pin_host(self.h, a.ctypes.data, a.nbytes))

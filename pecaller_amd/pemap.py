@@ -29,6 +29,7 @@ SYMBOLS = [
     "pecall_dev_sites_stage_records", "pecall_dev_sites_gather", "pecall_dev_sites_merge_ms", "pecall_dev_call_records",
     "pecall_dev_sites_stage_records_guided", "pecall_dev_call_records_guided",
     "pecall_dev_sites_base_text",
+    "pecall_dev_sites_base_gz",
     "pemap_dev_stage_fastq", "pemap_dev_submit_fastq", "pemap_dev_seed_launch", "pemap_dev_pipeline_stats",
 ]
 

@@ -20,12 +20,11 @@
 #include <rocprim/rocprim.hpp>
 
 static char g_create_err[512] = "";
-struct PmChunkCtr;
 
 // ---- batches in flight (pemap_dev_submit_batch / pemap_dev_wait_batch).  The staged-read arrays of the object are cut in
-// PM_RING slots of ring_cap rows; a submitted batch owns one slot from its host-to-device copy to the device-to-host copy of
+// PM_RING slots of PmRing::cap rows; a submitted batch owns one slot from its host-to-device copy to the device-to-host copy of
 // its m1 / m2 / mapping_type.  Lengths and results pass through pinned staging buffers of the slot; the read rows are copied
-// straight from the caller's buffers (pinned through pemap_dev_pin_host, or registered on first use).
+// straight from the caller's buffers where the caller pinned them (pemap_dev_pin_host).
 #define PM_RING 3
 struct PmRingSlot
 {
@@ -44,7 +43,7 @@ struct PmRingSlot
 
 // ---- chunks in flight.  The pipeline keeps PM_SETS chunks in flight (the seed stage of chunk k+1 beside the SW / walk of chunk k),
 // so everything a chunk works on exists PM_SETS times: chunk g of a run, counted over the runs queued behind each other, uses set
-// g % PM_SETS.  All sets have the same sizes (the capacities are members of the object) and are allocated and released together.
+// g % PM_SETS.  All sets have the same sizes (the capacities are PmChunkWork's) and are allocated and released together.
 #define PM_SETS 2
 // A third set is this constant plus what the constant does not say: the waits of enqueue_seed on ev_lists_free / ev_walk_done are
 // written for "the chunk PM_SETS back" but were only ever run with two sets, the seed stage would run three chunks ahead of the ALU
@@ -63,7 +62,7 @@ struct PmChunkSet
   uint64_t rest_id = 0;         // run serial and chunk number of the last remainder enqueued on the set (launch_rest)
 };
 
-// The timing events of a chunk (pemap_dev::evs holds PM_NEV per chunk), each recorded behind the kernel(s) it is named for, and the
+// The timing events of a chunk (PmRun::evs holds PM_NEV per chunk), each recorded behind the kernel(s) it is named for, and the
 // times pemap_dev_run_stats reports (in the order of include/pemap_hip.h), each the sum over pm_intervals' rows for its slot.
 enum PmEvent
 {
@@ -72,6 +71,14 @@ enum PmEvent
 };
 enum PmTime { PM_T_SEED, PM_T_SW_SINGLE, PM_T_SW_MULTI, PM_T_SELECT, PM_T_SW_REDO, PM_T_WALK, PM_T_LOOKUP, PM_T_VOTE, PM_NT };
 static_assert (PM_NT == 8, "pemap_dev_run_stats copies last_ms into the caller's times_ms8");
+// the slots of pemap_dev_pipeline_stats (include/pemap_hip.h): runs queued; of them, runs that continued a pending pipeline; absorbs because
+// the chunk table was full / the longest read changed / the pending runs' arrays are too small; ring set-ups; the last run's chunks; its first
+enum PmPipeStat
+{
+  PM_PS_RUNS, PM_PS_CONTINUED, PM_PS_ABSORB_TABLE_FULL, PM_PS_ABSORB_LENGTH, PM_PS_ABSORB_ARRAYS, PM_PS_RING_SETUPS, PM_PS_LAST_CHUNKS,
+  PM_PS_LAST_FIRST_CHUNK, PM_NPS
+};
+static_assert (PM_NPS == 8, "pemap_dev_pipeline_stats copies pstat into the caller's out8");
 static const struct { PmTime slot; PmEvent from, to; bool seed_too; } pm_intervals[] = {
   // the seed stage in two rows: its look-ups (one measurement for two slots), then vote, remainder and emit (the reference layout's run on the ALU stream)
   { PM_T_LOOKUP, PM_EV_LOOKUP_BEGIN, PM_EV_LOOKUP_END, true }, { PM_T_SEED, PM_EV_VOTE_BEGIN, PM_EV_SEED_END },
@@ -79,6 +86,19 @@ static const struct { PmTime slot; PmEvent from, to; bool seed_too; } pm_interva
   { PM_T_SW_MULTI, PM_EV_SW_SINGLE_END, PM_EV_SW_MULTI_END }, { PM_T_SELECT, PM_EV_SW_MULTI_END, PM_EV_SELECT_END },
   { PM_T_SW_REDO, PM_EV_SELECT_END, PM_EV_SW_REDO_END }, { PM_T_WALK, PM_EV_SW_REDO_END, PM_EV_WALK_END },
 };
+
+// per-chunk device counters: the kernels' PmCounters plus what the look-up kernel counts
+struct PmChunkCtr
+{
+  PmCounters c;
+  unsigned long long positions;
+  unsigned n_big;
+  unsigned next_end;            // work counter of the persistent look-up waves
+  unsigned n_big2;              // read-ends the second tier of the fused seed kernel leaves to pm_seed_kernel
+  unsigned next_end2;           // the second tier's work counter
+};
+
+#define PM_MAX_CHUNKS 256
 
 // Host ranges page-locked through pemap_dev_pin_host.  HIP's registrations are process-wide and keyed by the pointer, so the
 // table is too (one object must not undo what another still copies from); a range stays until its last unpin.  The library
@@ -93,7 +113,6 @@ struct PmPinned
 };
 static std::mutex g_pin_mu;
 static std::vector < PmPinned > g_pinned;
-
 
 // Tuning knobs.  The environment is read ONCE, by pemap_dev_create, into the object: nothing below
 // calls getenv again, so two objects of one process may run with different settings and a setting cannot change under a
@@ -187,43 +206,130 @@ struct PmFastq
   PfqCtl *d_ctl = nullptr;      // [2]
   struct Host { PfqCtl ctl[2]; unsigned next[2]; } *h = nullptr;        // pinned
 };
-static void fq_free (PmFastq & F);
 
-struct pemap_dev
+// ---- the object and its groups.  What a pemap_dev owns is split by owner; each group says who makes it and who reads it, and has one
+// free function (pointers released and nulled by the primitives below, capacities 0, events destroyed).  pemap_dev_destroy is those
+// functions.  An ensure function frees what it re-makes through them and sets the capacity behind the last allocation: one that fails
+// leaves null pointers under a capacity of 0.
+template < class ... T > static void pm_free (T * &... p)
 {
-  int device = 0;
-  PmKnobs kn = {};
-  hipStream_t stream = nullptr;
-  char err[512] = "";
-  // index
+  ((hipFree (p), p = nullptr), ...);
+}
+
+template < class ... T > static void pm_host_free (T * &... p)
+{
+  ((p ? (void) hipHostFree (p) : (void) 0, p = nullptr), ...);
+}
+
+static void pm_event_free (hipEvent_t & e)
+{
+  (e ? (void) hipEventDestroy (e) : (void) 0, e = nullptr);
+}
+
+static void fq_free (PmFastq & F)
+{
+  for (PmFastqMate & M : F.mate)
+    {
+      pm_free (M.d_text, M.d_tile_cnt, M.d_line_start, M.d_sums, M.d_tile_in, M.d_rec_off, M.d_rec_next, M.d_rec_len);
+      M = PmFastqMate ();
+    }
+  pm_free (F.d_ctl);
+  pm_host_free (F.h);
+}
+
+// The index.  Made by pemap_dev_index_alloc (the arrays and sizes; their contents by the caller's copies or build_from_genome) and
+// by build_replicas at index_commit (d_rep, d_multi and their figures); read by index_of for every kernel, pemap_dev_buffer, index_share.
+struct PmIndexArrays
+{
   uint32_t *d_pos_index = nullptr, *d_mers = nullptr;
-  uint32_t *d_rep = nullptr, *d_multi = nullptr;        // look-up replicas (pemap_aux.hip.h), built by index_commit
+  uint32_t *d_rep = nullptr, *d_multi = nullptr;        // look-up replicas (pemap_aux.hip.h)
   uint32_t multi_base = 0;
-  int n_rep = 0, rep_want = -1; // rep_want: -1 = when the memory is there (default), 0 = never, 8 = required
+  int n_rep = 0;
   uint64_t multi_units = 0;
   uint8_t *d_genome = nullptr, *d_genome_alloc = nullptr;       // the letters, and the allocation they sit in (padded in front)
   uint32_t *d_contig_starts = nullptr;
   uint64_t n_mers = 0, gsize = 0;
   int n_contigs = 0, idepth = 16;
-  bool index_ready = false;
-  uint32_t *d_counts = nullptr; // the pileup counter planes (PmPile): 6 planes of pile_plane_words words
-  size_t pile_plane_words = 0;
+  bool ready = false;
+};
+
+// keep_rep: the replicas' allocation stays for the next index (build_replicas says why); only pemap_dev_destroy releases it
+static void index_free (PmIndexArrays & x, bool keep_rep)
+{
+  pm_free (x.d_pos_index, x.d_mers, x.d_multi, x.d_genome_alloc, x.d_contig_starts);
+  if (!keep_rep)
+    pm_free (x.d_rep);
+  x.d_genome = nullptr;
+  x.n_mers = x.gsize = x.multi_units = 0;
+  x.n_contigs = x.n_rep = 0;
+  x.ready = false;
+}
+
+// The pileup.  The planes are made by pemap_dev_index_alloc (the genome sizes them), the cursor by pemap_dev_create, the log by
+// ensure_work; the walk and pile kernels write them (pile_of), drain_ins and fold_summary keep the host's side, and the fetch entries,
+// pemap_dev_buffer (4) and pemap_dev_absorb read.
+struct PmPileup
+{
+  uint32_t *d_counts = nullptr; // the counter planes (PmPile): 6 planes of plane_words words
+  size_t plane_words = 0;
   // plane 0 holds differences while the object maps (PmPile): guarded by mu.  run_slice unfolds, pile_fold folds back for every
-  // entry that reads or hands out the counters; d_pile_tiles is the conversions' word per tile of PD_TILE words.
-  bool pile_diff = false;
-  uint32_t *d_pile_tiles = nullptr;
-  // each chunk's big-end remainder is enqueued exactly once: checked in launch_rest (DESIGN.md, the round-3 fault)
-  uint64_t run_serial = 0;
-  bool rest_twice = false;
-  // params
-  int paired = 1, min_dist = 0, max_dist = 500, bisulfite = 0;
-  double min_align = 0.9;       // MIN_ALIGN default, pemapper.c:151
-  // staged reads (capacity cap_reads rows each)
-  uint8_t *d_reads1 = nullptr, *d_reads2 = nullptr;
-  int *d_len1 = nullptr, *d_len2 = nullptr;
-  int cap_reads = 0, n_staged = 0, stride = 0, staged_paired = 0, max_len_staged = 0, min_len_staged = 0;
-  std::vector < int >h_len1, h_len2;
-  // per-chunk work arrays and events, one set per chunk in flight, and the capacities all sets share
+  // entry that reads or hands out the counters; d_tiles is the conversions' word per tile of PD_TILE words.
+  bool diff = false;
+  uint32_t *d_tiles = nullptr;
+  PmInsCursor *d_cur = nullptr;
+  uint8_t *d_ins_log = nullptr;
+  unsigned ins_cap = 0;
+  std::vector < uint8_t > h_ins;        // host copy of all insertion-log bytes so far
+  long summary[13] = {};
+};
+
+// planes_only: what a new index re-makes; the cursor, the log and the host's totals go on
+static void pile_free (PmPileup & p, bool planes_only)
+{
+  pm_free (p.d_counts, p.d_tiles);
+  p.plane_words = 0;
+  p.diff = false;
+  if (planes_only)
+    return;
+  pm_free (p.d_cur, p.d_ins_log);
+  p.ins_cap = 0;
+}
+
+// The staged read set: one resident set of reads (stage_reads, stage_fastq, synth_reads) or the ring's PM_RING slots of rows (ring_setup).
+// Made by ensure_reads and described by reads_staged / ring_setup / ring_take; read by run_slice (batch_of), by collect and
+// ring_queue_run (the outputs) and by fold_summary (h_len).
+struct PmReadSet
+{
+  uint8_t *d_rows[2] = {};      // per mate: cap rows of stride bytes
+  int *d_len[2] = {};
+  std::vector < int >h_len[2];
+  int cap = 0, stride = 0;
+  int n = 0, paired = 0, max_len = 0, min_len = 0;      // what is staged: rows, pairing, the longest and the shortest read
+  uint32_t *d_m1 = nullptr, *d_m2 = nullptr;    // a run's results: cap_out rows
+  int *d_mtype = nullptr;
+  int cap_out = 0;
+};
+
+// (the two parts ensure_reads re-makes on their own: the mates' arrays, the outputs)
+static void reads_free (PmReadSet & r, bool rows, bool outputs)
+{
+  if (rows)
+    {
+      pm_free (r.d_rows[0], r.d_rows[1], r.d_len[0], r.d_len[1]);
+      r.cap = r.n = 0;
+    }
+  if (outputs)
+    {
+      pm_free (r.d_m1, r.d_m2, r.d_mtype);
+      r.cap_out = 0;
+    }
+}
+
+// The chunk work: what the chunks in flight compute in.  pemap_dev_create makes the grids and the sets' events, ensure_work the arrays
+// sized by a chunk's read-ends, its direction slabs and its path words, ensure_pipeline the lists; the launch functions read them.
+// A part is released by its work_free_* and allocated again for every set.
+struct PmChunkWork
+{
   PmChunkSet set[PM_SETS];
   int cap_ends = 0;             // read-ends the hit, winner and task arrays hold
   size_t dirbuf_dwords = 0;
@@ -231,66 +337,164 @@ struct pemap_dev
   int path_words = 0, path_cap_ends = 0;
   int lists_cap = 0;
   bool lists_arrays = false;    // the (key, segment) lists exist (not needed, and not allocated, while the fused seed kernel serves)
-  // work arrays of the object: used by one stream at a time
-  uint32_t *d_redo = nullptr;
-  uint32_t *d_m1 = nullptr, *d_m2 = nullptr;
-  int *d_mtype = nullptr;
-  int cap_out = 0;
-  PmInsCursor *d_cur = nullptr;
-  uint32_t *d_seed_scratch = nullptr;
-  uint8_t *d_ins_log = nullptr;
-  unsigned ins_cap = 0;
-  int sw_grid = 0;
-  // run bookkeeping
-  int run_first = 0, run_n = 0;
-  bool run_pending = false;     // kernels of the last run still in flight / not yet accounted
-  int run_chunks = 0, run_L = 0;
-  uint64_t run_ends = 0;
-  // which way run_slice and ring_setup went, since the object was made (pemap_dev_pipeline_stats: host integers, guarded by mu)
-  uint64_t pstat[8] = { };
+  uint32_t *d_redo = nullptr;   // cap_ends; used by one stream at a time, like the scratch
+  uint32_t *d_seed_scratch = nullptr;   // big_grid spill areas of pm_seed_kernel
+  int sw_grid = 0, big_grid = 0;
+};
+
+static void work_free_paths (PmChunkWork & w)
+{
+  for (PmChunkSet & s : w.set)
+    pm_free (s.path, s.nsteps);
+  w.path_words = w.path_cap_ends = 0;
+}
+
+static void work_free_dirs (PmChunkWork & w)
+{
+  for (PmChunkSet & s : w.set)
+    pm_free (s.dirbuf);
+  w.dirbuf_dwords = w.dir_slabs = 0;
+}
+
+static void work_free_lists (PmChunkWork & w)
+{
+  for (PmChunkSet & s : w.set)
+    pm_free (s.lists.hdr, s.lists.key, s.lists.seg, s.lists.big_list);
+  w.lists_cap = 0;
+  w.lists_arrays = false;
+}
+
+static void work_free_ends (PmChunkWork & w)
+{
+  for (PmChunkSet & s : w.set)
+    {
+      PmHits & h = s.hits;
+      pm_free (h.n_hits, h.spot, h.gpos, h.nn, h.orient, h.score, h.sti, h.stk, h.slot);
+      pm_free (s.wins, s.walks, s.tasks_s, s.tasks_m);
+    }
+  pm_free (w.d_redo);
+  w.cap_ends = 0;
+  work_free_paths (w);
+}
+
+static void work_free (PmChunkWork & w)
+{
+  work_free_ends (w);
+  work_free_dirs (w);
+  work_free_lists (w);
+  pm_free (w.d_seed_scratch);
+  for (PmChunkSet & s : w.set)
+    for (hipEvent_t * e : { &s.ev_lists_ready, &s.ev_lists_free, &s.ev_walk_done })
+      pm_event_free (*e);
+}
+
+// A run's bookkeeping.  run_slice writes what is queued, absorb_run the totals of what ran; the seed stream, the chunks' counters and
+// their timing events are made by ensure_pipeline.  Read by the next run_slice (does it continue the pipeline?), collect and the stats entries.
+struct PmRun
+{
+  int first = 0, n = 0, chunks = 0, L = 0;
+  uint64_t ends = 0;
+  bool pending = false;         // kernels of the last run still in flight / not yet accounted
+  // each chunk's big-end remainder is enqueued exactly once: checked in launch_rest (DESIGN.md, the round-3 fault)
+  uint64_t serial = 0;
+  bool rest_twice = false;
   // two-stream pipeline: the look-up kernel of chunk k+1 (memory stream) runs beside vote/SW/walk of chunk k
   hipStream_t stream2 = nullptr;
-  int n_cus = 0;
+  PmChunkCtr *d_chunk_ctr = nullptr;    // PM_MAX_CHUNKS
+  std::vector < hipEvent_t > evs;       // PM_NEV per chunk
+  uint64_t last_big = 0, last_big2 = 0; // read-ends the fused seed kernel's first tier passed over; of them, left to pm_seed_kernel
+  PmCounters last_ctr = {};     // summed over the chunks of the last run
+  PmInsCursor last_cur = {};
+  float last_ms[PM_NT] = {};
   // the fused seed kernel's first tier: workgroups of the form for S segments that the runtime keeps resident on a CU with the
   // form's LDS (0 = not asked yet), and what the last launch used: the knob, the runtime's answer, workgroups per CU, LDS bytes
   int seed_resident[32] = { };
   int seed_launch[4] = { };
-  PmChunkCtr *d_chunk_ctr = nullptr;
-  std::vector < hipEvent_t > evs;
-  int big_grid = 0;
-  uint64_t last_big = 0, last_big2 = 0;  // read-ends the fused seed kernel's first tier passed over; of them, left to pm_seed_kernel
-  PmCounters last_ctr = {};     // summed over the chunks of the last run
-  PmInsCursor last_cur = {};
-  // batches in flight
+  // which way run_slice and ring_setup went, since the object was made (pemap_dev_pipeline_stats: host integers, guarded by mu)
+  uint64_t pstat[PM_NPS] = { };
+};
+
+// (the stream goes with the object's other streams, in pemap_dev_destroy)
+static void run_free (PmRun & r)
+{
+  pm_free (r.d_chunk_ctr);
+  for (hipEvent_t & e : r.evs)
+    pm_event_free (e);
+  r.evs.clear ();
+}
+
+// The ring of batches in flight.  ring_setup makes the slots' pinned blocks (sized like the read set's rows, which the slots cut up) and
+// ring_leave gives the rows back to a resident set; ring_take hands a submit its slot, ring_queue_run fills it in, ring_finish delivers.
+struct PmRing
+{
+  PmRingSlot slot[PM_RING];
+  int cap = 0;                  // rows per slot, 0 = the ring is not set up (the staged arrays hold a resident read set)
+  unsigned long long seq = 0;
+  hipStream_t stream_h2d = nullptr;
+};
+
+static bool ring_active (const PmRing & g)     // (mu held)
+{
+  for (const PmRingSlot & r : g.slot)
+    if (r.active)
+      return true;
+  return false;
+}
+
+// blocks_only: what ring_setup re-makes; the slots' events serve the next geometry too
+static void ring_free (PmRing & g, bool blocks_only)
+{
+  for (PmRingSlot & r : g.slot)
+    {
+      pm_host_free (r.h_len, r.h_res, r.h_rows);
+      r.h_rows_bytes = 0;
+      if (blocks_only)
+        continue;
+      pm_event_free (r.ev_done);
+      for (hipEvent_t & e : r.ev_copy)
+        pm_event_free (e);
+      r.ev_copy.clear ();
+    }
+  g.cap = 0;
+}
+
+struct pemap_dev
+{
+  int device = 0, n_cus = 0;
+  PmKnobs kn = {};
+  hipStream_t stream = nullptr; // the ALU stream (pemap_dev_create); the seed stream is run.stream2, the copy stream rg.stream_h2d
+  char err[512] = "";
+  int rep_want = -1;            // settings.  Replicas: -1 = when the memory is there (default), 0 = never, 8 = required
+  int paired = 1, min_dist = 0, max_dist = 500, bisulfite = 0;
+  double min_align = 0.9;       // MIN_ALIGN default, pemapper.c:151
+  PmIndexArrays ix;
+  PmPileup pile;
+  PmReadSet rd;
+  PmChunkWork wk;
+  PmRun run;
   std::mutex mu;                // guards the enqueue state: submit / wait may be called from several host threads
   // Submitters are serialised for the whole of a submit (taken BEFORE mu).  ring_finish drops mu while the host blocks on the old
-  // batch's event; with mu alone a second submitter saw the same ring_seq there, chose the same slot, and whichever came second went
+  // batch's event; with mu alone a second submitter saw the same rg.seq there, chose the same slot, and whichever came second went
   // on with a stale slot and `first` -- overwriting an active slot's staging and handing out a ticket of another slot (round-2 review).
   // Waiters take mu only, so a wait is never held up by a submit that blocks on a full ring.
   std::mutex submit_mu;
-  PmRingSlot ring[PM_RING];
-  int ring_cap = 0;             // rows per slot, 0 = the ring is not set up (the staged arrays hold a resident read set)
-  unsigned long long ring_seq = 0;
-  hipStream_t stream_h2d = nullptr;
-  float last_ms[PM_NT] = {};
-  std::vector < uint8_t > h_ins;        // host copy of all insertion-log bytes so far
-  long summary[13] = {};
+  PmRing rg;
   PmFastq fq;
 };
 
 static inline PmPile pile_of (const pemap_dev * d)
 {
   PmPile p;
-  p.w = d->d_counts;
-  p.plane_words = d->pile_plane_words;
-  p.genome = d->d_genome;
+  p.w = d->pile.d_counts;
+  p.plane_words = d->pile.plane_words;
+  p.genome = d->ix.d_genome;
   return p;
 }
 
-static inline PmIndex index_of (const pemap_dev * d)   // (here and below: in the order of the struct's fields)
+static inline PmIndex index_of (const pemap_dev * d)
 {
-  return PmIndex { d->d_pos_index, d->d_mers, d->d_genome, d->d_contig_starts, d->n_mers, d->gsize, d->n_contigs, d->idepth,
-                   d->d_rep, d->d_multi, d->multi_base, d->n_rep };
+  return PmIndex { d->ix.d_pos_index, d->ix.d_mers, d->ix.d_genome, d->ix.d_contig_starts, d->ix.n_mers, d->ix.gsize, d->ix.n_contigs, d->ix.idepth,
+                   d->ix.d_rep, d->ix.d_multi, d->ix.multi_base, d->ix.n_rep };
 }
 
 static inline PmParams params_of (const pemap_dev * d)
@@ -318,12 +522,6 @@ template < class T > static int dev_alloc (pemap_dev * d, T ** p, size_t n)
   return 0;
 }
 
-template < class T > static void dev_free (T * &p)
-{
-  hipFree (p);
-  p = nullptr;
-}
-
 // a device temporary of one function: freed when it goes out of scope, on the early returns of TRY / HIPCHK too
 template < class T > struct DevTmp
 {
@@ -342,6 +540,28 @@ extern "C" const char *pemap_dev_last_error (const pemap_dev * dev)
   return dev ? dev->err : g_create_err;
 }
 
+extern "C" void pemap_dev_destroy (pemap_dev * d)
+{
+  if (!d)
+    return;
+  hipSetDevice (d->device);
+  for (hipStream_t st : { d->stream, d->run.stream2 })
+    if (st)
+      hipStreamSynchronize (st);
+  index_free (d->ix, false);
+  pile_free (d->pile, false);
+  reads_free (d->rd, true, true);
+  work_free (d->wk);
+  run_free (d->run);
+  ring_free (d->rg, false);
+  fq_free (d->fq);
+  for (hipStream_t st : { d->rg.stream_h2d, d->run.stream2, d->stream })
+    if (st)
+      hipStreamDestroy (st);
+  delete d;
+}
+
+// (every failure ends in pemap_dev_destroy, through the pointer's deleter: the stream, the events and the cursor made so far go with it)
 extern "C" int pemap_dev_create (pemap_dev ** out, int device_id)
 {
   *out = nullptr;
@@ -350,7 +570,7 @@ extern "C" int pemap_dev_create (pemap_dev ** out, int device_id)
     return fail (nullptr, "no HIP device visible: this library has no CPU path");
   if (device_id < 0 || device_id >= n)
     return fail (nullptr, "device %d out of range (0..%d)", device_id, n - 1);
-  std::unique_ptr < pemap_dev > d (new pemap_dev ());
+  std::unique_ptr < pemap_dev, void (*) (pemap_dev *) > d (new pemap_dev (), pemap_dev_destroy);
   d->device = device_id;
   if (hipSetDevice (device_id) != hipSuccess)
     return fail (nullptr, "hipSetDevice(%d) failed", device_id);
@@ -367,157 +587,24 @@ extern "C" int pemap_dev_create (pemap_dev ** out, int device_id)
   // big_grid blocks and passed to the kernel as its capacity.  (Round 1: the area was sized by another grid, an A/B run
   // raised big_grid above it through an environment knob, and the blocks beyond it wrote past the allocation: the memory
   // access fault of DESIGN.md section 8.)
-  d->sw_grid = cus * d->kn.sw_waves_per_cu;
-  d->big_grid = cus * d->kn.big_blocks_per_cu;
+  d->wk.sw_grid = cus * d->kn.sw_waves_per_cu;
+  d->wk.big_grid = cus * d->kn.big_blocks_per_cu;
   d->n_cus = cus;
   if (hipStreamCreateWithFlags (&d->stream, hipStreamNonBlocking) != hipSuccess)
     return fail (nullptr, "hipStreamCreate failed");
-  for (PmChunkSet & s : d->set)
+  for (PmChunkSet & s : d->wk.set)
     for (hipEvent_t * e : { &s.ev_lists_ready, &s.ev_lists_free, &s.ev_walk_done })
       if (hipEventCreateWithFlags (e, hipEventDisableTiming) != hipSuccess)
         return fail (nullptr, "hipEventCreate failed");
-  if (hipMalloc ((void **) &d->d_cur, sizeof (PmInsCursor)) != hipSuccess)
+  if (hipMalloc ((void **) &d->pile.d_cur, sizeof (PmInsCursor)) != hipSuccess)
     return fail (nullptr, "hipMalloc failed");
-  hipMemset (d->d_cur, 0, sizeof (PmInsCursor));
+  hipMemset (d->pile.d_cur, 0, sizeof (PmInsCursor));
   *out = d.release ();
   return 0;
 }
 
-static void free_index (pemap_dev * d)
-{
-  dev_free (d->d_pos_index);
-  dev_free (d->d_mers);
-  dev_free (d->d_multi);        // d_rep is kept for the next index (pemap_dev_destroy frees it)
-  d->n_rep = 0;
-  dev_free (d->d_genome_alloc);
-  d->d_genome = nullptr;
-  dev_free (d->d_contig_starts);
-  dev_free (d->d_counts);
-  dev_free (d->d_pile_tiles);
-  d->pile_diff = false;
-  d->index_ready = false;
-}
-
-// ---- the chunk sets' arrays, in four groups by what sizes them: the read-ends of a chunk (free_work), the direction slabs, the path
-// words, the lists.  A group is released here and allocated in ensure_work / ensure_pipeline, always for every set.
-static void free_hits (PmHits & h)
-{
-  dev_free (h.n_hits);
-  dev_free (h.spot);
-  dev_free (h.gpos);
-  dev_free (h.nn);
-  dev_free (h.orient);
-  dev_free (h.score);
-  dev_free (h.sti);
-  dev_free (h.stk);
-  dev_free (h.slot);
-}
-
-static void free_paths (pemap_dev * d)
-{
-  for (PmChunkSet & s : d->set)
-    {
-      dev_free (s.path);
-      dev_free (s.nsteps);
-    }
-  d->path_words = d->path_cap_ends = 0;
-}
-
-static void free_dirs (pemap_dev * d)
-{
-  for (PmChunkSet & s : d->set)
-    dev_free (s.dirbuf);
-  d->dirbuf_dwords = 0;
-}
-
-static void free_lists (pemap_dev * d)
-{
-  for (PmChunkSet & s : d->set)
-    {
-      dev_free (s.lists.hdr);
-      dev_free (s.lists.key);
-      dev_free (s.lists.seg);
-      dev_free (s.lists.big_list);
-    }
-  d->lists_cap = 0;
-  d->lists_arrays = false;
-}
-
-static void free_work (pemap_dev * d)
-{
-  for (PmChunkSet & s : d->set)
-    {
-      free_hits (s.hits);
-      dev_free (s.wins);
-      dev_free (s.walks);
-      dev_free (s.tasks_s);
-      dev_free (s.tasks_m);
-    }
-  dev_free (d->d_redo);
-  d->cap_ends = 0;
-  free_paths (d);
-}
-
-extern "C" void pemap_dev_destroy (pemap_dev * d)
-{
-  if (!d)
-    return;
-  hipSetDevice (d->device);
-  hipStreamSynchronize (d->stream);
-  if (d->stream2)
-    hipStreamSynchronize (d->stream2);
-  free_index (d);
-  hipFree (d->d_rep);
-  free_work (d);
-  free_dirs (d);
-  free_lists (d);
-  for (PmChunkSet & s : d->set)
-    for (hipEvent_t e : { s.ev_lists_ready, s.ev_lists_free, s.ev_walk_done })
-      if (e)
-        hipEventDestroy (e);
-  hipFree (d->d_reads1);
-  hipFree (d->d_reads2);
-  hipFree (d->d_len1);
-  hipFree (d->d_len2);
-  hipFree (d->d_m1);
-  hipFree (d->d_m2);
-  hipFree (d->d_mtype);
-  hipFree (d->d_cur);
-  hipFree (d->d_seed_scratch);
-  hipFree (d->d_ins_log);
-  fq_free (d->fq);
-  for (int i = 0; i < PM_RING; i++)
-    {
-      if (d->ring[i].h_len)
-        hipHostFree (d->ring[i].h_len);
-      if (d->ring[i].h_res)
-        hipHostFree (d->ring[i].h_res);
-      if (d->ring[i].h_rows)
-        hipHostFree (d->ring[i].h_rows);
-      if (d->ring[i].ev_done)
-        hipEventDestroy (d->ring[i].ev_done);
-      for (size_t k = 0; k < d->ring[i].ev_copy.size (); k++)
-        hipEventDestroy (d->ring[i].ev_copy[k]);
-    }
-  if (d->stream_h2d)
-    hipStreamDestroy (d->stream_h2d);
-  for (size_t i = 0; i < d->evs.size (); i++)
-    hipEventDestroy (d->evs[i]);
-  hipFree (d->d_chunk_ctr);
-  if (d->stream2)
-    hipStreamDestroy (d->stream2);
-  hipStreamDestroy (d->stream);
-  delete d;
-}
-
 // ------------------------------------------------------------------------------------------------------------
 static const uint64_t POS_INDEX_N = (1ull << 32) + 1ull;
-static int drain_ins (pemap_dev * d);
-static int ring_leave (pemap_dev * d);
-static bool ring_busy (pemap_dev * d);
-static int ring_finish_all (pemap_dev * d, std::unique_lock < std::mutex > &lk);
-static int absorb_run (pemap_dev * d);
-static void fold_summary (pemap_dev * d, int first, int n, const uint32_t * m1, const uint32_t * m2, const int *mapping_type);
 
 // Zeros in device memory, there when this returns.  hipMemset of device memory returns before the fill has run, and on the null
 // stream it is not ordered against the object's non-blocking streams: the 26 GB pileup of a genome of 2.1 G letters was still being
@@ -538,43 +625,45 @@ extern "C" int pemap_dev_index_alloc (pemap_dev * d, uint64_t n_mers, uint64_t g
                  (unsigned long long) genome_size, n_contigs);
   if (idepth != 16)
     return fail (d, "index_alloc: idepth %d: the .idx table is addressed by 16-mers (index_genome_whole.c:149)", idepth);
-  free_index (d);
-  d->n_mers = n_mers;
-  d->gsize = genome_size;
-  d->n_contigs = n_contigs;
-  d->idepth = idepth;
-  TRY (dev_alloc (d, &d->d_pos_index, POS_INDEX_N));
-  TRY (dev_alloc (d, &d->d_mers, n_mers + 128));
+  index_free (d->ix, true);
+  pile_free (d->pile, true);
+  d->ix.n_mers = n_mers;
+  d->ix.gsize = genome_size;
+  d->ix.n_contigs = n_contigs;
+  d->ix.idepth = idepth;
+  TRY (dev_alloc (d, &d->ix.d_pos_index, POS_INDEX_N));
+  TRY (dev_alloc (d, &d->ix.d_mers, n_mers + 128));
   // (256 bytes in front, 512 behind: pm_band_kernel's window loads start a few bytes before a window and the kernels' 8-byte loads
   // end a few bytes behind one; d_genome points at the first letter)
-  TRY (dev_alloc (d, &d->d_genome_alloc, genome_size + 768));
-  HIPCHK (d, hipMemset (d->d_genome_alloc, 0, 256));
-  d->d_genome = d->d_genome_alloc + 256;
-  TRY (dev_alloc (d, &d->d_contig_starts, (size_t) n_contigs + 2));
+  TRY (dev_alloc (d, &d->ix.d_genome_alloc, genome_size + 768));
+  HIPCHK (d, hipMemset (d->ix.d_genome_alloc, 0, 256));
+  d->ix.d_genome = d->ix.d_genome_alloc + 256;
+  TRY (dev_alloc (d, &d->ix.d_contig_starts, (size_t) n_contigs + 2));
   // (a plane is a whole number of 256-byte blocks: planes start line-aligned)
-  d->pile_plane_words = (((size_t) genome_size + 2) / 2 + 63) & ~(size_t) 63;
-  TRY (dev_alloc (d, &d->d_counts, 6 * d->pile_plane_words));
-  TRY (dev_alloc (d, &d->d_pile_tiles, (d->pile_plane_words + PD_TILE - 1) / PD_TILE));
-  HIPCHK (d, hipMemset (d->d_genome + genome_size, 0, 512));
-  TRY (zero_on_stream (d, d->d_counts, 6 * d->pile_plane_words * sizeof (uint32_t)));
+  const size_t plane_words = (((size_t) genome_size + 2) / 2 + 63) & ~(size_t) 63;
+  TRY (dev_alloc (d, &d->pile.d_counts, 6 * plane_words));
+  TRY (dev_alloc (d, &d->pile.d_tiles, (plane_words + PD_TILE - 1) / PD_TILE));
+  d->pile.plane_words = plane_words;
+  HIPCHK (d, hipMemset (d->ix.d_genome + genome_size, 0, 512));
+  TRY (zero_on_stream (d, d->pile.d_counts, 6 * d->pile.plane_words * sizeof (uint32_t)));
   return 0;
 }
 
 // The 8 look-up replicas and the records of the multi-position buckets (pemap_aux.hip.h), from pos_index / mers.
 static int build_replicas (pemap_dev * d)
 {
-  dev_free (d->d_multi);
-  d->n_rep = 0;
+  pm_free (d->ix.d_multi);
+  d->ix.n_rep = 0;
   int want = d->rep_want;
   if (want < 0 && d->kn.replicas >= 0)
     want = d->kn.replicas ? 8 : 0;
   if (want == 0)
     {
-      dev_free (d->d_rep);
+      pm_free (d->ix.d_rep);
       return 0;
     }
   const size_t rep_bytes = 8ull * (1ull << 32) * sizeof (uint32_t);
-  if (!d->d_rep)
+  if (!d->ix.d_rep)
     {
       // The replicas' 128 GiB are allocated once per object and kept across indexes.  What must stay free beside them for
       // the work arrays of a run (direction slabs, hit records, lists) and the records is probed by allocating it.  The
@@ -587,12 +676,12 @@ static int build_replicas (pemap_dev * d)
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo (&fr, &tot) == hipSuccess && fr >= rep_bytes + reserve)
           {
-            if (hipMalloc ((void **) &d->d_rep, rep_bytes) == hipSuccess)
+            if (hipMalloc ((void **) &d->ix.d_rep, rep_bytes) == hipSuccess)
               ok = true;
             else
               {
                 (void) hipGetLastError ();
-                d->d_rep = nullptr;
+                d->ix.d_rep = nullptr;
               }
           }
       }
@@ -604,21 +693,18 @@ static int build_replicas (pemap_dev * d)
               (void) hipDeviceSynchronize ();
               usleep (300000);
             }
-          if (hipMalloc ((void **) &d->d_rep, rep_bytes) == hipSuccess)
+          if (hipMalloc ((void **) &d->ix.d_rep, rep_bytes) == hipSuccess)
             {
               if (hipMalloc (&probe, reserve) == hipSuccess)
                 ok = true;
               else
-                {
-                  hipFree (d->d_rep);
-                  d->d_rep = nullptr;
-                }
+                pm_free (d->ix.d_rep);
               hipFree (probe);
             }
           if (!ok)
             {
               (void) hipGetLastError ();
-              d->d_rep = nullptr;
+              d->ix.d_rep = nullptr;
             }
         }
       if (!ok)
@@ -632,10 +718,10 @@ static int build_replicas (pemap_dev * d)
           return 0;
         }
     }
-  uint32_t *units = d->d_rep + (1ull << 32);    // replica 1's place holds the record offsets until replica 0 is encoded
+  uint32_t *units = d->ix.d_rep + (1ull << 32);    // replica 1's place holds the record offsets until replica 0 is encoded
   const uint64_t n = 1ull << 32;
   const unsigned grid = (unsigned) d->n_cus * 64u;
-  hipLaunchKernelGGL (ix_rep_units_kernel, dim3 (grid), dim3 (256), 0, d->stream, d->d_pos_index, units);
+  hipLaunchKernelGGL (ix_rep_units_kernel, dim3 (grid), dim3 (256), 0, d->stream, d->ix.d_pos_index, units);
   const uint64_t sc_tiles = (n + SC_TILE - 1) / SC_TILE;
   DevTmp < unsigned long long > d_total;
   DevTmp < uint32_t > d_tsum;
@@ -647,32 +733,32 @@ static int build_replicas (pemap_dev * d)
   HIPCHK (d, hipMemcpyAsync (&total, d_total, sizeof (total), hipMemcpyDeviceToHost, d->stream));
   HIPCHK (d, hipStreamSynchronize (d->stream));
   // entries below multi_base are positions (compressed coordinates < genome size); codes up to 0xFFFFFFFD address the records
-  d->multi_base = (uint32_t) d->gsize;
-  const bool fits = total < (unsigned long long) (0xFFFFFFFEu - d->multi_base);
+  d->ix.multi_base = (uint32_t) d->ix.gsize;
+  const bool fits = total < (unsigned long long) (0xFFFFFFFEu - d->ix.multi_base);
   if (fits)
     {
       hipLaunchKernelGGL (ix_sumscan_apply_kernel, dim3 ((unsigned) sc_tiles), dim3 (SC_BLOCK), 0, d->stream, units, n, d_tsum);
-      TRY (dev_alloc (d, &d->d_multi, (size_t) total * 4 + 64));
-      hipLaunchKernelGGL (ix_rep_encode_kernel, dim3 (grid), dim3 (256), 0, d->stream, d->d_pos_index, d->d_mers, units, d->multi_base, d->d_rep,
-                          d->d_multi);
+      TRY (dev_alloc (d, &d->ix.d_multi, (size_t) total * 4 + 64));
+      hipLaunchKernelGGL (ix_rep_encode_kernel, dim3 (grid), dim3 (256), 0, d->stream, d->ix.d_pos_index, d->ix.d_mers, units, d->ix.multi_base, d->ix.d_rep,
+                          d->ix.d_multi);
       for (int p = 1; p < 8; p++)
-        hipLaunchKernelGGL (ix_rep_permute_kernel, dim3 ((unsigned) d->n_cus * 32u), dim3 (256), 0, d->stream, d->d_rep,
-                            d->d_rep + ((size_t) p << 32), p);
+        hipLaunchKernelGGL (ix_rep_permute_kernel, dim3 ((unsigned) d->n_cus * 32u), dim3 (256), 0, d->stream, d->ix.d_rep,
+                            d->ix.d_rep + ((size_t) p << 32), p);
     }
   HIPCHK (d, hipStreamSynchronize (d->stream));
   HIPCHK (d, hipGetLastError ());
   if (!fits)
     {
       if (want == 8)
-        return fail (d, "look-up replicas: %llu record units do not fit the codes above genome size %llu", total, (unsigned long long) d->gsize);
+        return fail (d, "look-up replicas: %llu record units do not fit the codes above genome size %llu", total, (unsigned long long) d->ix.gsize);
       // as when the memory is not there: the reference's layout serves the look-ups
       fprintf (stderr, "libpemap_hip: device %d: the look-up replicas need %llu record units and a genome of %llu letters leaves codes for %llu; "
                "the look-ups read the reference's table instead (slower, same results; PEMAP_REPLICAS=0 silences this)\n", d->device, total,
-               (unsigned long long) d->gsize, (unsigned long long) (0xFFFFFFFEu - d->multi_base - 1u));
+               (unsigned long long) d->ix.gsize, (unsigned long long) (0xFFFFFFFEu - d->ix.multi_base - 1u));
       return 0;
     }
-  d->multi_units = total;
-  d->n_rep = 8;
+  d->ix.multi_units = total;
+  d->ix.n_rep = 8;
   return 0;
 }
 
@@ -681,7 +767,7 @@ extern "C" int pemap_dev_set_lookup_replicas (pemap_dev * d, int n)
   if (n != -1 && n != 0 && n != 8)
     return fail (d, "set_lookup_replicas: %d (-1 = when the memory is there, 0 = never, 8 = required)", n);
   d->rep_want = n;
-  if (d->index_ready)
+  if (d->ix.ready)
     {
       HIPCHK (d, hipSetDevice (d->device));
       HIPCHK (d, hipDeviceSynchronize ());
@@ -692,34 +778,20 @@ extern "C" int pemap_dev_set_lookup_replicas (pemap_dev * d, int n)
 
 extern "C" int pemap_dev_lookup_replicas (pemap_dev * d, int *n_replicas, uint64_t * record_bytes)
 {
-  *n_replicas = d->n_rep;
+  *n_replicas = d->ix.n_rep;
   if (record_bytes)
-    *record_bytes = d->n_rep ? d->multi_units * 16ull : 0ull;
+    *record_bytes = d->ix.n_rep ? d->ix.multi_units * 16ull : 0ull;
   return 0;
-}
-
-extern "C" int pemap_dev_seed_launch (pemap_dev * d, int *asked, int *resident, int *launched, int *lds_bytes)
-{
-  *asked = d->seed_launch[0];
-  *resident = d->seed_launch[1];
-  *launched = d->seed_launch[2];
-  *lds_bytes = d->seed_launch[3];
-  return 0;
-}
-
-extern "C" int pemap_dev_sw_grid (pemap_dev * d)
-{
-  return d->sw_grid;
 }
 
 extern "C" int pemap_dev_index_commit (pemap_dev * d)
 {
-  if (!d->d_pos_index)
+  if (!d->ix.d_pos_index)
     return fail (d, "index_commit: no index arrays allocated");
   HIPCHK (d, hipSetDevice (d->device));
   HIPCHK (d, hipDeviceSynchronize ());
   TRY (build_replicas (d));
-  d->index_ready = true;
+  d->ix.ready = true;
   return 0;
 }
 
@@ -728,16 +800,18 @@ extern "C" int pemap_dev_load_index (pemap_dev * d, const uint32_t * pos_index, 
                                      int idepth)
 {
   TRY (pemap_dev_index_alloc (d, n_mers, genome_size, n_contigs, idepth));
-  HIPCHK (d, hipMemcpy (d->d_pos_index, pos_index, POS_INDEX_N * sizeof (uint32_t), hipMemcpyHostToDevice));
-  HIPCHK (d, hipMemcpy (d->d_mers, mers, n_mers * sizeof (uint32_t), hipMemcpyHostToDevice));
-  HIPCHK (d, hipMemcpy (d->d_genome, genome, genome_size, hipMemcpyHostToDevice));
-  HIPCHK (d, hipMemcpy (d->d_contig_starts, contig_starts, ((size_t) n_contigs + 1) * sizeof (uint32_t), hipMemcpyHostToDevice));
+  HIPCHK (d, hipMemcpy (d->ix.d_pos_index, pos_index, POS_INDEX_N * sizeof (uint32_t), hipMemcpyHostToDevice));
+  HIPCHK (d, hipMemcpy (d->ix.d_mers, mers, n_mers * sizeof (uint32_t), hipMemcpyHostToDevice));
+  HIPCHK (d, hipMemcpy (d->ix.d_genome, genome, genome_size, hipMemcpyHostToDevice));
+  HIPCHK (d, hipMemcpy (d->ix.d_contig_starts, contig_starts, ((size_t) n_contigs + 1) * sizeof (uint32_t), hipMemcpyHostToDevice));
   return pemap_dev_index_commit (d);
 }
 
-static int build_from_device_genome (pemap_dev * d, const uint32_t * contig_len, int n_contigs, int bisulfite)
+// the index of a genome that lies on the host or on the device (`from`)
+static int build_from_genome (pemap_dev * d, const void *genome, hipMemcpyKind from, uint64_t gsize, const uint32_t * contig_len, int n_contigs, int bisulfite)
 {
-  const uint64_t gsize = d->gsize;
+  TRY (pemap_dev_index_alloc (d, 0, gsize, n_contigs, 16));
+  HIPCHK (d, hipMemcpy (d->ix.d_genome, genome, gsize, from));
   std::vector < uint64_t > real_starts (n_contigs + 1);
   std::vector < uint32_t > cstarts (n_contigs + 1);
   real_starts[0] = 0;
@@ -752,7 +826,7 @@ static int build_from_device_genome (pemap_dev * d, const uint32_t * contig_len,
   if (real_starts[n_contigs] != gsize)
     return fail (d, "build_index: contig lengths sum to %llu, genome has %llu letters", (unsigned long long) real_starts[n_contigs],
                  (unsigned long long) gsize);
-  HIPCHK (d, hipMemcpy (d->d_contig_starts, cstarts.data (), (n_contigs + 1) * sizeof (uint32_t), hipMemcpyHostToDevice));
+  HIPCHK (d, hipMemcpy (d->ix.d_contig_starts, cstarts.data (), (n_contigs + 1) * sizeof (uint32_t), hipMemcpyHostToDevice));
   {
     // the temporaries (some 3 x n_mers words) are released, last one first, before the replicas are built
     DevTmp < uint64_t > d_real, d_total, d_to;
@@ -764,7 +838,7 @@ static int build_from_device_genome (pemap_dev * d, const uint32_t * contig_len,
     TRY (dev_alloc (d, &d_tc.p, n_tiles));
     TRY (dev_alloc (d, &d_to.p, n_tiles));
     TRY (dev_alloc (d, &d_total.p, 1));
-    hipLaunchKernelGGL (ix_count_kernel, dim3 ((unsigned) n_tiles), dim3 (IX_BLOCK), 0, d->stream, d->d_genome, d_real, n_contigs, gsize,
+    hipLaunchKernelGGL (ix_count_kernel, dim3 ((unsigned) n_tiles), dim3 (IX_BLOCK), 0, d->stream, d->ix.d_genome, d_real, n_contigs, gsize,
                         bisulfite, d_tc);
     hipLaunchKernelGGL (ix_scan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d_tc, d_to, n_tiles, d_total);
     uint64_t n_mers = 0;
@@ -775,25 +849,25 @@ static int build_from_device_genome (pemap_dev * d, const uint32_t * contig_len,
     TRY (dev_alloc (d, &d_keys.p, n_mers));
     TRY (dev_alloc (d, &d_vals.p, n_mers));
     TRY (dev_alloc (d, &d_keys2.p, n_mers));
-    dev_free (d->d_mers);
-    TRY (dev_alloc (d, &d->d_mers, n_mers + 128));
-    d->n_mers = n_mers;
-    hipLaunchKernelGGL (ix_emit_kernel, dim3 ((unsigned) n_tiles), dim3 (IX_BLOCK), 0, d->stream, d->d_genome, d_real, n_contigs, gsize,
+    pm_free (d->ix.d_mers);
+    TRY (dev_alloc (d, &d->ix.d_mers, n_mers + 128));
+    d->ix.n_mers = n_mers;
+    hipLaunchKernelGGL (ix_emit_kernel, dim3 ((unsigned) n_tiles), dim3 (IX_BLOCK), 0, d->stream, d->ix.d_genome, d_real, n_contigs, gsize,
                         bisulfite, d_to, d_keys, d_vals);
     // stable LSD radix sort by k-mer: equal k-mers keep genome order, which is the .mdx order
     size_t tmp_bytes = 0;
-    HIPCHK (d, rocprim::radix_sort_pairs (nullptr, tmp_bytes, d_keys.p, d_keys2.p, d_vals.p, d->d_mers, (size_t) n_mers, 0, 32, d->stream));
+    HIPCHK (d, rocprim::radix_sort_pairs (nullptr, tmp_bytes, d_keys.p, d_keys2.p, d_vals.p, d->ix.d_mers, (size_t) n_mers, 0, 32, d->stream));
     HIPCHK (d, hipMalloc (&d_tmp.p, tmp_bytes ? tmp_bytes : 1));
-    HIPCHK (d, rocprim::radix_sort_pairs (d_tmp.p, tmp_bytes, d_keys.p, d_keys2.p, d_vals.p, d->d_mers, (size_t) n_mers, 0, 32, d->stream));
+    HIPCHK (d, rocprim::radix_sort_pairs (d_tmp.p, tmp_bytes, d_keys.p, d_keys2.p, d_vals.p, d->ix.d_mers, (size_t) n_mers, 0, 32, d->stream));
     // prefix table: bucket ends scattered, then a running maximum over 2^32 + 1 entries
-    HIPCHK (d, hipMemsetAsync (d->d_pos_index, 0, POS_INDEX_N * sizeof (uint32_t), d->stream));
+    HIPCHK (d, hipMemsetAsync (d->ix.d_pos_index, 0, POS_INDEX_N * sizeof (uint32_t), d->stream));
     hipLaunchKernelGGL (ix_run_ends_kernel, dim3 ((unsigned) ((n_mers + 255) / 256)), dim3 (256), 0, d->stream, d_keys2, n_mers,
-                        d->d_pos_index);
+                        d->ix.d_pos_index);
     const uint64_t sc_tiles = (POS_INDEX_N + SC_TILE - 1) / SC_TILE;
     TRY (dev_alloc (d, &d_tmax.p, sc_tiles));
-    hipLaunchKernelGGL (ix_maxscan_reduce_kernel, dim3 ((unsigned) sc_tiles), dim3 (SC_BLOCK), 0, d->stream, d->d_pos_index, POS_INDEX_N, d_tmax);
+    hipLaunchKernelGGL (ix_maxscan_reduce_kernel, dim3 ((unsigned) sc_tiles), dim3 (SC_BLOCK), 0, d->stream, d->ix.d_pos_index, POS_INDEX_N, d_tmax);
     hipLaunchKernelGGL (ix_maxscan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d_tmax, sc_tiles);
-    hipLaunchKernelGGL (ix_maxscan_apply_kernel, dim3 ((unsigned) sc_tiles), dim3 (SC_BLOCK), 0, d->stream, d->d_pos_index, POS_INDEX_N, d_tmax);
+    hipLaunchKernelGGL (ix_maxscan_apply_kernel, dim3 ((unsigned) sc_tiles), dim3 (SC_BLOCK), 0, d->stream, d->ix.d_pos_index, POS_INDEX_N, d_tmax);
     HIPCHK (d, hipStreamSynchronize (d->stream));
     HIPCHK (d, hipGetLastError ());
   }
@@ -803,17 +877,13 @@ static int build_from_device_genome (pemap_dev * d, const uint32_t * contig_len,
 extern "C" int pemap_dev_build_index (pemap_dev * d, const char *genome, uint64_t genome_size, const uint32_t * contig_len,
                                       int n_contigs, int bisulfite)
 {
-  TRY (pemap_dev_index_alloc (d, 0, genome_size, n_contigs, 16));
-  HIPCHK (d, hipMemcpy (d->d_genome, genome, genome_size, hipMemcpyHostToDevice));
-  return build_from_device_genome (d, contig_len, n_contigs, bisulfite);
+  return build_from_genome (d, genome, hipMemcpyHostToDevice, genome_size, contig_len, n_contigs, bisulfite);
 }
 
 extern "C" int pemap_dev_build_index_resident (pemap_dev * d, const void *d_genome, uint64_t genome_size,
                                                const uint32_t * contig_len, int n_contigs, int bisulfite)
 {
-  TRY (pemap_dev_index_alloc (d, 0, genome_size, n_contigs, 16));
-  HIPCHK (d, hipMemcpy (d->d_genome, d_genome, genome_size, hipMemcpyDeviceToDevice));
-  return build_from_device_genome (d, contig_len, n_contigs, bisulfite);
+  return build_from_genome (d, d_genome, hipMemcpyDeviceToDevice, genome_size, contig_len, n_contigs, bisulfite);
 }
 
 // ---- plane 0 between counts and differences (PmPile, pemap_pile_diff.h).  Both conversions run on the ALU stream, behind whatever
@@ -839,25 +909,24 @@ struct PmConvTimer
   }
   ~PmConvTimer ()
   {
-    for (int i = 0; i < 2; i++)
-      if (ev[i])
-        hipEventDestroy (ev[i]);
+    pm_event_free (ev[0]);
+    pm_event_free (ev[1]);
   }
 };
 
 // counts -> differences, enqueued only: the pile kernels behind it on the stream find differences
 static int pile_unfold_locked (pemap_dev * d)
 {
-  if (d->pile_diff)
+  if (d->pile.diff)
     return 0;
-  const uint64_t n_words = d->pile_plane_words, n_tiles = (n_words + PD_TILE - 1) / PD_TILE;
+  const uint64_t n_words = d->pile.plane_words, n_tiles = (n_words + PD_TILE - 1) / PD_TILE;
   uint64_t sgrid = (n_tiles + PD_BLOCK - 1) / PD_BLOCK;
   if (sgrid > (uint64_t) d->n_cus * 8)
     sgrid = (uint64_t) d->n_cus * 8;
   const bool log = env_int ("PEMAP_PILE_CONV_LOG", 0) != 0;
   std::unique_ptr < PmConvTimer > tm (log ? new PmConvTimer (d->stream) : nullptr);
-  hipLaunchKernelGGL (pd_unfold_save_kernel, dim3 ((unsigned) sgrid), dim3 (PD_BLOCK), 0, d->stream, d->d_counts, n_tiles, d->d_pile_tiles);
-  hipLaunchKernelGGL (pd_unfold_apply_kernel, dim3 ((unsigned) n_tiles), dim3 (PD_BLOCK), 0, d->stream, d->d_counts, n_words, d->d_pile_tiles);
+  hipLaunchKernelGGL (pd_unfold_save_kernel, dim3 ((unsigned) sgrid), dim3 (PD_BLOCK), 0, d->stream, d->pile.d_counts, n_tiles, d->pile.d_tiles);
+  hipLaunchKernelGGL (pd_unfold_apply_kernel, dim3 ((unsigned) n_tiles), dim3 (PD_BLOCK), 0, d->stream, d->pile.d_counts, n_words, d->pile.d_tiles);
   HIPCHK (d, hipGetLastError ());
   if (tm)
     {
@@ -866,32 +935,32 @@ static int pile_unfold_locked (pemap_dev * d)
       HIPCHK (d, hipStreamSynchronize (d->stream));
       tm->report ("unfolded");
     }
-  d->pile_diff = true;
+  d->pile.diff = true;
   return 0;
 }
 
 // differences -> counts, and waited for: afterwards the planes hold what the reference's array would
 static int pile_fold_locked (pemap_dev * d)
 {
-  if (!d->pile_diff)
+  if (!d->pile.diff)
     return 0;
   HIPCHK (d, hipSetDevice (d->device));
-  const uint64_t n_words = d->pile_plane_words, n_tiles = (n_words + PD_TILE - 1) / PD_TILE;
+  const uint64_t n_words = d->pile.plane_words, n_tiles = (n_words + PD_TILE - 1) / PD_TILE;
   DevTmp < unsigned long long > d_total;
   TRY (dev_alloc (d, &d_total.p, 1));
   // PEMAP_PILE_CONV_LOG=1: either conversion's time on the device goes to stderr
   const bool log = env_int ("PEMAP_PILE_CONV_LOG", 0) != 0;
   std::unique_ptr < PmConvTimer > tm (log ? new PmConvTimer (d->stream) : nullptr);
-  hipLaunchKernelGGL (pd_fold_sums_kernel, dim3 ((unsigned) n_tiles), dim3 (PD_BLOCK), 0, d->stream, d->d_counts, n_words, d->d_pile_tiles);
-  hipLaunchKernelGGL (ix_sumscan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d->d_pile_tiles, n_tiles, d_total);
-  hipLaunchKernelGGL (pd_fold_apply_kernel, dim3 ((unsigned) n_tiles), dim3 (PD_BLOCK), 0, d->stream, d->d_counts, n_words, d->d_pile_tiles);
+  hipLaunchKernelGGL (pd_fold_sums_kernel, dim3 ((unsigned) n_tiles), dim3 (PD_BLOCK), 0, d->stream, d->pile.d_counts, n_words, d->pile.d_tiles);
+  hipLaunchKernelGGL (ix_sumscan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d->pile.d_tiles, n_tiles, d_total);
+  hipLaunchKernelGGL (pd_fold_apply_kernel, dim3 ((unsigned) n_tiles), dim3 (PD_BLOCK), 0, d->stream, d->pile.d_counts, n_words, d->pile.d_tiles);
   if (tm)
     tm->stop (d->stream);
   HIPCHK (d, hipGetLastError ());
   HIPCHK (d, hipStreamSynchronize (d->stream));
   if (tm)
     tm->report ("folded");
-  d->pile_diff = false;
+  d->pile.diff = false;
   return 0;
 }
 
@@ -901,21 +970,41 @@ static int pile_fold (pemap_dev * d)
   return pile_fold_locked (d);
 }
 
+// drain the device insertion log into the host copy and reset the cursor (stream must be idle)
+static int drain_ins (pemap_dev * d)
+{
+  HIPCHK (d, hipStreamSynchronize (d->stream));
+  PmInsCursor cur;
+  HIPCHK (d, hipMemcpy (&cur, d->pile.d_cur, sizeof (cur), hipMemcpyDeviceToHost));
+  unsigned nb = cur.ins_bytes;
+  if (nb > d->pile.ins_cap)
+    nb = d->pile.ins_cap;
+  if (nb)
+    {
+      size_t at = d->pile.h_ins.size ();
+      d->pile.h_ins.resize (at + nb);
+      HIPCHK (d, hipMemcpy (d->pile.h_ins.data () + at, d->pile.d_ins_log, nb, hipMemcpyDeviceToHost));
+    }
+  HIPCHK (d, hipMemset (d->pile.d_cur, 0, sizeof (PmInsCursor)));
+  d->run.last_cur.ins_bytes = 0;
+  return 0;
+}
+
 extern "C" int pemap_dev_buffer (pemap_dev * d, int which, void **d_ptr, uint64_t * n_bytes)
 {
-  if (!d->d_pos_index)
+  if (!d->ix.d_pos_index)
     return fail (d, "buffer: no index");
   if (which == 4)
     TRY (pile_fold (d));        // the view holds counts when it is handed out (include/pemap_hip.h)
   switch (which)
     {
-    case 0: *d_ptr = d->d_pos_index; *n_bytes = POS_INDEX_N * 4; break;
-    case 1: *d_ptr = d->d_mers; *n_bytes = d->n_mers * 4; break;
-    case 2: *d_ptr = d->d_genome; *n_bytes = d->gsize; break;
-    case 3: *d_ptr = d->d_contig_starts; *n_bytes = ((uint64_t) d->n_contigs + 1) * 4; break;
-    case 4: *d_ptr = d->d_counts; *n_bytes = 6 * d->pile_plane_words * 4; break;
-    case 5: *d_ptr = d->d_rep; *n_bytes = d->n_rep ? 8ull * (1ull << 32) * 4ull : 0ull; break;
-    case 6: *d_ptr = d->d_multi; *n_bytes = d->n_rep ? d->multi_units * 16ull : 0ull; break;
+    case 0: *d_ptr = d->ix.d_pos_index; *n_bytes = POS_INDEX_N * 4; break;
+    case 1: *d_ptr = d->ix.d_mers; *n_bytes = d->ix.n_mers * 4; break;
+    case 2: *d_ptr = d->ix.d_genome; *n_bytes = d->ix.gsize; break;
+    case 3: *d_ptr = d->ix.d_contig_starts; *n_bytes = ((uint64_t) d->ix.n_contigs + 1) * 4; break;
+    case 4: *d_ptr = d->pile.d_counts; *n_bytes = 6 * d->pile.plane_words * 4; break;
+    case 5: *d_ptr = d->ix.d_rep; *n_bytes = d->ix.n_rep ? 8ull * (1ull << 32) * 4ull : 0ull; break;
+    case 6: *d_ptr = d->ix.d_multi; *n_bytes = d->ix.n_rep ? d->ix.multi_units * 16ull : 0ull; break;
     default: return fail (d, "buffer: which = %d", which);
     }
   return 0;
@@ -923,12 +1012,12 @@ extern "C" int pemap_dev_buffer (pemap_dev * d, int which, void **d_ptr, uint64_
 
 extern "C" int pemap_dev_index_info (pemap_dev * d, uint64_t * n_mers, uint64_t * genome_size, int *n_contigs, int *idepth)
 {
-  if (!d->index_ready)
+  if (!d->ix.ready)
     return fail (d, "index_info: no index");
-  *n_mers = d->n_mers;
-  *genome_size = d->gsize;
-  *n_contigs = d->n_contigs;
-  *idepth = d->idepth;
+  *n_mers = d->ix.n_mers;
+  *genome_size = d->ix.gsize;
+  *n_contigs = d->ix.n_contigs;
+  *idepth = d->ix.idepth;
   return 0;
 }
 
@@ -945,68 +1034,88 @@ extern "C" int pemap_dev_read_buffer (pemap_dev * d, int which, uint64_t byte_of
   return 0;
 }
 
-// The parameters are read again when a batch is delivered (ring_finish: m2 is copied in paired mode; fold_summary: the second end's
-// length, the distance cut-off), and ring_setup delivers what is in flight when the pairing changed.  So a change first delivers
-// every batch in flight and absorbs the pending run, under the values they were submitted with; a call that changes nothing is free.
-extern "C" int pemap_dev_set_params (pemap_dev * d, int paired, int min_dist, int max_dist, double min_align, int bisulfite)
+// ---- staging: the read set's arrays and what they hold.  Either part is released through reads_free before it is made again and gets
+// its capacity behind its last allocation: where one fails the part is empty (null, capacity 0, nothing staged) and the next call makes it.
+static int ensure_reads (pemap_dev * d, int n, int stride, int paired)
 {
-  std::unique_lock < std::mutex > sub (d->submit_mu);   // (the order of ring_leave: no submit slips in while mu is dropped in ring_finish)
-  std::unique_lock < std::mutex > lk (d->mu);
-  paired = paired ? 1 : 0;
-  bisulfite = bisulfite ? 1 : 0;
-  if (d->paired == paired && d->min_dist == min_dist && d->max_dist == max_dist && d->min_align == min_align && d->bisulfite == bisulfite)
-    return 0;
-  bool busy = d->run_pending;
-  for (int i = 0; i < PM_RING; i++)
-    busy = busy || d->ring[i].active;
-  if (busy)
+  PmReadSet & R = d->rd;
+  if (n > R.cap || stride != R.stride || (paired && !R.d_rows[1]))
     {
-      HIPCHK (d, hipSetDevice (d->device));
-      TRY (ring_finish_all (d, lk));
-      if (d->run_pending)
+      const int cap = n > R.cap ? n : R.cap;
+      reads_free (R, true, false);
+      for (int m = 0; m < 2; m++)
         {
-          TRY (absorb_run (d));
-          d->run_pending = false;
+          TRY (dev_alloc (d, &R.d_rows[m], (size_t) cap * stride + 64));
+          TRY (dev_alloc (d, &R.d_len[m], (size_t) cap));
         }
+      R.cap = cap;
+      R.stride = stride;
     }
-  d->paired = paired;
-  d->min_dist = min_dist;
-  d->max_dist = max_dist;
-  d->min_align = min_align;
-  d->bisulfite = bisulfite;
+  if (n > R.cap_out)
+    {
+      reads_free (R, false, true);
+      TRY (dev_alloc (d, &R.d_m1, (size_t) n));
+      TRY (dev_alloc (d, &R.d_m2, (size_t) n));
+      TRY (dev_alloc (d, &R.d_mtype, (size_t) n));
+      R.cap_out = n;
+    }
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------------------
-static int ensure_reads (pemap_dev * d, int n, int stride, int paired)
+// the arrays hold n rows (pairs, if paired) whose lengths lie in mn..mx
+static void reads_staged (pemap_dev * d, int n, int paired, int mx, int mn)
 {
-  if (n > d->cap_reads || stride != d->stride || (paired && !d->d_reads2))
+  d->rd.n = n;
+  d->rd.paired = paired ? 1 : 0;
+  d->rd.max_len = mx;
+  d->rd.min_len = mn;
+}
+
+static int check_lengths (pemap_dev * d, const int *len, int n, int *mx, int *mn)
+{
+  for (int i = 0; i < n; i++)
     {
-      hipFree (d->d_reads1);
-      hipFree (d->d_reads2);
-      hipFree (d->d_len1);
-      hipFree (d->d_len2);
-      d->d_reads1 = d->d_reads2 = nullptr;
-      d->d_len1 = d->d_len2 = nullptr;
-      int cap = n > d->cap_reads ? n : d->cap_reads;
-      TRY (dev_alloc (d, &d->d_reads1, (size_t) cap * stride + 64));
-      TRY (dev_alloc (d, &d->d_len1, (size_t) cap));
-      TRY (dev_alloc (d, &d->d_reads2, (size_t) cap * stride + 64));
-      TRY (dev_alloc (d, &d->d_len2, (size_t) cap));
-      d->cap_reads = cap;
-      d->stride = stride;
-    }
-  if (n > d->cap_out)
-    {
-      hipFree (d->d_m1);
-      hipFree (d->d_m2);
-      hipFree (d->d_mtype);
-      TRY (dev_alloc (d, &d->d_m1, (size_t) n));
-      TRY (dev_alloc (d, &d->d_m2, (size_t) n));
-      TRY (dev_alloc (d, &d->d_mtype, (size_t) n));
-      d->cap_out = n;
+      if (len[i] < PEMAP_MIN_READ || len[i] > PEMAP_MAX_READ)
+        return fail (d, "read %d has length %d: supported range is %d..%d", i, len[i], PEMAP_MIN_READ, PEMAP_MAX_READ);
+      if (len[i] > *mx)
+        *mx = len[i];
+      if (len[i] < *mn)
+        *mn = len[i];
     }
   return 0;
+}
+
+// result fold of one finished batch, pemapper.c:1238-1265
+static void fold_summary (pemap_dev * d, int first, int n, const uint32_t * m1, const uint32_t * m2, const int *mapping_type)
+{
+  long *S = d->pile.summary;
+  for (int j = 0; j < n; j++)
+    {
+      uint32_t a = m1[j], b = (d->paired && m2) ? m2[j] : 0;
+      int la = d->rd.h_len[0][first + j], lb = d->paired ? d->rd.h_len[1][first + j] : 0;
+      S[4 + mapping_type[j]]++;
+      if (a)
+        {
+          S[0]++;
+          S[1] += la;
+          if (b)
+            {
+              S[0]++;
+              S[1] += lb;
+              long test = (long) (uint32_t) (a - b);    // unsigned difference widened to long, pemapper.c:1250
+              if (test < (long) d->max_dist * 4)
+                {
+                  S[2] += test;
+                  S[3]++;
+                }
+            }
+        }
+      else if (b)
+        {
+          S[0]++;
+          S[1] += lb;
+        }
+    }
 }
 
 // SW geometry for the longest staged read L: lanes per alignment and W columns per lane, the smallest instantiation with
@@ -1103,7 +1212,7 @@ static size_t task_quarter_words (int n_ends, bool multi)
 static PmTaskList task_list (const pemap_dev * d, const PmChunkSet & S, PmCounters * ctr, bool multi)
 {
   uint32_t *const t = multi ? S.tasks_m : S.tasks_s;
-  const size_t q = task_quarter_words (d->cap_ends, multi);
+  const size_t q = task_quarter_words (d->wk.cap_ends, multi);
   const bool rule = pm_gapless_on (d);
   PmTaskList l;
   l.all = t;
@@ -1121,60 +1230,55 @@ static PmTaskList task_list (const pemap_dev * d, const PmChunkSet & S, PmCounte
   return l;
 }
 
-static int alloc_hits (pemap_dev * d, PmHits & h, int n_ends)
-{
-  size_t nh = (size_t) n_ends * PM_MAX_HITS;
-  TRY (dev_alloc (d, &h.n_hits, (size_t) n_ends));
-  TRY (dev_alloc (d, &h.slot, (size_t) n_ends));
-  TRY (dev_alloc (d, &h.spot, nh));
-  TRY (dev_alloc (d, &h.gpos, nh));
-  TRY (dev_alloc (d, &h.nn, nh));
-  TRY (dev_alloc (d, &h.orient, nh));
-  TRY (dev_alloc (d, &h.score, nh));
-  TRY (dev_alloc (d, &h.sti, nh));
-  TRY (dev_alloc (d, &h.stk, nh));
-  return 0;
-}
-
 static int ensure_work (pemap_dev * d, int n_ends)
 {
-  if (n_ends > d->cap_ends)
+  if (n_ends > d->wk.cap_ends)
     {
-      free_work (d);
-      for (PmChunkSet & s : d->set)
+      work_free_ends (d->wk);
+      for (PmChunkSet & s : d->wk.set)
         {
-          TRY (alloc_hits (d, s.hits, n_ends));
+          PmHits & h = s.hits;
+          const size_t nh = (size_t) n_ends * PM_MAX_HITS;
+          TRY (dev_alloc (d, &h.n_hits, (size_t) n_ends));
+          TRY (dev_alloc (d, &h.slot, (size_t) n_ends));
+          TRY (dev_alloc (d, &h.spot, nh));
+          TRY (dev_alloc (d, &h.gpos, nh));
+          TRY (dev_alloc (d, &h.nn, nh));
+          TRY (dev_alloc (d, &h.orient, nh));
+          TRY (dev_alloc (d, &h.score, nh));
+          TRY (dev_alloc (d, &h.sti, nh));
+          TRY (dev_alloc (d, &h.stk, nh));
           TRY (dev_alloc (d, &s.wins, (size_t) n_ends));
           TRY (dev_alloc (d, &s.walks, (size_t) n_ends));
           TRY (dev_alloc (d, &s.tasks_s, task_quarter_words (n_ends, false) * PM_TASK_QUARTERS));
           TRY (dev_alloc (d, &s.tasks_m, task_quarter_words (n_ends, true) * PM_TASK_QUARTERS));
         }
-      TRY (dev_alloc (d, &d->d_redo, (size_t) n_ends));
-      d->cap_ends = n_ends;
+      TRY (dev_alloc (d, &d->wk.d_redo, (size_t) n_ends));
+      d->wk.cap_ends = n_ends;
     }
-  if (!d->d_seed_scratch)
-    TRY (dev_alloc (d, &d->d_seed_scratch, (size_t) d->big_grid * 6 * PM_MAX_SEG * PM_SEG_LIST_MAX));
-  const size_t need = ((size_t) n_ends + 1) * slab_dwords_for (d, d->max_len_staged); // + 1: dump slab for task-less lane groups
-  if (need > d->dirbuf_dwords)
+  if (!d->wk.d_seed_scratch)
+    TRY (dev_alloc (d, &d->wk.d_seed_scratch, (size_t) d->wk.big_grid * 6 * PM_MAX_SEG * PM_SEG_LIST_MAX));
+  const size_t need = ((size_t) n_ends + 1) * slab_dwords_for (d, d->rd.max_len); // + 1: dump slab for task-less lane groups
+  if (need > d->wk.dirbuf_dwords)
     {
-      free_dirs (d);
-      for (PmChunkSet & s : d->set)
+      work_free_dirs (d->wk);
+      for (PmChunkSet & s : d->wk.set)
         TRY (dev_alloc (d, &s.dirbuf, need));
-      d->dirbuf_dwords = need;
+      d->wk.dirbuf_dwords = need;
     }
-  d->dir_slabs = d->dirbuf_dwords / slab_dwords_for (d, d->max_len_staged);
+  d->wk.dir_slabs = d->wk.dirbuf_dwords / slab_dwords_for (d, d->rd.max_len);
   // recorded traceback steps: PM_PATH_WORDS words of 32 two-bit steps per read-end
-  const int pwords = PM_PATH_WORDS (d->max_len_staged);
-  if (n_ends > d->path_cap_ends || pwords != d->path_words)
+  const int pwords = PM_PATH_WORDS (d->rd.max_len);
+  if (n_ends > d->wk.path_cap_ends || pwords != d->wk.path_words)
     {
-      free_paths (d);
-      for (PmChunkSet & s : d->set)
+      work_free_paths (d->wk);
+      for (PmChunkSet & s : d->wk.set)
         {
           TRY (dev_alloc (d, &s.path, (size_t) n_ends * pwords));
           TRY (dev_alloc (d, &s.nsteps, (size_t) n_ends));
         }
-      d->path_words = pwords;
-      d->path_cap_ends = n_ends;
+      d->wk.path_words = pwords;
+      d->wk.path_cap_ends = n_ends;
     }
   // insertion log: 64 bytes per read-end of a chunk is ample for real data, and at least 512 MB so that runs queued back to
   // back (the log is drained when a run is absorbed) do not fill it; overflow is reported as an error
@@ -1183,64 +1287,56 @@ static int ensure_work (pemap_dev * d, int n_ends)
     want = (size_t) 512 << 20;
   if (want > 0xF0000000ull)
     want = 0xF0000000ull;
-  if (want > d->ins_cap)
+  if (want > d->pile.ins_cap)
     {
       TRY (drain_ins (d));
-      hipFree (d->d_ins_log);
-      TRY (dev_alloc (d, &d->d_ins_log, want));
-      d->ins_cap = (unsigned) want;
+      pm_free (d->pile.d_ins_log);
+      d->pile.ins_cap = 0;     // (set again behind the allocation: a log that is not there holds nothing)
+      TRY (dev_alloc (d, &d->pile.d_ins_log, want));
+      d->pile.ins_cap = (unsigned) want;
     }
   return 0;
 }
 
-static int check_lengths (pemap_dev * d, const int *len, int n, int *mx, int *mn)
+static int seg_template (int L)
 {
-  for (int i = 0; i < n; i++)
-    {
-      if (len[i] < PEMAP_MIN_READ || len[i] > PEMAP_MAX_READ)
-        return fail (d, "read %d has length %d: supported range is %d..%d", i, len[i], PEMAP_MIN_READ, PEMAP_MAX_READ);
-      if (len[i] > *mx)
-        *mx = len[i];
-      if (len[i] < *mn)
-        *mn = len[i];
-    }
-  return 0;
+  const int segs = L / 16 + ((L % 16) ? 1 : 0);      // len/16 (+1 unless divisible), pemapper.c:1573-1587
+  return segs <= 7 ? 7 : segs <= 10 ? 10 : segs <= 13 ? 13 : segs <= 16 ? 16 : 19;
 }
 
-extern "C" int pemap_dev_stage_reads (pemap_dev * d, const char *reads1, const int *len1, const char *reads2, const int *len2,
-                                      int n, int stride)
+// f (std::integral_constant < int, SM >) for the segment template SM of reads up to L bases
+template < class F > static void with_seg_template (int L, F f)
 {
-  HIPCHK (d, hipSetDevice (d->device));
-  if (n <= 0)
-    return fail (d, "stage_reads: n = %d", n);
-  if (d->paired && (!reads2 || !len2))
-    return fail (d, "stage_reads: paired mode needs reads2/len2");
-  if (stride < PEMAP_MIN_READ)
-    return fail (d, "stage_reads: stride %d", stride);
-  int mx = 0, mn = 1 << 30;
-  TRY (check_lengths (d, len1, n, &mx, &mn));
-  if (d->paired)
-    TRY (check_lengths (d, len2, n, &mx, &mn));
-  if (mx > stride)
-    return fail (d, "stage_reads: a read is longer than the row stride %d", stride);
-  TRY (ring_leave (d));
-  TRY (pemap_dev_sync (d));
-  TRY (ensure_reads (d, n, stride, d->paired));
-  HIPCHK (d, hipMemcpy (d->d_reads1, reads1, (size_t) n * stride, hipMemcpyHostToDevice));
-  HIPCHK (d, hipMemcpy (d->d_len1, len1, (size_t) n * sizeof (int), hipMemcpyHostToDevice));
-  d->h_len1.assign (len1, len1 + n);
-  d->h_len2.clear ();
-  if (d->paired)
+  switch (seg_template (L))
     {
-      HIPCHK (d, hipMemcpy (d->d_reads2, reads2, (size_t) n * stride, hipMemcpyHostToDevice));
-      HIPCHK (d, hipMemcpy (d->d_len2, len2, (size_t) n * sizeof (int), hipMemcpyHostToDevice));
-      d->h_len2.assign (len2, len2 + n);
+    case 7: f (std::integral_constant < int, 7 > {}); break;
+    case 10: f (std::integral_constant < int, 10 > {}); break;
+    case 13: f (std::integral_constant < int, 13 > {}); break;
+    case 16: f (std::integral_constant < int, 16 > {}); break;
+    default: f (std::integral_constant < int, 19 > {}); break;
     }
-  d->n_staged = n;
-  d->staged_paired = d->paired;
-  d->max_len_staged = mx;
-  d->min_len_staged = mn;
-  return 0;
+}
+
+// chunk size run_slice cuts a run of n pairs of reads up to L bases into
+static int chunk_pairs_for (const pemap_dev * d, int n, int L)
+{
+  const int per = d->paired ? 2 : 1;
+  // one direction slab per read-end must fit the budget; the pipeline wants several chunks per run
+  size_t slab_bytes = slab_dwords_for (d, L) * 4;
+  long max_ends = (long) (dir_budget_bytes (d) / slab_bytes);
+  if (max_ends > 20000000)
+    max_ends = 20000000;        // task ids are end * 200 + hit in 32 bits
+  int chunk = (int) (max_ends / per);
+  const int want = d->kn.chunk_pairs;
+  if (want > 0 && chunk > want)
+    chunk = want;
+  if (chunk < 1)
+    chunk = 1;
+  if (chunk > n)
+    chunk = n;
+  if ((n + chunk - 1) / chunk > PM_MAX_CHUNKS)
+    chunk = (n + PM_MAX_CHUNKS - 1) / PM_MAX_CHUNKS;
+  return chunk;
 }
 
 __global__ void pm_nop_kernel ()
@@ -1266,38 +1362,6 @@ struct RunCtx
   size_t dump_off;              // dwords from the start of a set's dirbuf to its dump slab
 };
 
-// per-chunk device counters: the kernels' PmCounters plus what the look-up kernel counts
-struct PmChunkCtr
-{
-  PmCounters c;
-  unsigned long long positions;
-  unsigned n_big;
-  unsigned next_end;            // work counter of the persistent look-up waves
-  unsigned n_big2;              // read-ends the second tier of the fused seed kernel leaves to pm_seed_kernel
-  unsigned next_end2;           // the second tier's work counter
-};
-
-#define PM_MAX_CHUNKS 256
-
-static int seg_template (int L)
-{
-  const int segs = L / 16 + ((L % 16) ? 1 : 0);      // len/16 (+1 unless divisible), pemapper.c:1573-1587
-  return segs <= 7 ? 7 : segs <= 10 ? 10 : segs <= 13 ? 13 : segs <= 16 ? 16 : 19;
-}
-
-// f (std::integral_constant < int, SM >) for the segment template SM of reads up to L bases
-template < class F > static void with_seg_template (int L, F f)
-{
-  switch (seg_template (L))
-    {
-    case 7: f (std::integral_constant < int, 7 > {}); break;
-    case 10: f (std::integral_constant < int, 10 > {}); break;
-    case 13: f (std::integral_constant < int, 13 > {}); break;
-    case 16: f (std::integral_constant < int, 16 > {}); break;
-    default: f (std::integral_constant < int, 19 > {}); break;
-    }
-}
-
 #ifndef PM_LOOKUP_WAVES_DEFAULT
 #define PM_LOOKUP_WAVES_DEFAULT 12
 #endif
@@ -1305,7 +1369,7 @@ template < class F > static void with_seg_template (int L, F f)
 // is the seed stage of this run the fused kernel (pm_seed4_kernel: look-ups and vote of a read-end in one wave)?
 static bool pm_fused (const pemap_dev * d)
 {
-  return d->n_rep == 8;
+  return d->ix.n_rep == 8;
 }
 
 // The seed stage's schedule, decided once per run by run_slice ("The seed stage's schedule"):
@@ -1349,7 +1413,7 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
         lds = sizeof (PmSeed4Shared < sm.value, 0 >);
         if (sm.value <= 10)
           per_simd = PM_S4_WAVES_PER_EU;
-        int &res = d->seed_resident[sm.value];
+        int &res = d->run.seed_resident[sm.value];
         if (res <= 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor (&res, pm_seed4_kernel < sm.value, 0 >, 64, lds) != hipSuccess)
           res = 0;
         fit = res;
@@ -1361,10 +1425,10 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
         lw = fit;
       if (lw > 4 * per_simd)
         lw = 4 * per_simd;
-      d->seed_launch[0] = lw_asked;
-      d->seed_launch[1] = resident;
-      d->seed_launch[2] = lw;
-      d->seed_launch[3] = (int) lds;
+      d->run.seed_launch[0] = lw_asked;
+      d->run.seed_launch[1] = resident;
+      d->run.seed_launch[2] = lw;
+      d->run.seed_launch[3] = (int) lds;
     }
   int lgrid = lw * d->n_cus;
   if (lgrid > c.b.n_ends)
@@ -1384,7 +1448,7 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
   // the list (twice, for reads over 160 bases), a few waves per CU -- most launches find a few thousand ends; what THAT leaves goes
   // to pm_seed_kernel (launch_rest)
   PmLists L2 = L;
-  L2.big_list = L.big_list + d->lists_cap;
+  L2.big_list = L.big_list + d->wk.lists_cap;
   L2.n_big = &cc->n_big2;
   L2.next_end = &cc->next_end2;
   const int grid2 = d->kn.tier2_waves * d->n_cus;
@@ -1433,10 +1497,10 @@ static void launch_rest (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChun
 {
   // The remainder appends to the chunk's task lists and uses the one spill scratch: a second launch for the same chunk doubles the
   // appended tasks past the lists' ends (the fault PEMAP_REST_STREAM3=1 produced in round 3).  Refused here, reported by run_slice.
-  const uint64_t id = (d->run_serial << 24) | (uint64_t) (cc - d->d_chunk_ctr);
+  const uint64_t id = (d->run.serial << 24) | (uint64_t) (cc - d->run.d_chunk_ctr);
   if (S.rest_id == id)
     {
-      d->rest_twice = true;
+      d->run.rest_twice = true;
       return;
     }
   S.rest_id = id;
@@ -1444,13 +1508,13 @@ static void launch_rest (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChun
   const unsigned *n_list = &cc->n_big;
   if (pm_fused (d))
     {
-      list += d->lists_cap;
+      list += d->wk.lists_cap;
       n_list = &cc->n_big2;
     }
   with_seg_template (c.L, [&] (auto sm)
   {
-    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed_kernel < sm.value >), dim3 (d->big_grid), dim3 (PM_SEED_THREADS), 0, st, c.ix, c.b, c.prm, S.hits, S.tasks_s,
-                        S.tasks_m, &cc->c, d->d_seed_scratch, d->big_grid, list, n_list);
+    hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed_kernel < sm.value >), dim3 (d->wk.big_grid), dim3 (PM_SEED_THREADS), 0, st, c.ix, c.b, c.prm, S.hits, S.tasks_s,
+                        S.tasks_m, &cc->c, d->wk.d_seed_scratch, d->wk.big_grid, list, n_list);
   });
   hipEventRecord (S.ev_lists_free, st);
 }
@@ -1465,9 +1529,9 @@ static void launch_emit (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChun
 // ---- the seed stream's work for chunk g (the chunk's rows in c.b)
 static int enqueue_seed (pemap_dev * d, const PmSchedule & s, const RunCtx & c, int g, const hipEvent_t * copy_ev)
 {
-  PmChunkSet & S = d->set[g % PM_SETS];
-  PmChunkCtr *cc = d->d_chunk_ctr + g;
-  hipEvent_t *ev = &d->evs[(size_t) g * PM_NEV];
+  PmChunkSet & S = d->wk.set[g % PM_SETS];
+  PmChunkCtr *cc = d->run.d_chunk_ctr + g;
+  hipEvent_t *ev = &d->run.evs[(size_t) g * PM_NEV];
   if (copy_ev)
     HIPCHK (d, hipStreamWaitEvent (s.seed, *copy_ev, 0));
   // the set's lists must have been consumed by the remainder of chunk g - PM_SETS
@@ -1514,7 +1578,7 @@ template < int W, int LPA, bool DIRS > static auto launch_cascade (pemap_dev * d
   // keeps the routing by x <= 6 alone -- its full DP is one pass whatever the band takes, and the problems are spared the second
   // launch.  PEMAP_BAND_GATE=1 / 0 decide for every chunk.  (The outputs are the same either way.)
   PmTaskList lg = l;
-  if (d->kn.band_gate < 0 && (long) n_ends <= (long) d->sw_grid * (64 / LPA))
+  if (d->kn.band_gate < 0 && (long) n_ends <= (long) d->wk.sw_grid * (64 / LPA))
     lg.n_gate = nullptr;
   // the multi-hit list's rule and band launches fill the device; the single-hit list holds at most one problem per read-end
   int ggrid = d->n_cus * 16, bgrid = d->n_cus * d->kn.band_waves_per_cu;
@@ -1553,7 +1617,7 @@ template < int W, int LPA, bool DIRS > static auto launch_cascade (pemap_dev * d
   if (l.band)
     hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_band_kernel < DIRS >), dim3 (bgrid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, S.hits, l.band, l.n_band, ctr,
                         S.dirbuf, slab_dwords_for (d, c.L), l.band_next);
-  hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, DIRS >), dim3 (d->sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, S.hits, l.dp, l.n_dp, ctr,
+  hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, DIRS >), dim3 (d->wk.sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, S.hits, l.dp, l.n_dp, ctr,
                       S.dirbuf, S.dirbuf + c.dump_off, c.tstride, c.L, d->kn.sw_prio, l.dp_next);
 }
 
@@ -1576,11 +1640,11 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
   hipEventRecord (ev[PM_EV_SW_SINGLE_END], d->stream);
   launch_cascade < W, LPA, false > (d, c, S, ctr, task_list (d, S, ctr, true));
   hipEventRecord (ev[PM_EV_SW_MULTI_END], d->stream);
-  hipLaunchKernelGGL (pm_select_kernel, dim3 ((c.b.n + 63) / 64), dim3 (64), 0, d->stream, c.b, c.prm, H, d->d_redo, wins, S.walks,
+  hipLaunchKernelGGL (pm_select_kernel, dim3 ((c.b.n + 63) / 64), dim3 (64), 0, d->stream, c.b, c.prm, H, d->wk.d_redo, wins, S.walks,
                       ctr, m1, m2, mt);
   hipEventRecord (ev[PM_EV_SELECT_END], d->stream);
-  hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, true >), dim3 (d->sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H,
-                      d->d_redo, &ctr->n_redo, ctr, dirbuf, dirbuf + c.dump_off, c.tstride, c.L, d->kn.sw_prio, &ctr->sw_next[2]);
+  hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_sw_kernel < W, LPA, true >), dim3 (d->wk.sw_grid), dim3 (64), 0, d->stream, c.ix, c.b, c.prm, H,
+                      d->wk.d_redo, &ctr->n_redo, ctr, dirbuf, dirbuf + c.dump_off, c.tstride, c.L, d->kn.sw_prio, &ctr->sw_next[2]);
   hipEventRecord (ev[PM_EV_SW_REDO_END], d->stream);
   // PEMAP_WALK_BLOCKS_PER_CU (default 4, swept 1..16): resident 256-lane blocks of the walk per CU; few enough walkers that
   // their direction lines stay in L2 between steps
@@ -1589,8 +1653,8 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
   if (wgrid > d->n_cus * wbp * 4)
     wgrid = d->n_cus * wbp * 4;         // (waves: the knob counts blocks of four)
   // (the walk on the look-up stream, beside the next chunk's vote and SW, was tried: 107 ms per step against 103; it stays here)
-  hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_walk_kernel < W, LPA >), dim3 (wgrid), dim3 (64), 0, d->stream, c.b, H, wins, S.walks, ctr, d->d_cur,
-                      dirbuf, c.tstride, pile_of (d), d->d_ins_log, d->ins_cap, S.path, d->path_words, S.nsteps);
+  hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_walk_kernel < W, LPA >), dim3 (wgrid), dim3 (64), 0, d->stream, c.b, H, wins, S.walks, ctr, d->pile.d_cur,
+                      dirbuf, c.tstride, pile_of (d), d->pile.d_ins_log, d->pile.ins_cap, S.path, d->wk.path_words, S.nsteps);
   // the winners applied to the pileup: the plain diagonals two to a wave, then the walked ones, one wave each, by their recorded steps
   // PEMAP_PILE_BLOCKS_PER_CU (default 4, swept 2 / 3 / 4 / 6 / 8 in round 9): the waves wait for their atomics' old words, and more of
   // them than this only take wave slots from the seed kernel on the other stream
@@ -1599,7 +1663,7 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
   if (pgrid > d->n_cus * pbp * 4)
     pgrid = d->n_cus * pbp * 4;         // (waves: the knob counts blocks of four)
   hipLaunchKernelGGL (pm_pile_kernel, dim3 (pgrid), dim3 (64), 0, d->stream, c.b, H, wins, ctr, pile_of (d));
-  hipLaunchKernelGGL (pm_pile_walked_kernel, dim3 (pgrid), dim3 (64), 0, d->stream, c.b, H, wins, S.walks, ctr, pile_of (d), S.path, d->path_words, S.nsteps);
+  hipLaunchKernelGGL (pm_pile_walked_kernel, dim3 (pgrid), dim3 (64), 0, d->stream, c.b, H, wins, S.walks, ctr, pile_of (d), S.path, d->wk.path_words, S.nsteps);
   hipEventRecord (ev[PM_EV_WALK_END], d->stream);
   hipEventRecord (S.ev_walk_done, d->stream);
 }
@@ -1607,9 +1671,9 @@ template < int W, int LPA > static void launch_chunk (pemap_dev * d, const PmSch
 // wait for the run in flight and fold its chunks' counters and kernel times into the run's totals
 static int absorb_run (pemap_dev * d)
 {
-  HIPCHK (d, hipStreamSynchronize (d->stream2));
+  HIPCHK (d, hipStreamSynchronize (d->run.stream2));
   HIPCHK (d, hipStreamSynchronize (d->stream));
-  const int nch = d->run_chunks;
+  const int nch = d->run.chunks;
 #ifdef PEMAP_TIMING_PROBES
   {
     // the fused seed kernel's phase probes (pemap_seed4.hip.h): cycles summed over waves, printed per run
@@ -1638,9 +1702,9 @@ static int absorb_run (pemap_dev * d)
   }
 #endif
   std::vector < PmChunkCtr > hc (nch);
-  HIPCHK (d, hipMemcpy (hc.data (), d->d_chunk_ctr, sizeof (PmChunkCtr) * nch, hipMemcpyDeviceToHost));
-  HIPCHK (d, hipMemcpy (&d->last_cur, d->d_cur, sizeof (PmInsCursor), hipMemcpyDeviceToHost));
-  PmCounters & t = d->last_ctr;
+  HIPCHK (d, hipMemcpy (hc.data (), d->run.d_chunk_ctr, sizeof (PmChunkCtr) * nch, hipMemcpyDeviceToHost));
+  HIPCHK (d, hipMemcpy (&d->run.last_cur, d->pile.d_cur, sizeof (PmInsCursor), hipMemcpyDeviceToHost));
+  PmCounters & t = d->run.last_ctr;
   for (int k = 0; k < nch; k++)
     {
       const PmCounters & c = hc[k].c;
@@ -1662,49 +1726,63 @@ static int absorb_run (pemap_dev * d)
       t.cells_dirs += c.cells_dirs;
       t.pile_incs += c.pile_incs;
       t.n_ins += c.n_ins;
-      d->last_big += hc[k].n_big;
-      d->last_big2 += hc[k].n_big2;
-      hipEvent_t *ev = &d->evs[(size_t) k * PM_NEV];
+      d->run.last_big += hc[k].n_big;
+      d->run.last_big2 += hc[k].n_big2;
+      hipEvent_t *ev = &d->run.evs[(size_t) k * PM_NEV];
       float ms = 0.f;
       for (const auto & iv : pm_intervals)
         if (hipEventElapsedTime (&ms, ev[iv.from], ev[iv.to]) == hipSuccess)
           {
-            d->last_ms[iv.slot] += ms;
-            d->last_ms[PM_T_SEED] += iv.seed_too ? ms : 0.f;
+            d->run.last_ms[iv.slot] += ms;
+            d->run.last_ms[PM_T_SEED] += iv.seed_too ? ms : 0.f;
           }
     }
-  if (d->last_cur.ins_overflow)
-    return fail (d, "insertion log overflow (%u bytes): lower PEMAP_CHUNK_PAIRS or map smaller slices", d->ins_cap);
-  if (d->last_cur.ins_bytes > d->ins_cap / 2)
+  if (d->run.last_cur.ins_overflow)
+    return fail (d, "insertion log overflow (%u bytes): lower PEMAP_CHUNK_PAIRS or map smaller slices", d->pile.ins_cap);
+  if (d->run.last_cur.ins_bytes > d->pile.ins_cap / 2)
     return drain_ins (d);
+  return 0;
+}
+
+static int absorb_pending (pemap_dev * d)
+{
+  if (d->run.pending)
+    {
+      TRY (absorb_run (d));
+      d->run.pending = false;
+    }
   return 0;
 }
 
 static int ensure_pipeline (pemap_dev * d, int chunk_ends)
 {
-  if (!d->stream2)
+  // (a CU mask and stream priorities for the look-up stream were tried in rounds 1 and 2 and gave nothing)
+  if (!d->run.stream2)
+    HIPCHK (d, hipStreamCreateWithFlags (&d->run.stream2, hipStreamNonBlocking));
+  if (d->run.evs.empty ())
     {
-      // (a CU mask and stream priorities for the look-up stream were tried in rounds 1 and 2 and gave nothing)
-      HIPCHK (d, hipStreamCreateWithFlags (&d->stream2, hipStreamNonBlocking));
-      TRY (dev_alloc (d, &d->d_chunk_ctr, (size_t) PM_MAX_CHUNKS));
-      d->evs.resize ((size_t) PM_MAX_CHUNKS * PM_NEV);
-      for (size_t i = 0; i < d->evs.size (); i++)
-        HIPCHK (d, hipEventCreate (&d->evs[i]));
-    }
-  if (chunk_ends > d->lists_cap || (chunk_ends > 0 && !pm_fused (d) && !d->lists_arrays))
-    {
-      if (chunk_ends < d->lists_cap)
-        chunk_ends = d->lists_cap;
-      // (the look-up kernels of a pending run may still be writing the old arrays)
-      if (d->run_pending)
+      // (the counters and the events are there together or not at all: the next call tries again)
+      int rc = dev_alloc (d, &d->run.d_chunk_ctr, (size_t) PM_MAX_CHUNKS);
+      d->run.evs.resize ((size_t) PM_MAX_CHUNKS * PM_NEV, nullptr);
+      for (size_t i = 0; !rc && i < d->run.evs.size (); i++)
+        if (hipEventCreate (&d->run.evs[i]) != hipSuccess)
+          rc = fail (d, "hipEventCreate failed");
+      if (rc)
         {
-          TRY (absorb_run (d));
-          d->run_pending = false;
+          run_free (d->run);
+          return rc;
         }
-      free_lists (d);
+    }
+  if (chunk_ends > d->wk.lists_cap || (chunk_ends > 0 && !pm_fused (d) && !d->wk.lists_arrays))
+    {
+      if (chunk_ends < d->wk.lists_cap)
+        chunk_ends = d->wk.lists_cap;
+      // (the look-up kernels of a pending run may still be writing the old arrays)
+      TRY (absorb_pending (d));
+      work_free_lists (d->wk);
       // (the fused seed kernel keeps the lists in LDS: only the big-end list is needed then)
       const size_t list_ends = pm_fused (d) ? 0 : (size_t) chunk_ends;
-      for (PmChunkSet & s : d->set)
+      for (PmChunkSet & s : d->wk.set)
         {
           TRY (dev_alloc (d, &s.lists.hdr, list_ends));
           TRY (dev_alloc (d, &s.lists.key, list_ends * 2 * PM_SEED_CAP));
@@ -1712,32 +1790,10 @@ static int ensure_pipeline (pemap_dev * d, int chunk_ends)
           // (first half: the ends the fused seed kernel passes over; second half: what its second tier leaves of them)
           TRY (dev_alloc (d, &s.lists.big_list, 2 * (size_t) chunk_ends));
         }
-      d->lists_arrays = !pm_fused (d);
-      d->lists_cap = chunk_ends;
+      d->wk.lists_arrays = !pm_fused (d);
+      d->wk.lists_cap = chunk_ends;
     }
   return 0;
-}
-
-// chunk size run_slice cuts a run of n pairs of reads up to L bases into
-static int chunk_pairs_for (const pemap_dev * d, int n, int L)
-{
-  const int per = d->paired ? 2 : 1;
-  // one direction slab per read-end must fit the budget; the pipeline wants several chunks per run
-  size_t slab_bytes = slab_dwords_for (d, L) * 4;
-  long max_ends = (long) (dir_budget_bytes (d) / slab_bytes);
-  if (max_ends > 20000000)
-    max_ends = 20000000;        // task ids are end * 200 + hit in 32 bits
-  int chunk = (int) (max_ends / per);
-  const int want = d->kn.chunk_pairs;
-  if (want > 0 && chunk > want)
-    chunk = want;
-  if (chunk < 1)
-    chunk = 1;
-  if (chunk > n)
-    chunk = n;
-  if ((n + chunk - 1) / chunk > PM_MAX_CHUNKS)
-    chunk = (n + PM_MAX_CHUNKS - 1) / PM_MAX_CHUNKS;
-  return chunk;
 }
 
 // copy_evs (may be NULL): one event per chunk, recorded behind the host-to-device copy of that chunk's rows; the first stream
@@ -1746,15 +1802,15 @@ static int chunk_pairs_for (const pemap_dev * d, int n, int L)
 static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_t * copy_evs = nullptr)
 {
   HIPCHK (d, hipSetDevice (d->device));
-  if (!d->index_ready)
+  if (!d->ix.ready)
     return fail (d, "run: no index loaded");
-  if (d->n_staged <= 0)
+  if (d->rd.n <= 0)
     return fail (d, "run: no reads staged");
-  if (first < 0 || n <= 0 || first + n > d->n_staged)
-    return fail (d, "run: slice [%d, %d) outside the %d staged reads", first, first + n, d->n_staged);
-  if (d->staged_paired != d->paired)
-    return fail (d, "run: reads were staged in %s mode", d->staged_paired ? "paired" : "single");
-  const int L = d->max_len_staged;
+  if (first < 0 || n <= 0 || first + n > d->rd.n)
+    return fail (d, "run: slice [%d, %d) outside the %d staged reads", first, first + n, d->rd.n);
+  if (d->rd.paired != d->paired)
+    return fail (d, "run: reads were staged in %s mode", d->rd.paired ? "paired" : "single");
+  const int L = d->rd.max_len;
   const int per = d->paired ? 2 : 1;
   const int chunk = chunk_pairs_for (d, n, L);
   const int nch = (n + chunk - 1) / chunk;
@@ -1762,25 +1818,24 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
   // sets, same event chain), so that look-ups of this run's first chunk overlap the previous run's last.  The pending runs
   // are absorbed first only when the per-chunk bookkeeping would overflow or the geometry changes.
   int k0 = 0;
-  if (d->run_pending)
+  if (d->run.pending)
     {
       // (a smaller chunk than the pending runs' fits their arrays: the tail of a batch continues the pipeline too)
-      const bool same = d->kn.pipeline == 1 && d->run_L == L && chunk * per <= d->cap_ends
-        && chunk * per <= d->lists_cap && (size_t) (chunk * per) < d->dir_slabs;
-      if (same && d->run_chunks + nch <= PM_MAX_CHUNKS)
-        k0 = d->run_chunks;
+      const bool same = d->kn.pipeline == 1 && d->run.L == L && chunk * per <= d->wk.cap_ends
+        && chunk * per <= d->wk.lists_cap && (size_t) (chunk * per) < d->wk.dir_slabs;
+      if (same && d->run.chunks + nch <= PM_MAX_CHUNKS)
+        k0 = d->run.chunks;
       else
         {
           // (why, for pemap_dev_pipeline_stats: the chunk table is full; the longest read changed; anything else of `same`)
-          d->pstat[same ? 2 : d->kn.pipeline == 1 && d->run_L != L ? 3 : 4]++;
-          TRY (absorb_run (d));
-          d->run_pending = false;
+          d->run.pstat[same ? PM_PS_ABSORB_TABLE_FULL : d->kn.pipeline == 1 && d->run.L != L ? PM_PS_ABSORB_LENGTH : PM_PS_ABSORB_ARRAYS]++;
+          TRY (absorb_pending (d));
         }
     }
-  d->pstat[0]++;
-  d->pstat[1] += k0 > 0;
-  d->pstat[6] = (uint64_t) nch;
-  d->pstat[7] = (uint64_t) k0;
+  d->run.pstat[PM_PS_RUNS]++;
+  d->run.pstat[PM_PS_CONTINUED] += k0 > 0;
+  d->run.pstat[PM_PS_LAST_CHUNKS] = (uint64_t) nch;
+  d->run.pstat[PM_PS_LAST_FIRST_CHUNK] = (uint64_t) k0;
   TRY (ensure_work (d, chunk * per));
   TRY (ensure_pipeline (d, chunk * per));
   // PEMAP_PIPELINE=1 (default): the seed stage on stream2, PM_SETS chunks ahead of the ALU stream; 2: everything on the ALU stream.
@@ -1790,7 +1845,7 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
   // 16.3 at 2 x 160, 11.1 against 11.3 at 2 x 100), behind the seed kernel for longer ones (2 x 245: 56.9 ms against 58.6).
   PmSchedule s;
   s.ahead = d->kn.pipeline == 1;
-  s.seed = s.ahead ? d->stream2 : d->stream;
+  s.seed = s.ahead ? d->run.stream2 : d->stream;
   s.emit_on_alu = s.ahead && pm_fused (d) && seg_template (L) <= 10;
   RunCtx c;
   c.ix = index_of (d);
@@ -1798,36 +1853,36 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
   c.L = L;
   c.tstride = tstride_for (d, L);
   // (the last slab of the allocation, whatever this run's chunk size: chunks of earlier, larger runs may still be in flight)
-  c.dump_off = (d->dir_slabs - 1) * slab_dwords_for (d, L);
+  c.dump_off = (d->wk.dir_slabs - 1) * slab_dwords_for (d, L);
   if (k0 == 0)
     {
-      memset (&d->last_ctr, 0, sizeof (d->last_ctr));
-      memset (d->last_ms, 0, sizeof (d->last_ms));
-      d->last_big = d->last_big2 = 0;
-      d->run_ends = 0;
+      memset (&d->run.last_ctr, 0, sizeof (d->run.last_ctr));
+      memset (d->run.last_ms, 0, sizeof (d->run.last_ms));
+      d->run.last_big = d->run.last_big2 = 0;
+      d->run.ends = 0;
     }
   // the first chunk that finds plane 0 holding counts has them turned into differences, ahead of its pile kernel on the ALU stream
   TRY (pile_unfold_locked (d));
-  d->run_serial++;
-  d->run_first = first;
-  d->run_n = n;
-  d->run_ends += (uint64_t) n * per;
-  d->run_chunks = k0 + nch;
-  d->run_L = L;
+  d->run.serial++;
+  d->run.first = first;
+  d->run.n = n;
+  d->run.ends += (uint64_t) n * per;
+  d->run.chunks = k0 + nch;
+  d->run.L = L;
   // fresh per-chunk counters: zeroed on the stream that touches them first (the seed stream, so that a queued run's first
   // look-ups do not wait for the previous run's ALU work)
-  HIPCHK (d, hipMemsetAsync (d->d_chunk_ctr + k0, 0, sizeof (PmChunkCtr) * nch, s.seed));
+  HIPCHK (d, hipMemsetAsync (d->run.d_chunk_ctr + k0, 0, sizeof (PmChunkCtr) * nch, s.seed));
   auto batch_of = [&] (int k, PmBatch & bb, int &f, int &m)
   {
     const int off = k * chunk;
     m = (n - off < chunk) ? n - off : chunk;
     f = first + off;
-    bb.reads1 = d->d_reads1 + (size_t) f * d->stride;
-    bb.reads2 = d->paired ? d->d_reads2 + (size_t) f * d->stride : nullptr;
-    bb.len1 = d->d_len1 + f;
-    bb.len2 = d->paired ? d->d_len2 + f : nullptr;
+    bb.reads1 = d->rd.d_rows[0] + (size_t) f * d->rd.stride;
+    bb.reads2 = d->paired ? d->rd.d_rows[1] + (size_t) f * d->rd.stride : nullptr;
+    bb.len1 = d->rd.d_len[0] + f;
+    bb.len2 = d->paired ? d->rd.d_len[1] + f : nullptr;
     bb.n = m;
-    bb.stride = d->stride;
+    bb.stride = d->rd.stride;
     bb.paired = d->paired;
     bb.n_ends = m * per;
   };
@@ -1847,14 +1902,14 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
       int f, m;
       batch_of (k, c.b, f, m);
       const int g = k0 + k;
-      PmChunkSet & S = d->set[g % PM_SETS];
-      PmChunkCtr *cc = d->d_chunk_ctr + g;
-      hipEvent_t *ev = &d->evs[(size_t) g * PM_NEV];
+      PmChunkSet & S = d->wk.set[g % PM_SETS];
+      PmChunkCtr *cc = d->run.d_chunk_ctr + g;
+      hipEvent_t *ev = &d->run.evs[(size_t) g * PM_NEV];
       if (!s.ahead)
         TRY (enqueue_seed_k (k));
       HIPCHK (d, hipStreamWaitEvent (d->stream, S.ev_lists_ready, 0));
-      uint32_t *m1 = d->d_m1 + f, *m2 = d->paired ? d->d_m2 + f : nullptr;
-      int *mt = d->d_mtype + f;
+      uint32_t *m1 = d->rd.d_m1 + f, *m2 = d->paired ? d->rd.d_m2 + f : nullptr;
+      int *mt = d->rd.d_mtype + f;
       with_sw_geom (d, L, [&] (auto w, auto lanes)
       {
         launch_chunk < w.value, lanes.value > (d, s, c, m1, m2, mt, S, cc, ev);
@@ -1863,21 +1918,18 @@ static int run_slice (pemap_dev * d, int first, int n, int sync, const hipEvent_
       if (s.ahead && k + PM_SETS < nch)
         TRY (enqueue_seed_k (k + PM_SETS));
     }
-  if (d->rest_twice)
+  if (d->run.rest_twice)
     return fail (d, "internal: the seed-stage remainder of a chunk was enqueued twice");
-  d->run_pending = true;
+  d->run.pending = true;
   if (sync)
-    {
-      TRY (absorb_run (d));
-      d->run_pending = false;
-    }
+    TRY (absorb_pending (d));
   return 0;
 }
 
 extern "C" int pemap_dev_run (pemap_dev * d, int sync)
 {
   std::lock_guard < std::mutex > lk (d->mu);
-  return run_slice (d, 0, d->n_staged, sync);
+  return run_slice (d, 0, d->rd.n, sync);
 }
 
 extern "C" int pemap_dev_run_slice (pemap_dev * d, int first, int n, int sync)
@@ -1889,45 +1941,21 @@ extern "C" int pemap_dev_run_slice (pemap_dev * d, int first, int n, int sync)
 extern "C" int pemap_dev_sync (pemap_dev * d)
 {
   HIPCHK (d, hipSetDevice (d->device));
-  if (d->run_pending)
-    {
-      TRY (absorb_run (d));
-      d->run_pending = false;
-    }
+  TRY (absorb_pending (d));
   HIPCHK (d, hipStreamSynchronize (d->stream));
-  return 0;
-}
-
-// drain the device insertion log into the host copy and reset the cursor (stream must be idle)
-static int drain_ins (pemap_dev * d)
-{
-  HIPCHK (d, hipStreamSynchronize (d->stream));
-  PmInsCursor cur;
-  HIPCHK (d, hipMemcpy (&cur, d->d_cur, sizeof (cur), hipMemcpyDeviceToHost));
-  unsigned nb = cur.ins_bytes;
-  if (nb > d->ins_cap)
-    nb = d->ins_cap;
-  if (nb)
-    {
-      size_t at = d->h_ins.size ();
-      d->h_ins.resize (at + nb);
-      HIPCHK (d, hipMemcpy (d->h_ins.data () + at, d->d_ins_log, nb, hipMemcpyDeviceToHost));
-    }
-  HIPCHK (d, hipMemset (d->d_cur, 0, sizeof (PmInsCursor)));
-  d->last_cur.ins_bytes = 0;
   return 0;
 }
 
 extern "C" int pemap_dev_collect (pemap_dev * d, uint32_t * m1, uint32_t * m2, int *mapping_type)
 {
   TRY (pemap_dev_sync (d));
-  const int n = d->run_n, first = d->run_first;
+  const int n = d->run.n, first = d->run.first;
   if (n <= 0)
     return fail (d, "collect: nothing was run");
-  HIPCHK (d, hipMemcpy (m1, d->d_m1 + first, (size_t) n * sizeof (uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK (d, hipMemcpy (m1, d->rd.d_m1 + first, (size_t) n * sizeof (uint32_t), hipMemcpyDeviceToHost));
   if (d->paired && m2)
-    HIPCHK (d, hipMemcpy (m2, d->d_m2 + first, (size_t) n * sizeof (uint32_t), hipMemcpyDeviceToHost));
-  HIPCHK (d, hipMemcpy (mapping_type, d->d_mtype + first, (size_t) n * sizeof (int), hipMemcpyDeviceToHost));
+    HIPCHK (d, hipMemcpy (m2, d->rd.d_m2 + first, (size_t) n * sizeof (uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK (d, hipMemcpy (mapping_type, d->rd.d_mtype + first, (size_t) n * sizeof (int), hipMemcpyDeviceToHost));
   TRY (drain_ins (d));
   fold_summary (d, first, n, m1, m2, mapping_type);
   return 0;
@@ -1939,39 +1967,6 @@ extern "C" int pemap_dev_collect (pemap_dev * d, uint32_t * m1, uint32_t * m2, i
 // copies (their own stream) and its kernels (the object's pipeline, continued from the batch before) and returns; wait blocks
 // until the batch's m1 / m2 / mapping_type are in the caller's buffers.  With two or three batches in flight the copies of
 // batch k + 1 and the results of batch k - 1 move while batch k is computed, and the pipeline never drains between calls.
-
-// result fold of one finished batch, pemapper.c:1238-1265
-static void fold_summary (pemap_dev * d, int first, int n, const uint32_t * m1, const uint32_t * m2, const int *mapping_type)
-{
-  long *S = d->summary;
-  for (int j = 0; j < n; j++)
-    {
-      uint32_t a = m1[j], b = (d->paired && m2) ? m2[j] : 0;
-      int la = d->h_len1[first + j], lb = d->paired ? d->h_len2[first + j] : 0;
-      S[4 + mapping_type[j]]++;
-      if (a)
-        {
-          S[0]++;
-          S[1] += la;
-          if (b)
-            {
-              S[0]++;
-              S[1] += lb;
-              long test = (long) (uint32_t) (a - b);    // unsigned difference widened to long, pemapper.c:1250
-              if (test < (long) d->max_dist * 4)
-                {
-                  S[2] += test;
-                  S[3]++;
-                }
-            }
-        }
-      else if (b)
-        {
-          S[0]++;
-          S[1] += lb;
-        }
-    }
-}
 
 // is [p, p + bytes) inside a range pinned by the caller?
 bool pm_host_pin_lookup (const void *p, size_t bytes)
@@ -2057,7 +2052,7 @@ extern "C" int pemap_dev_pin_host (pemap_dev * d, const void *host_ptr, uint64_t
   HIPCHK (d, hipSetDevice (d->device));
   if (!host_ptr || !n_bytes)
     return fail (d, "pin_host: empty range");
-  if (!pm_host_pin_range (host_ptr, (size_t) n_bytes, d->stream_h2d))
+  if (!pm_host_pin_range (host_ptr, (size_t) n_bytes, d->rg.stream_h2d))
     return fail (d, "pin_host: hipHostRegister of %llu bytes failed", (unsigned long long) n_bytes);
   return 0;
 }
@@ -2088,8 +2083,8 @@ extern "C" int pemap_dev_unpin_host (pemap_dev * d, const void *host_ptr)
   // copies out of the range may still be queued on this object's copy stream
   {
     std::lock_guard < std::mutex > lk (d->mu);
-    if (d->stream_h2d)
-      HIPCHK (d, hipStreamSynchronize (d->stream_h2d));
+    if (d->rg.stream_h2d)
+      HIPCHK (d, hipStreamSynchronize (d->rg.stream_h2d));
   }
   const int rc = pm_host_unpin (host_ptr);
   if (rc == 1)
@@ -2102,7 +2097,7 @@ extern "C" int pemap_dev_unpin_host (pemap_dev * d, const void *host_ptr)
 // wait for the batch in `slot` and deliver it (mu held through lk; released while the host blocks on the event)
 static int ring_finish (pemap_dev * d, int slot, std::unique_lock < std::mutex > &lk)
 {
-  PmRingSlot & r = d->ring[slot];
+  PmRingSlot & r = d->rg.slot[slot];
   if (!r.active)
     return 0;
   const unsigned long long seq = r.seq;
@@ -2117,8 +2112,8 @@ static int ring_finish (pemap_dev * d, int slot, std::unique_lock < std::mutex >
   const int n = r.n;
   memcpy (r.m1, r.h_res, (size_t) n * 4);
   if (d->paired && r.m2)
-    memcpy (r.m2, r.h_res + d->ring_cap, (size_t) n * 4);
-  memcpy (r.mt, r.h_res + 2 * (size_t) d->ring_cap, (size_t) n * 4);
+    memcpy (r.m2, r.h_res + d->rg.cap, (size_t) n * 4);
+  memcpy (r.mt, r.h_res + 2 * (size_t) d->rg.cap, (size_t) n * 4);
   fold_summary (d, r.first, n, r.m1, r.m2, r.mt);
   r.active = false;
   return 0;
@@ -2131,7 +2126,7 @@ static int ring_finish_all (pemap_dev * d, std::unique_lock < std::mutex > &lk)
     {
       int pick = -1;
       for (int i = 0; i < PM_RING; i++)
-        if (d->ring[i].active && (pick < 0 || d->ring[i].seq < d->ring[pick].seq))
+        if (d->rg.slot[i].active && (pick < 0 || d->rg.slot[i].seq < d->rg.slot[pick].seq))
           pick = i;
       if (pick < 0)
         return 0;
@@ -2139,64 +2134,99 @@ static int ring_finish_all (pemap_dev * d, std::unique_lock < std::mutex > &lk)
     }
 }
 
-// the staged arrays go back to holding one resident read set (stage_reads, synth_reads): no batch may be in flight
-static int ring_leave (pemap_dev * d)
+// the staged arrays go back to holding one resident read set, of n rows at `stride` (stage_reads, stage_fastq, synth_reads): the
+// batches in flight are delivered, the pending run is accounted, the arrays are there
+static int ring_leave (pemap_dev * d, int n, int stride, int paired)
 {
-  std::unique_lock < std::mutex > sub (d->submit_mu);
-  std::unique_lock < std::mutex > lk (d->mu);
-  TRY (ring_finish_all (d, lk));
-  d->ring_cap = 0;
-  return 0;
+  {
+    std::unique_lock < std::mutex > sub (d->submit_mu);
+    std::unique_lock < std::mutex > lk (d->mu);
+    TRY (ring_finish_all (d, lk));
+    d->rg.cap = 0;
+  }
+  TRY (pemap_dev_sync (d));
+  return ensure_reads (d, n, stride, paired);
 }
 
 static int ring_setup (pemap_dev * d, int n, int stride, std::unique_lock < std::mutex > &lk)
 {
-  if (!d->stream_h2d)
-    {
-      HIPCHK (d, hipStreamCreateWithFlags (&d->stream_h2d, hipStreamNonBlocking));
-    }
-  if (d->ring_cap >= n && d->stride == stride && d->staged_paired == d->paired && (!d->paired || d->d_reads2))
+  if (!d->rg.stream_h2d)
+    HIPCHK (d, hipStreamCreateWithFlags (&d->rg.stream_h2d, hipStreamNonBlocking));
+  if (d->rg.cap >= n && d->rd.stride == stride && d->rd.paired == d->paired && (!d->paired || d->rd.d_rows[1]))
     return 0;
   // a different geometry: everything in flight is delivered and accounted first
-  d->pstat[5]++;
+  d->run.pstat[PM_PS_RING_SETUPS]++;
   TRY (ring_finish_all (d, lk));
-  if (d->run_pending)
-    {
-      TRY (absorb_run (d));
-      d->run_pending = false;
-    }
+  TRY (absorb_pending (d));
   HIPCHK (d, hipDeviceSynchronize ());
-  int cap = n > d->ring_cap ? n : d->ring_cap;
+  int cap = n > d->rg.cap ? n : d->rg.cap;
   if (cap < 1024)
     cap = 1024;
   if ((long) cap * PM_RING > 2000000000L)
     return fail (d, "submit_batch: %d reads per batch are too many", n);
+  // (from here to its last block the ring is not set up: rg.cap is 0, and a submit after a failure comes through here again)
+  ring_free (d->rg, true);
   TRY (ensure_reads (d, cap * PM_RING, stride, d->paired));
-  for (int i = 0; i < PM_RING; i++)
+  for (PmRingSlot & r : d->rg.slot)
     {
-      PmRingSlot & r = d->ring[i];
-      if (r.h_len)
-        hipHostFree (r.h_len);
-      if (r.h_res)
-        hipHostFree (r.h_res);
-      r.h_len = nullptr;
-      r.h_res = nullptr;
-      if (r.h_rows)
-        hipHostFree (r.h_rows);
-      r.h_rows = nullptr;
-      r.h_rows_bytes = 0;
       HIPCHK (d, hipHostMalloc ((void **) &r.h_len, (size_t) cap * 2 * sizeof (int), hipHostMallocDefault));
       HIPCHK (d, hipHostMalloc ((void **) &r.h_res, (size_t) cap * 3 * sizeof (uint32_t), hipHostMallocDefault));
       if (!r.ev_done)
         HIPCHK (d, hipEventCreateWithFlags (&r.ev_done, hipEventDisableTiming));
     }
-  d->ring_cap = cap;
-  d->n_staged = cap * PM_RING;
-  d->staged_paired = d->paired;
-  d->max_len_staged = 0;
-  d->min_len_staged = 1 << 30;
-  d->h_len1.assign ((size_t) cap * PM_RING, 0);
-  d->h_len2.assign (d->paired ? (size_t) cap * PM_RING : 0, 0);
+  d->rg.cap = cap;
+  reads_staged (d, cap * PM_RING, d->paired, 0, 1 << 30);
+  d->rd.h_len[0].assign ((size_t) cap * PM_RING, 0);
+  d->rd.h_len[1].assign (d->paired ? (size_t) cap * PM_RING : 0, 0);
+  return 0;
+}
+
+// ---- what the two submits share.  A batch of n rows at `stride` gets the slot of this submission (mu and submit_mu held): the ring
+// set up for it, the batch that used the slot PM_RING submissions ago delivered; `first` is the slot's first row in the staged arrays.
+struct PmSlotTake
+{
+  PmRingSlot *r;
+  int first;
+  uint8_t *rows[2];             // per mate: the slot's device rows and lengths, its pinned staging of the lengths
+  int *lens[2], *h_len[2];
+};
+
+static int ring_take (pemap_dev * d, int n, int stride, std::unique_lock < std::mutex > &lk, PmSlotTake & t)
+{
+  TRY (ring_setup (d, n, stride, lk));
+  const int slot = (int) (d->rg.seq % PM_RING);
+  TRY (ring_finish (d, slot, lk));
+  t.r = &d->rg.slot[slot];
+  t.first = slot * d->rg.cap;
+  for (int m = 0; m < 2; m++)
+    {
+      t.rows[m] = d->rd.d_rows[m] + (size_t) t.first * stride;
+      t.lens[m] = d->rd.d_len[m] + t.first;
+      t.h_len[m] = t.r->h_len + (size_t) m * d->rg.cap;
+    }
+  return 0;
+}
+
+// The batch's lengths (mn..mx) in: the kernels' geometry follows the longest read seen since the ring was set up (any upper bound gives
+// the same results; a bound that never shrinks keeps consecutive batches in one pipeline).  Then the pipeline's streams, which must exist
+// before the first copy event is waited on, and one copy event per slice of the batch, the slices cut like the kernels' chunks (chunk
+// k's look-ups wait for r.ev_copy[k]).  *slice receives the slice's size in rows.
+static int ring_slices (pemap_dev * d, PmRingSlot & r, int n, int mx, int mn, int *slice)
+{
+  if (mx > d->rd.max_len)
+    d->rd.max_len = mx;
+  if (mn < d->rd.min_len)
+    d->rd.min_len = mn;
+  if (!d->run.stream2)
+    TRY (ensure_pipeline (d, 0));
+  *slice = chunk_pairs_for (d, n, d->rd.max_len);
+  const int n_slices = (n + *slice - 1) / *slice;
+  while ((int) r.ev_copy.size () < n_slices)
+    {
+      hipEvent_t e;
+      HIPCHK (d, hipEventCreateWithFlags (&e, hipEventDisableTiming));
+      r.ev_copy.push_back (e);
+    }
   return 0;
 }
 
@@ -2209,31 +2239,101 @@ static int ring_queue_run (pemap_dev * d, PmRingSlot & r, int first, int n, uint
   // Not on a stream of their own: HIP multiplexes streams onto a few hardware queues, and a copy stream parked on "batch k is
   // done" held up whichever pipeline stream shared its queue -- 3.5 ms per batch (measured: 45.2 ms per step against 41.7).
   hipStream_t rs = d->stream;
-  HIPCHK (d, hipMemcpyAsync (r.h_res, d->d_m1 + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
+  HIPCHK (d, hipMemcpyAsync (r.h_res, d->rd.d_m1 + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
   if (d->paired)
-    HIPCHK (d, hipMemcpyAsync (r.h_res + d->ring_cap, d->d_m2 + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
-  HIPCHK (d, hipMemcpyAsync (r.h_res + 2 * (size_t) d->ring_cap, d->d_mtype + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
+    HIPCHK (d, hipMemcpyAsync (r.h_res + d->rg.cap, d->rd.d_m2 + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
+  HIPCHK (d, hipMemcpyAsync (r.h_res + 2 * (size_t) d->rg.cap, d->rd.d_mtype + first, (size_t) n * 4, hipMemcpyDeviceToHost, rs));
   HIPCHK (d, hipEventRecord (r.ev_done, rs));
   // the slot becomes a batch in flight only now that its event is recorded: an error above leaves it free, and nothing stale is
   // ever "delivered" into the caller's buffers or folded into the summary
   r.active = true;
-  r.seq = d->ring_seq;
+  r.seq = d->rg.seq;
   r.n = n;
   r.first = first;
   r.m1 = m1;
   r.m2 = m2;
   r.mt = mapping_type;
-  *ticket = d->ring_seq++;
+  *ticket = d->rg.seq++;
+  return 0;
+}
+
+static bool ring_busy (pemap_dev * d)
+{
+  std::lock_guard < std::mutex > lk (d->mu);
+  return ring_active (d->rg);
+}
+
+// The parameters are read again when a batch is delivered (ring_finish: m2 is copied in paired mode; fold_summary: the second end's
+// length, the distance cut-off), and ring_setup delivers what is in flight when the pairing changed.  So a change first delivers
+// every batch in flight and absorbs the pending run, under the values they were submitted with; a call that changes nothing is free.
+extern "C" int pemap_dev_set_params (pemap_dev * d, int paired, int min_dist, int max_dist, double min_align, int bisulfite)
+{
+  std::unique_lock < std::mutex > sub (d->submit_mu);   // (the order of ring_leave: no submit slips in while mu is dropped in ring_finish)
+  std::unique_lock < std::mutex > lk (d->mu);
+  paired = paired ? 1 : 0;
+  bisulfite = bisulfite ? 1 : 0;
+  if (d->paired == paired && d->min_dist == min_dist && d->max_dist == max_dist && d->min_align == min_align && d->bisulfite == bisulfite)
+    return 0;
+  if (d->run.pending || ring_active (d->rg))
+    {
+      HIPCHK (d, hipSetDevice (d->device));
+      TRY (ring_finish_all (d, lk));
+      TRY (absorb_pending (d));
+    }
+  d->paired = paired;
+  d->min_dist = min_dist;
+  d->max_dist = max_dist;
+  d->min_align = min_align;
+  d->bisulfite = bisulfite;
+  return 0;
+}
+
+// what stage_reads and submit_batch ask of the caller's n rows; the longest and the shortest read
+static int check_rows (pemap_dev * d, const char *who, const int *len1, const int *len2, int n, int stride, int *mx, int *mn)
+{
+  if (stride < PEMAP_MIN_READ)
+    return fail (d, "%s: stride %d", who, stride);
+  *mx = 0;
+  *mn = 1 << 30;
+  TRY (check_lengths (d, len1, n, mx, mn));
+  if (d->paired)
+    TRY (check_lengths (d, len2, n, mx, mn));
+  if (*mx > stride)
+    return fail (d, "%s: a read is longer than the row stride %d", who, stride);
+  return 0;
+}
+
+extern "C" int pemap_dev_stage_reads (pemap_dev * d, const char *reads1, const int *len1, const char *reads2, const int *len2,
+                                      int n, int stride)
+{
+  HIPCHK (d, hipSetDevice (d->device));
+  if (n <= 0)
+    return fail (d, "stage_reads: n = %d", n);
+  if (d->paired && (!reads2 || !len2))
+    return fail (d, "stage_reads: paired mode needs reads2/len2");
+  int mx, mn;
+  TRY (check_rows (d, "stage_reads", len1, len2, n, stride, &mx, &mn));
+  TRY (ring_leave (d, n, stride, d->paired));
+  const char *const rows[2] = { reads1, reads2 };
+  const int *const lens[2] = { len1, len2 };
+  d->rd.h_len[1].clear ();
+  for (int m = 0; m < (d->paired ? 2 : 1); m++)
+    {
+      HIPCHK (d, hipMemcpy (d->rd.d_rows[m], rows[m], (size_t) n * stride, hipMemcpyHostToDevice));
+      HIPCHK (d, hipMemcpy (d->rd.d_len[m], lens[m], (size_t) n * sizeof (int), hipMemcpyHostToDevice));
+      d->rd.h_len[m].assign (lens[m], lens[m] + n);
+    }
+  reads_staged (d, n, d->paired, mx, mn);
   return 0;
 }
 
 extern "C" int pemap_dev_submit_batch (pemap_dev * d, const char *reads1, const int *len1, const char *reads2, const int *len2,
                                        int n, int stride, uint32_t * m1, uint32_t * m2, int *mapping_type, uint64_t * ticket)
 {
-  std::unique_lock < std::mutex > sub (d->submit_mu);   // ring_seq, the slot and `first` below stay this call's own while mu is dropped
+  std::unique_lock < std::mutex > sub (d->submit_mu);   // rg.seq, the slot and `first` below stay this call's own while mu is dropped
   std::unique_lock < std::mutex > lk (d->mu);
   HIPCHK (d, hipSetDevice (d->device));
-  if (!d->index_ready)
+  if (!d->ix.ready)
     return fail (d, "submit_batch: no index loaded");
   if (n <= 0)
     return fail (d, "submit_batch: n = %d", n);
@@ -2241,82 +2341,50 @@ extern "C" int pemap_dev_submit_batch (pemap_dev * d, const char *reads1, const 
     return fail (d, "submit_batch: a required pointer is NULL");
   if (d->paired && (!reads2 || !len2 || !m2))
     return fail (d, "submit_batch: paired mode needs reads2 / len2 / m2");
-  if (stride < PEMAP_MIN_READ)
-    return fail (d, "submit_batch: stride %d", stride);
-  int mx = 0, mn = 1 << 30;
-  TRY (check_lengths (d, len1, n, &mx, &mn));
-  if (d->paired)
-    TRY (check_lengths (d, len2, n, &mx, &mn));
-  if (mx > stride)
-    return fail (d, "submit_batch: a read is longer than the row stride %d", stride);
-  TRY (ring_setup (d, n, stride, lk));
-  const int slot = (int) (d->ring_seq % PM_RING);
-  PmRingSlot & r = d->ring[slot];
-  TRY (ring_finish (d, slot, lk));      // the batch that used the slot PM_RING submissions ago
-  const int first = slot * d->ring_cap;
-  // the kernels' geometry follows the longest read seen since the ring was set up (any upper bound gives the same results;
-  // a bound that never shrinks keeps consecutive batches in one pipeline)
-  if (mx > d->max_len_staged)
-    d->max_len_staged = mx;
-  if (mn < d->min_len_staged)
-    d->min_len_staged = mn;
-  memcpy (&d->h_len1[first], len1, (size_t) n * sizeof (int));
-  memcpy (r.h_len, len1, (size_t) n * sizeof (int));
-  HIPCHK (d, hipMemcpyAsync (d->d_len1 + first, r.h_len, (size_t) n * sizeof (int), hipMemcpyHostToDevice, d->stream_h2d));
-  if (d->paired)
+  int mx, mn;
+  TRY (check_rows (d, "submit_batch", len1, len2, n, stride, &mx, &mn));
+  PmSlotTake t;
+  TRY (ring_take (d, n, stride, lk, t));
+  PmRingSlot & r = *t.r;
+  const int first = t.first, mates = d->paired ? 2 : 1;
+  const char *const rows[2] = { reads1, reads2 };
+  const int *const lens[2] = { len1, len2 };
+  for (int m = 0; m < mates; m++)
     {
-      memcpy (&d->h_len2[first], len2, (size_t) n * sizeof (int));
-      memcpy (r.h_len + d->ring_cap, len2, (size_t) n * sizeof (int));
-      HIPCHK (d, hipMemcpyAsync (d->d_len2 + first, r.h_len + d->ring_cap, (size_t) n * sizeof (int), hipMemcpyHostToDevice, d->stream_h2d));
+      memcpy (&d->rd.h_len[m][first], lens[m], (size_t) n * sizeof (int));
+      memcpy (t.h_len[m], lens[m], (size_t) n * sizeof (int));
+      HIPCHK (d, hipMemcpyAsync (t.lens[m], t.h_len[m], (size_t) n * sizeof (int), hipMemcpyHostToDevice, d->rg.stream_h2d));
     }
   // the rows move by DMA straight out of the caller's buffers when the caller pinned them (pemap_dev_pin_host); otherwise they
   // are copied, slice by slice, into the slot's pinned staging buffer first (the DMA of slice k runs beside the host copy of k + 1)
-  const bool direct1 = pm_host_pin_lookup (reads1, (size_t) n * stride);
-  const bool direct2 = d->paired ? pm_host_pin_lookup (reads2, (size_t) n * stride) : true;
-  if (!direct1 || !direct2)
+  bool direct[2] = { true, true };
+  for (int m = 0; m < mates; m++)
+    direct[m] = pm_host_pin_lookup (rows[m], (size_t) n * stride);
+  const size_t need = (size_t) d->rg.cap * stride * 2;
+  if ((!direct[0] || !direct[1]) && r.h_rows_bytes < need)
     {
-      const size_t need = (size_t) d->ring_cap * stride * 2;
-      if (r.h_rows_bytes < need)
-        {
-          if (r.h_rows)
-            hipHostFree (r.h_rows);
-          r.h_rows = nullptr;
-          r.h_rows_bytes = 0;
-          HIPCHK (d, hipHostMalloc ((void **) &r.h_rows, need, hipHostMallocDefault));
-          r.h_rows_bytes = need;
-        }
+      pm_host_free (r.h_rows);
+      r.h_rows_bytes = 0;
+      HIPCHK (d, hipHostMalloc ((void **) &r.h_rows, need, hipHostMallocDefault));
+      r.h_rows_bytes = need;
     }
-  if (!d->stream2)
-    TRY (ensure_pipeline (d, 0));       // the pipeline's streams must exist before the first copy event is waited on
-  // the copies are cut like the kernels' chunks, one event each: chunk k's look-ups start when its rows have landed
-  const int slice = chunk_pairs_for (d, n, d->max_len_staged);
-  const int n_slices = (n + slice - 1) / slice;
-  while ((int) r.ev_copy.size () < n_slices)
-    {
-      hipEvent_t e;
-      HIPCHK (d, hipEventCreateWithFlags (&e, hipEventDisableTiming));
-      r.ev_copy.push_back (e);
-    }
+  int slice;
+  TRY (ring_slices (d, r, n, mx, mn, &slice));
   for (int k = 0, off = 0; off < n; off += slice, k++)
     {
-      const int m = n - off < slice ? n - off : slice;
-      const char *src1 = reads1 + (size_t) off * stride, *src2 = d->paired ? reads2 + (size_t) off * stride : nullptr;
-      if (!direct1)
+      const int cnt = n - off < slice ? n - off : slice;
+      for (int m = 0; m < mates; m++)
         {
-          char *stg = r.h_rows + (size_t) off * stride;
-          pm_par_memcpy (stg, src1, (size_t) m * stride);
-          src1 = stg;
+          const char *src = rows[m] + (size_t) off * stride;
+          if (!direct[m])
+            {
+              char *stg = r.h_rows + ((size_t) m * d->rg.cap + off) * stride;
+              pm_par_memcpy (stg, src, (size_t) cnt * stride);
+              src = stg;
+            }
+          HIPCHK (d, hipMemcpyAsync (t.rows[m] + (size_t) off * stride, src, (size_t) cnt * stride, hipMemcpyHostToDevice, d->rg.stream_h2d));
         }
-      if (d->paired && !direct2)
-        {
-          char *stg = r.h_rows + ((size_t) d->ring_cap + off) * stride;
-          pm_par_memcpy (stg, src2, (size_t) m * stride);
-          src2 = stg;
-        }
-      HIPCHK (d, hipMemcpyAsync (d->d_reads1 + (size_t) (first + off) * stride, src1, (size_t) m * stride, hipMemcpyHostToDevice, d->stream_h2d));
-      if (d->paired)
-        HIPCHK (d, hipMemcpyAsync (d->d_reads2 + (size_t) (first + off) * stride, src2, (size_t) m * stride, hipMemcpyHostToDevice, d->stream_h2d));
-      HIPCHK (d, hipEventRecord (r.ev_copy[k], d->stream_h2d));
+      HIPCHK (d, hipEventRecord (r.ev_copy[k], d->rg.stream_h2d));
     }
   return ring_queue_run (d, r, first, n, m1, m2, mapping_type, ticket);
 }
@@ -2325,10 +2393,10 @@ extern "C" int pemap_dev_wait_batch (pemap_dev * d, uint64_t ticket)
 {
   std::unique_lock < std::mutex > lk (d->mu);
   HIPCHK (d, hipSetDevice (d->device));
-  if (ticket >= d->ring_seq)
+  if (ticket >= d->rg.seq)
     return fail (d, "wait_batch: ticket %llu was never handed out", (unsigned long long) ticket);
   const int slot = (int) (ticket % PM_RING);
-  if (!d->ring[slot].active || d->ring[slot].seq != ticket)
+  if (!d->rg.slot[slot].active || d->rg.slot[slot].seq != ticket)
     return 0;                   // delivered already (by a later submit that needed the slot, or by another wait)
   return ring_finish (d, slot, lk);
 }
@@ -2342,15 +2410,9 @@ extern "C" int pemap_dev_map_batch (pemap_dev * d, const char *reads1, const int
   TRY (pemap_dev_submit_batch (d, reads1, len1, reads2, len2, n, stride, m1, m2, mapping_type, &t));
   TRY (pemap_dev_wait_batch (d, t));
   std::unique_lock < std::mutex > lk (d->mu);
-  bool idle = true;
-  for (int i = 0; i < PM_RING; i++)
-    idle = idle && !d->ring[i].active;
-  if (idle && d->run_pending)
-    {
-      // nothing else in flight: account the run now (counters, kernel times, insertion log), so that run_stats describes this call
-      TRY (absorb_run (d));
-      d->run_pending = false;
-    }
+  // nothing else in flight: account the run now (counters, kernel times, insertion log), so that run_stats describes this call
+  if (!ring_active (d->rg))
+    TRY (absorb_pending (d));
   // the one-call entry hands the counters back as counts: a view of buffer 4 taken before the call is read after it.  (With other
   // threads' batches still in flight the fold queues behind them, and their next chunk unfolds again.)
   return pile_fold_locked (d);
@@ -2358,7 +2420,7 @@ extern "C" int pemap_dev_map_batch (pemap_dev * d, const char *reads1, const int
 
 extern "C" int pemap_dev_summary (pemap_dev * d, long *out13)
 {
-  memcpy (out13, d->summary, sizeof (d->summary));
+  memcpy (out13, d->pile.summary, sizeof (d->pile.summary));
   return 0;
 }
 
@@ -2368,17 +2430,17 @@ extern "C" int pemap_dev_pipeline_stats (pemap_dev * d, uint64_t * out8)
   if (!out8)
     return fail (d, "pipeline_stats: out8 must not be NULL");
   std::lock_guard < std::mutex > lk (d->mu);
-  memcpy (out8, d->pstat, sizeof (d->pstat));
+  memcpy (out8, d->run.pstat, sizeof (d->run.pstat));
   return 0;
 }
 
 extern "C" int pemap_dev_run_stats (pemap_dev * d, uint64_t * s, float *t)
 {
   TRY (pemap_dev_sync (d));     // a run still in flight is accounted first
-  const PmCounters & c = d->last_ctr;
+  const PmCounters & c = d->run.last_ctr;
   if (s)
     {
-      s[0] = d->run_ends;
+      s[0] = d->run.ends;
       s[1] = c.positions;
       s[2] = (uint64_t) c.n_tasks_s + c.n_tasks_m;
       s[3] = (uint64_t) c.n_tasks_dp + c.n_band[0] + c.n_redo;
@@ -2388,18 +2450,32 @@ extern "C" int pemap_dev_run_stats (pemap_dev * d, uint64_t * s, float *t)
       s[7] = c.n_ins;
       s[8] = c.n_wins;
       s[9] = c.n_redo;
-      s[10] = d->last_big;
-      s[11] = (uint64_t) d->run_chunks;
+      s[10] = d->run.last_big;
+      s[11] = (uint64_t) d->run.chunks;
       s[12] = ((uint64_t) c.n_tasks_s - c.n_tasks_dp - c.n_band[0]) + ((uint64_t) c.n_tasks_m - c.n_tasks_mdp - c.n_band[1]);
       s[13] = (uint64_t) c.n_band[0] + c.n_band[1];
       s[14] = c.cells_band;
-      s[15] = d->last_big2;
+      s[15] = d->run.last_big2;
       s[16] = c.n_walks;
       s[17] = (uint64_t) c.n_gate[0] + c.n_gate[1];
     }
   if (t)
-    memcpy (t, d->last_ms, sizeof (d->last_ms));
+    memcpy (t, d->run.last_ms, sizeof (d->run.last_ms));
   return 0;
+}
+
+extern "C" int pemap_dev_seed_launch (pemap_dev * d, int *asked, int *resident, int *launched, int *lds_bytes)
+{
+  *asked = d->run.seed_launch[0];
+  *resident = d->run.seed_launch[1];
+  *launched = d->run.seed_launch[2];
+  *lds_bytes = d->run.seed_launch[3];
+  return 0;
+}
+
+extern "C" int pemap_dev_sw_grid (pemap_dev * d)
+{
+  return d->wk.sw_grid;
 }
 
 // The hit records of the last run's first chunk (set 0): meaningful for a run of one chunk only.
@@ -2408,9 +2484,9 @@ extern "C" int pemap_dev_debug_hits (pemap_dev * d, int *n_hits, uint32_t * spot
 {
   HIPCHK (d, hipSetDevice (d->device));
   HIPCHK (d, hipStreamSynchronize (d->stream));
-  const int n_ends = d->paired ? 2 * d->run_n : d->run_n;
+  const int n_ends = d->paired ? 2 * d->run.n : d->run.n;
   const size_t nh = (size_t) n_ends * PM_MAX_HITS;
-  const PmHits & H = d->set[0].hits;
+  const PmHits & H = d->wk.set[0].hits;
   if (n_hits)
     HIPCHK (d, hipMemcpy (n_hits, H.n_hits, (size_t) n_ends * sizeof (int), hipMemcpyDeviceToHost));
   if (spot)
@@ -2421,51 +2497,40 @@ extern "C" int pemap_dev_debug_hits (pemap_dev * d, int *n_hits, uint32_t * spot
     HIPCHK (d, hipMemcpy (win_start, H.gpos, nh * 4, hipMemcpyDeviceToHost));
   if (score)
     HIPCHK (d, hipMemcpy (score, H.score, nh * 8, hipMemcpyDeviceToHost));
-  if (win_len || start_i)
-    {
-      std::vector < int16_t > t (nh);
-      if (win_len)
-        {
-          HIPCHK (d, hipMemcpy (t.data (), H.nn, nh * 2, hipMemcpyDeviceToHost));
-          for (size_t i = 0; i < nh; i++)
-            win_len[i] = t[i];
-        }
-      if (start_i)
-        {
-          HIPCHK (d, hipMemcpy (t.data (), H.sti, nh * 2, hipMemcpyDeviceToHost));
-          for (size_t i = 0; i < nh; i++)
-            start_i[i] = t[i];
-        }
-    }
-  if (start_k)
-    {
-      std::vector < uint8_t > t (nh);
-      HIPCHK (d, hipMemcpy (t.data (), H.stk, nh, hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < nh; i++)
-        start_k[i] = t[i] & 3;  // (bit 2 = decided by the gapless rule)
-    }
-  return 0;
+  // the narrow arrays widened to the caller's ints
+  auto widened = [&] (int *out, const auto * dev, int mask) -> int
+  {
+    std::vector < std::decay_t < decltype (*dev) > > t (out ? nh : 0);
+    if (out)
+      HIPCHK (d, hipMemcpy (t.data (), dev, nh * sizeof (t[0]), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < t.size (); i++)
+      out[i] = t[i] & mask;
+    return 0;
+  };
+  TRY (widened (win_len, H.nn, -1));
+  TRY (widened (start_i, H.sti, -1));
+  return widened (start_k, H.stk, 3);   // (bit 2 = decided by the gapless rule)
 }
 
 // ------------------------------------------------------------------------------------------------------------
 extern "C" int pemap_dev_reset_pileup (pemap_dev * d)
 {
   HIPCHK (d, hipSetDevice (d->device));
-  if (!d->d_counts)
+  if (!d->pile.d_counts)
     return fail (d, "reset_pileup: no index");
   // (a batch delivered after the reset would be folded into the new totals: the rule of pemap_dev_absorb)
   if (ring_busy (d))
     return fail (d, "reset_pileup: the object has a submitted batch that was not waited for");
   HIPCHK (d, hipStreamSynchronize (d->stream));
-  TRY (zero_on_stream (d, d->d_counts, 6 * d->pile_plane_words * sizeof (uint32_t)));
+  TRY (zero_on_stream (d, d->pile.d_counts, 6 * d->pile.plane_words * sizeof (uint32_t)));
   {
     // a plane of zeros is one in both forms: no conversion, whichever form it had
     std::lock_guard < std::mutex > lk (d->mu);
-    d->pile_diff = false;
+    d->pile.diff = false;
   }
-  TRY (zero_on_stream (d, d->d_cur, sizeof (PmInsCursor)));
-  d->h_ins.clear ();
-  memset (d->summary, 0, sizeof (d->summary));
+  TRY (zero_on_stream (d, d->pile.d_cur, sizeof (PmInsCursor)));
+  d->pile.h_ins.clear ();
+  memset (d->pile.summary, 0, sizeof (d->pile.summary));
   return 0;
 }
 
@@ -2476,9 +2541,9 @@ extern "C" int pemap_dev_index_share (pemap_dev * dst, pemap_dev * src)
 {
   if (!dst || !src || dst == src)
     return fail (dst, "index_share: the source and the destination are the same object");
-  if (!src->index_ready)
+  if (!src->ix.ready)
     return fail (dst, "index_share: the source object has no committed index");
-  TRY (pemap_dev_index_alloc (dst, src->n_mers, src->gsize, src->n_contigs, src->idepth));
+  TRY (pemap_dev_index_alloc (dst, src->ix.n_mers, src->ix.gsize, src->ix.n_contigs, src->ix.idepth));
   const size_t piece = (size_t) 1 << 30;
   for (int which = 0; which < 4; which++)
     {
@@ -2495,15 +2560,6 @@ extern "C" int pemap_dev_index_share (pemap_dev * dst, pemap_dev * src)
   return pemap_dev_index_commit (dst);
 }
 
-static bool ring_busy (pemap_dev * d)
-{
-  std::lock_guard < std::mutex > lk (d->mu);
-  for (int i = 0; i < PM_RING; i++)
-    if (d->ring[i].active)
-      return true;
-  return false;
-}
-
 // the staged way's temporaries (on dst's device), released on every return
 struct PmAbsorbStage
 {
@@ -2512,14 +2568,9 @@ struct PmAbsorbStage
   hipEvent_t ev_copied[2] = {}, ev_added[2] = {};
   ~PmAbsorbStage ()
   {
-    for (int b = 0; b < 2; b++)
-      {
-        hipFree (buf[b]);
-        if (ev_copied[b])
-          hipEventDestroy (ev_copied[b]);
-        if (ev_added[b])
-          hipEventDestroy (ev_added[b]);
-      }
+    pm_free (buf[0], buf[1]);
+    for (hipEvent_t * e : { &ev_copied[0], &ev_copied[1], &ev_added[0], &ev_added[1] })
+      pm_event_free (*e);
     if (copy)
       hipStreamDestroy (copy);
   }
@@ -2539,11 +2590,11 @@ extern "C" int pemap_dev_absorb (pemap_dev * dst, pemap_dev * src)
 {
   if (!dst || !src || dst == src)
     return fail (dst, "absorb: the source and the destination are the same object");
-  if (!dst->index_ready || !src->index_ready)
-    return fail (dst, "absorb: %s object has no index", dst->index_ready ? "the source" : "the destination");
-  if (dst->gsize != src->gsize || dst->n_contigs != src->n_contigs || dst->pile_plane_words != src->pile_plane_words)
-    return fail (dst, "absorb: the objects hold different genomes (%llu letters in %d contigs against %llu in %d)", (unsigned long long) dst->gsize,
-                 dst->n_contigs, (unsigned long long) src->gsize, src->n_contigs);
+  if (!dst->ix.ready || !src->ix.ready)
+    return fail (dst, "absorb: %s object has no index", dst->ix.ready ? "the source" : "the destination");
+  if (dst->ix.gsize != src->ix.gsize || dst->ix.n_contigs != src->ix.n_contigs || dst->pile.plane_words != src->pile.plane_words)
+    return fail (dst, "absorb: the objects hold different genomes (%llu letters in %d contigs against %llu in %d)", (unsigned long long) dst->ix.gsize,
+                 dst->ix.n_contigs, (unsigned long long) src->ix.gsize, src->ix.n_contigs);
   if (ring_busy (dst) || ring_busy (src))
     return fail (dst, "absorb: %s object has a submitted batch that was not waited for", ring_busy (dst) ? "the destination" : "the source");
   if (pemap_dev_sync (src) || (hipSetDevice (src->device) != hipSuccess) || drain_ins (src))
@@ -2553,12 +2604,12 @@ extern "C" int pemap_dev_absorb (pemap_dev * dst, pemap_dev * src)
   TRY (pemap_dev_sync (dst));   // (leaves dst's device current)
   TRY (pile_fold (dst));
   // ---- counters: every 16-bit counter of the planes becomes (dst + src) mod 2^16, padding included
-  const size_t bytes = 6 * dst->pile_plane_words * sizeof (uint32_t);
+  const size_t bytes = 6 * dst->pile.plane_words * sizeof (uint32_t);
   // (a plane is a whole number of 256-byte blocks, index_alloc: whole 16-byte vectors, no tail)
-  if (dst->pile_plane_words % 64 != 0)
-    return fail (dst, "internal: a pileup plane of %zu words is not a whole number of 256-byte blocks", dst->pile_plane_words);
+  if (dst->pile.plane_words % 64 != 0)
+    return fail (dst, "internal: a pileup plane of %zu words is not a whole number of 256-byte blocks", dst->pile.plane_words);
   if (dst->device == src->device && !dst->kn.absorb_staged)
-    launch_pile_add (dst, dst->d_counts, src->d_counts, bytes);
+    launch_pile_add (dst, dst->pile.d_counts, src->pile.d_counts, bytes);
   else
     {
       // two staging buffers on dst's device: the copy of piece k + 1 runs under the add of piece k
@@ -2578,10 +2629,10 @@ extern "C" int pemap_dev_absorb (pemap_dev * dst, pemap_dev * src)
           const size_t m = bytes - o < chunk ? bytes - o : chunk;
           if (k >= 2)
             HIPCHK (dst, hipStreamWaitEvent (S.copy, S.ev_added[b], 0));        // the add of piece k - 2 has read the buffer
-          HIPCHK (dst, hipMemcpyPeerAsync (S.buf[b], dst->device, (const char *) src->d_counts + o, src->device, m, S.copy));
+          HIPCHK (dst, hipMemcpyPeerAsync (S.buf[b], dst->device, (const char *) src->pile.d_counts + o, src->device, m, S.copy));
           HIPCHK (dst, hipEventRecord (S.ev_copied[b], S.copy));
           HIPCHK (dst, hipStreamWaitEvent (dst->stream, S.ev_copied[b], 0));
-          launch_pile_add (dst, dst->d_counts + o / sizeof (uint32_t), S.buf[b], m);
+          launch_pile_add (dst, dst->pile.d_counts + o / sizeof (uint32_t), S.buf[b], m);
           HIPCHK (dst, hipEventRecord (S.ev_added[b], dst->stream));
         }
       HIPCHK (dst, hipStreamSynchronize (S.copy));
@@ -2590,9 +2641,9 @@ extern "C" int pemap_dev_absorb (pemap_dev * dst, pemap_dev * src)
   HIPCHK (dst, hipStreamSynchronize (dst->stream));
   HIPCHK (dst, hipGetLastError ());
   // ---- insertion log (drained above) and summary
-  dst->h_ins.insert (dst->h_ins.end (), src->h_ins.begin (), src->h_ins.end ());
+  dst->pile.h_ins.insert (dst->pile.h_ins.end (), src->pile.h_ins.begin (), src->pile.h_ins.end ());
   for (int i = 0; i < 13; i++)
-    dst->summary[i] += src->summary[i];
+    dst->pile.summary[i] += src->pile.summary[i];
   if (pemap_dev_reset_pileup (src))
     return fail (dst, "absorb: the source object: %.400s", src->err);
   return 0;
@@ -2601,7 +2652,7 @@ extern "C" int pemap_dev_absorb (pemap_dev * dst, pemap_dev * src)
 extern "C" int pemap_dev_fetch_pileup (pemap_dev * d, uint16_t * counts, pemap_ins_cb cb, void *user)
 {
   HIPCHK (d, hipSetDevice (d->device));
-  if (!d->d_counts)
+  if (!d->pile.d_counts)
     return fail (d, "fetch_pileup: no index");
   TRY (pemap_dev_sync (d));
   TRY (pile_fold (d));
@@ -2610,10 +2661,10 @@ extern "C" int pemap_dev_fetch_pileup (pemap_dev * d, uint16_t * counts, pemap_i
     {
       const uint64_t chunk = 48ull << 20;       // positions per round (6 counters each)
       DevTmp < uint16_t > d_tmp;
-      TRY (dev_alloc (d, &d_tmp.p, (size_t) (d->gsize < chunk ? d->gsize : chunk) * 6));
-      for (uint64_t o = 0; o < d->gsize; o += chunk)
+      TRY (dev_alloc (d, &d_tmp.p, (size_t) (d->ix.gsize < chunk ? d->ix.gsize : chunk) * 6));
+      for (uint64_t o = 0; o < d->ix.gsize; o += chunk)
         {
-          const uint64_t m = d->gsize - o < chunk ? d->gsize - o : chunk;
+          const uint64_t m = d->ix.gsize - o < chunk ? d->ix.gsize - o : chunk;
           hipLaunchKernelGGL (pile_to_u16_kernel, dim3 ((unsigned) ((m * 6 + 255) / 256)), dim3 (256), 0, d->stream, pile_of (d), o, m, d_tmp);
           HIPCHK (d, hipStreamSynchronize (d->stream));
           HIPCHK (d, hipMemcpy (counts + o * 6, d_tmp, m * 6 * sizeof (uint16_t), hipMemcpyDeviceToHost));
@@ -2622,7 +2673,7 @@ extern "C" int pemap_dev_fetch_pileup (pemap_dev * d, uint16_t * counts, pemap_i
   if (cb)
     {
       size_t at = 0;
-      const std::vector < uint8_t > &L = d->h_ins;
+      const std::vector < uint8_t > &L = d->pile.h_ins;
       char buf[512];
       while (at + 8 <= L.size ())
         {
@@ -2644,9 +2695,9 @@ extern "C" int pemap_dev_fetch_records (pemap_dev * d, uint64_t first, uint64_t 
                                         uint64_t * n_records)
 {
   HIPCHK (d, hipSetDevice (d->device));
-  if (!d->d_counts)
+  if (!d->pile.d_counts)
     return fail (d, "fetch_records: no index");
-  if (first + count > d->gsize)
+  if (first + count > d->ix.gsize)
     return fail (d, "fetch_records: range beyond the genome");
   if (count == 0)
     {
@@ -2735,7 +2786,28 @@ extern "C" int pemap_dev_free (pemap_dev * d, void *d_ptr)
 }
 
 static int synth_reads (pemap_dev * d, uint64_t seed, int n, int read_len, int paired, double sub_rate, double indel_rate, double one_indel_frac,
-                        uint64_t first_read);
+                        uint64_t first_read)
+{
+  HIPCHK (d, hipSetDevice (d->device));
+  if (!d->ix.ready)
+    return fail (d, "synth_reads: needs the resident genome");
+  if (read_len < PEMAP_MIN_READ || read_len > PEMAP_MAX_READ || n <= 0)
+    return fail (d, "synth_reads: bad n/read_len");
+  if (d->ix.gsize < 2000)
+    return fail (d, "synth_reads: genome too small");
+  int stride = (read_len + 15) & ~15;
+  TRY (ring_leave (d, n, stride, paired));
+  d->paired = paired ? 1 : 0;   // (behind the deliveries of ring_leave, which read the old value)
+  int ends = paired ? 2 * n : n;
+  hipLaunchKernelGGL (sy_reads_kernel, dim3 ((ends + 255) / 256), dim3 (256), 0, d->stream, seed, d->ix.d_genome, d->ix.gsize, n, read_len, paired,
+                      (unsigned) (sub_rate * 16777216.0), (unsigned) (indel_rate * 16777216.0), first_read, d->rd.d_rows[0], d->rd.d_len[0],
+                      d->rd.d_rows[1], d->rd.d_len[1], stride, (unsigned) (one_indel_frac * 16777216.0));
+  HIPCHK (d, hipStreamSynchronize (d->stream));
+  d->rd.h_len[0].assign (n, read_len);
+  d->rd.h_len[1].assign (paired ? n : 0, read_len);
+  reads_staged (d, n, paired, read_len, read_len);
+  return 0;
+}
 
 extern "C" int pemap_dev_synth_reads (pemap_dev * d, uint64_t seed, int n, int read_len, int paired, double sub_rate,
                                       double indel_rate, uint64_t first_read)
@@ -2749,60 +2821,29 @@ extern "C" int pemap_dev_synth_reads_indel (pemap_dev * d, uint64_t seed, int n,
   return synth_reads (d, seed, n, read_len, paired, sub_rate, 0.0, indel_read_frac, first_read);
 }
 
-static int synth_reads (pemap_dev * d, uint64_t seed, int n, int read_len, int paired, double sub_rate, double indel_rate, double one_indel_frac,
-                        uint64_t first_read)
-{
-  HIPCHK (d, hipSetDevice (d->device));
-  if (!d->index_ready)
-    return fail (d, "synth_reads: needs the resident genome");
-  if (read_len < PEMAP_MIN_READ || read_len > PEMAP_MAX_READ || n <= 0)
-    return fail (d, "synth_reads: bad n/read_len");
-  if (d->gsize < 2000)
-    return fail (d, "synth_reads: genome too small");
-  int stride = (read_len + 15) & ~15;
-  TRY (ring_leave (d));
-  TRY (pemap_dev_sync (d));
-  d->paired = paired ? 1 : 0;
-  TRY (ensure_reads (d, n, stride, paired));
-  int ends = paired ? 2 * n : n;
-  hipLaunchKernelGGL (sy_reads_kernel, dim3 ((ends + 255) / 256), dim3 (256), 0, d->stream, seed, d->d_genome, d->gsize, n, read_len, paired,
-                      (unsigned) (sub_rate * 16777216.0), (unsigned) (indel_rate * 16777216.0), first_read, d->d_reads1, d->d_len1,
-                      d->d_reads2, d->d_len2, stride, (unsigned) (one_indel_frac * 16777216.0));
-  HIPCHK (d, hipStreamSynchronize (d->stream));
-  d->h_len1.assign (n, read_len);
-  if (paired)
-    d->h_len2.assign (n, read_len);
-  else
-    d->h_len2.clear ();
-  d->n_staged = n;
-  d->staged_paired = paired ? 1 : 0;
-  d->max_len_staged = d->min_len_staged = read_len;
-  return 0;
-}
-
 extern "C" int pemap_dev_staged_reads (pemap_dev * d, char *reads1, int *len1, char *reads2, int *len2, int stride)
 {
   HIPCHK (d, hipSetDevice (d->device));
-  if (d->n_staged <= 0)
+  if (d->rd.n <= 0)
     return fail (d, "staged_reads: nothing staged");
-  if (stride != d->stride)
-    return fail (d, "staged_reads: the staged row stride is %d", d->stride);
+  if (stride != d->rd.stride)
+    return fail (d, "staged_reads: the staged row stride is %d", d->rd.stride);
   HIPCHK (d, hipStreamSynchronize (d->stream));
-  HIPCHK (d, hipMemcpy (reads1, d->d_reads1, (size_t) d->n_staged * stride, hipMemcpyDeviceToHost));
-  HIPCHK (d, hipMemcpy (len1, d->d_len1, (size_t) d->n_staged * 4, hipMemcpyDeviceToHost));
-  if (d->staged_paired && reads2)
+  char *const rows[2] = { reads1, reads2 };
+  int *const lens[2] = { len1, len2 };
+  for (int m = 0; m < (d->rd.paired && reads2 ? 2 : 1); m++)
     {
-      HIPCHK (d, hipMemcpy (reads2, d->d_reads2, (size_t) d->n_staged * stride, hipMemcpyDeviceToHost));
-      HIPCHK (d, hipMemcpy (len2, d->d_len2, (size_t) d->n_staged * 4, hipMemcpyDeviceToHost));
+      HIPCHK (d, hipMemcpy (rows[m], d->rd.d_rows[m], (size_t) d->rd.n * stride, hipMemcpyDeviceToHost));
+      HIPCHK (d, hipMemcpy (lens[m], d->rd.d_len[m], (size_t) d->rd.n * 4, hipMemcpyDeviceToHost));
     }
   return 0;
 }
 
 extern "C" int pemap_dev_staged_info (pemap_dev * d, int *n, int *stride, int *paired)
 {
-  *n = d->n_staged;
-  *stride = d->stride;
-  *paired = d->staged_paired;
+  *n = d->rd.n;
+  *stride = d->rd.stride;
+  *paired = d->rd.paired;
   return 0;
 }
 
@@ -2819,30 +2860,17 @@ struct PmFastqArgs
   int trim_start, trim_end, max_records, stride;
 };
 
-static void fq_free (PmFastq & F)
+// the arrays of the parse that share `cap` hold `need` elements each at least (their contents are not kept); cap is set behind the last
+template < class ... T > static int fq_grow (pemap_dev * d, size_t & cap, size_t need, T * &... p)
 {
-  for (PmFastqMate & M : F.mate)
-    {
-      for (void *p : { (void *) M.d_text, (void *) M.d_tile_cnt, (void *) M.d_line_start, (void *) M.d_sums, (void *) M.d_tile_in, (void *) M.d_rec_off,
-                       (void *) M.d_rec_next, (void *) M.d_rec_len })
-        hipFree (p);
-      M = PmFastqMate ();
-    }
-  hipFree (F.d_ctl);
-  if (F.h)
-    hipHostFree (F.h);
-  F.d_ctl = nullptr;
-  F.h = nullptr;
-}
-
-// an array of the parse that holds `need` elements at least (its contents are not kept)
-template < class T > static int fq_grow (pemap_dev * d, T * &p, size_t have, size_t need)
-{
-  if (p && have >= need)
+  if (cap >= need && (... && p))
     return 0;
-  hipFree (p);
-  p = nullptr;
-  return dev_alloc (d, &p, need);
+  pm_free (p...);
+  cap = 0;
+  int rc = 0;
+  ((rc = rc ? rc : dev_alloc (d, &p, need)), ...);
+  cap = rc ? 0 : need;
+  return rc;
 }
 
 static int fq_check_args (pemap_dev * d, const char *who, const PmFastqArgs & a, const pemap_fastq_result * res)
@@ -2887,12 +2915,10 @@ static int fq_parse (pemap_dev * d, hipStream_t st, const PmFastqArgs & a, pemap
       if (!bytes)
         continue;
       const size_t padded = (((size_t) bytes + 15) & ~(size_t) 15) + 16;        // every 16-byte load that begins inside the text stays inside
-      TRY (fq_grow (d, M.d_text, M.text_cap, padded));
-      M.text_cap = M.text_cap > padded ? M.text_cap : padded;
+      TRY (fq_grow (d, M.text_cap, padded, M.d_text));
       HIPCHK (d, hipMemcpyAsync (M.d_text, a.text[m], bytes, hipMemcpyHostToDevice, st));
       const unsigned nt = (bytes + PFQ_TILE - 1) / PFQ_TILE;
-      TRY (fq_grow (d, M.d_tile_cnt, M.tile_cap, nt));
-      M.tile_cap = M.tile_cap > nt ? M.tile_cap : nt;
+      TRY (fq_grow (d, M.tile_cap, nt, M.d_tile_cnt));
       hipLaunchKernelGGL (pfq_nl_count_kernel, dim3 (nt), dim3 (PFQ_BLOCK), 0, st, (const uint4 *) M.d_text, bytes, M.d_tile_cnt);
       hipLaunchKernelGGL (pfq_sum_top_kernel, dim3 (1), dim3 (PFQ_TOP), 0, st, M.d_tile_cnt, nt, &F.d_ctl[m].n_lines);
     }
@@ -2912,15 +2938,9 @@ static int fq_parse (pemap_dev * d, hipStream_t st, const PmFastqArgs & a, pemap
       // (a text has no more records than lines: an array of that many serves whatever max_records is)
       const unsigned lim = rec_limit[m] = nl < (unsigned) a.max_records ? nl : (unsigned) a.max_records;
       const unsigned nt = (bytes + PFQ_TILE - 1) / PFQ_TILE, nlt = (nl + PFQ_LINE_TILE - 1) / PFQ_LINE_TILE;
-      TRY (fq_grow (d, M.d_line_start, M.line_cap, (size_t) nl + 1));
-      M.line_cap = M.line_cap > (size_t) nl + 1 ? M.line_cap : (size_t) nl + 1;
-      TRY (fq_grow (d, M.d_sums, M.ltile_cap, nlt));
-      TRY (fq_grow (d, M.d_tile_in, M.ltile_cap, nlt));
-      M.ltile_cap = M.ltile_cap > nlt ? M.ltile_cap : nlt;
-      TRY (fq_grow (d, M.d_rec_off, M.rec_cap, lim));
-      TRY (fq_grow (d, M.d_rec_next, M.rec_cap, lim));
-      TRY (fq_grow (d, M.d_rec_len, M.rec_cap, lim));
-      M.rec_cap = M.rec_cap > lim ? M.rec_cap : lim;
+      TRY (fq_grow (d, M.line_cap, (size_t) nl + 1, M.d_line_start));
+      TRY (fq_grow (d, M.ltile_cap, nlt, M.d_sums, M.d_tile_in));
+      TRY (fq_grow (d, M.rec_cap, lim, M.d_rec_off, M.d_rec_next, M.d_rec_len));
       hipLaunchKernelGGL (pfq_nl_apply_kernel, dim3 (nt), dim3 (PFQ_BLOCK), 0, st, (const uint4 *) M.d_text, bytes, (const unsigned *) M.d_tile_cnt, nl, M.d_line_start);
       hipLaunchKernelGGL (pfq_role_sum_kernel, dim3 (nlt), dim3 (PFQ_BLOCK), 0, st, (const uint8_t *) M.d_text, bytes, (const unsigned *) M.d_line_start, nl, M.d_sums);
       hipLaunchKernelGGL (pfq_role_top_kernel, dim3 (1), dim3 (PFQ_TOP), 0, st, (const PfqTileSum *) M.d_sums, nlt, a.state[m], M.d_tile_in, &F.d_ctl[m]);
@@ -2990,19 +3010,13 @@ extern "C" int pemap_dev_stage_fastq (pemap_dev * d, const char *text1, uint64_t
   const int n = res->n;
   if (n == 0)
     return 0;
-  TRY (ring_leave (d));
-  TRY (pemap_dev_sync (d));
-  TRY (ensure_reads (d, n, stride, d->paired));
-  d->h_len1.assign ((size_t) n, 0);
-  d->h_len2.assign (d->paired ? (size_t) n : 0, 0);
-  uint8_t *const rows[2] = { d->d_reads1, d->d_reads2 };
-  int *const lens[2] = { d->d_len1, d->d_len2 }, *const h_len[2] = { d->h_len1.data (), d->h_len2.data () };
+  TRY (ring_leave (d, n, stride, d->paired));
+  d->rd.h_len[0].assign ((size_t) n, 0);
+  d->rd.h_len[1].assign (d->paired ? (size_t) n : 0, 0);
+  int *const h_len[2] = { d->rd.h_len[0].data (), d->rd.h_len[1].data () };
   int mx = 0, mn = 1 << 30;
-  TRY (fq_rows (d, d->stream, a, n, rows, lens, h_len, &mx, &mn, res));
-  d->n_staged = n;
-  d->staged_paired = d->paired;
-  d->max_len_staged = mx;
-  d->min_len_staged = mn;
+  TRY (fq_rows (d, d->stream, a, n, d->rd.d_rows, d->rd.d_len, h_len, &mx, &mn, res));
+  reads_staged (d, n, d->paired, mx, mn);
   return 0;
 }
 
@@ -3013,47 +3027,30 @@ extern "C" int pemap_dev_submit_fastq (pemap_dev * d, const char *text1, uint64_
   std::unique_lock < std::mutex > sub (d->submit_mu);
   std::unique_lock < std::mutex > lk (d->mu);
   HIPCHK (d, hipSetDevice (d->device));
-  if (!d->index_ready)
+  if (!d->ix.ready)
     return fail (d, "submit_fastq: no index loaded");
   const PmFastqArgs a = { { text1, text2 }, { bytes1, bytes2 }, { state1, state2 }, trim_start, trim_end, max_records, stride };
   TRY (fq_check_args (d, "submit_fastq", a, res));
   if (!m1 || !mapping_type || !ticket || (d->paired && !m2))
     return fail (d, "submit_fastq: a required pointer is NULL");
-  if (!d->stream_h2d)
-    HIPCHK (d, hipStreamCreateWithFlags (&d->stream_h2d, hipStreamNonBlocking));
+  if (!d->rg.stream_h2d)
+    HIPCHK (d, hipStreamCreateWithFlags (&d->rg.stream_h2d, hipStreamNonBlocking));
   // text and parse kernels on the copy stream: the batches in flight keep the pipeline's streams busy meanwhile
-  TRY (fq_parse (d, d->stream_h2d, a, res));
+  TRY (fq_parse (d, d->rg.stream_h2d, a, res));
   const int n = res->n;
   if (n == 0)
     return 0;
-  TRY (ring_setup (d, n, stride, lk));
-  const int slot = (int) (d->ring_seq % PM_RING);
-  PmRingSlot & r = d->ring[slot];
-  TRY (ring_finish (d, slot, lk));
-  const int first = slot * d->ring_cap;
-  uint8_t *const rows[2] = { d->d_reads1 + (size_t) first * stride, d->paired ? d->d_reads2 + (size_t) first * stride : nullptr };
-  int *const lens[2] = { d->d_len1 + first, d->paired ? d->d_len2 + first : nullptr }, *const h_len[2] = { r.h_len, r.h_len + d->ring_cap };
+  PmSlotTake t;
+  TRY (ring_take (d, n, stride, lk, t));
+  PmRingSlot & r = *t.r;
   int mx = 0, mn = 1 << 30;
-  TRY (fq_rows (d, d->stream_h2d, a, n, rows, lens, h_len, &mx, &mn, res));
-  if (mx > d->max_len_staged)
-    d->max_len_staged = mx;
-  if (mn < d->min_len_staged)
-    d->min_len_staged = mn;
-  memcpy (&d->h_len1[first], r.h_len, (size_t) n * sizeof (int));
-  if (d->paired)
-    memcpy (&d->h_len2[first], r.h_len + d->ring_cap, (size_t) n * sizeof (int));
-  if (!d->stream2)
-    TRY (ensure_pipeline (d, 0));
+  TRY (fq_rows (d, d->rg.stream_h2d, a, n, t.rows, t.lens, t.h_len, &mx, &mn, res));
+  for (int m = 0; m < (d->paired ? 2 : 1); m++)
+    memcpy (&d->rd.h_len[m][t.first], t.h_len[m], (size_t) n * sizeof (int));
   // the rows are on the device already: every slice's event is the same point of the copy stream
-  const int slice = chunk_pairs_for (d, n, d->max_len_staged);
-  const int n_slices = (n + slice - 1) / slice;
-  while ((int) r.ev_copy.size () < n_slices)
-    {
-      hipEvent_t e;
-      HIPCHK (d, hipEventCreateWithFlags (&e, hipEventDisableTiming));
-      r.ev_copy.push_back (e);
-    }
-  for (int k = 0; k < n_slices; k++)
-    HIPCHK (d, hipEventRecord (r.ev_copy[k], d->stream_h2d));
-  return ring_queue_run (d, r, first, n, m1, m2, mapping_type, ticket);
+  int slice;
+  TRY (ring_slices (d, r, n, mx, mn, &slice));
+  for (int k = 0; k * slice < n; k++)
+    HIPCHK (d, hipEventRecord (r.ev_copy[k], d->rg.stream_h2d));
+  return ring_queue_run (d, r, t.first, n, m1, m2, mapping_type, ticket);
 }

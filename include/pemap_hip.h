@@ -117,7 +117,7 @@ int pemap_dev_seed_launch (pemap_dev * dev, int *asked, int *resident, int *laun
  * For collectives (broadcast of 0..3 at start-up, sum of 4 at the end) and for copying the index back to the host.
  * Buffer 4 while the object maps: its first plane then holds differences of neighbouring counters, not counts (two atomics per
  * run of matched bases instead of one per word), and is turned back into counts -- a scan over the plane, waited for -- by
- * pemap_dev_buffer (which = 4) and pemap_dev_read_buffer through it, pemap_dev_fetch_pileup, pemap_dev_fetch_records,
+ * pemap_dev_buffer (which = 4) and pemap_dev_read_buffer through it, pemap_dev_fetch_pileup, pemap_dev_fetch_records (and _gz),
  * pemap_dev_absorb (both objects) and pemap_dev_map_batch before it returns; NOT by pemap_dev_run, pemap_dev_run_slice,
  * pemap_dev_sync, pemap_dev_submit_batch or pemap_dev_wait_batch.  So the view of buffer 4 holds counts when it is obtained, and
  * again after every pemap_dev_map_batch; a view kept across asynchronous runs (run / run_slice / submit_batch) must be obtained
@@ -235,6 +235,20 @@ int pemap_dev_fetch_pileup (pemap_dev * dev, uint16_t * counts, pemap_ins_cb cb,
  * returns the number of records through n_records (out may be NULL to count only). */
 int pemap_dev_fetch_records (pemap_dev * dev, uint64_t first, uint64_t count, void *out, uint64_t out_capacity,
                              uint64_t * n_records);
+/* pemap_dev_fetch_records with the records deflated on the device: the records of [first, first + count) are cut into pieces of 512
+ * and every piece becomes one BGZF member (a complete gzip member of under 65,536 bytes whose head says how long it is; the rule is
+ * pecaller_amd/csrc/pemap_gz_rule.h, tests/csrc/pemap_gz_rule_check.c states it serially).  gz_out receives the members back to back,
+ * *gz_bytes their length: they inflate to exactly the bytes pemap_dev_fetch_records returns for the range.  A file made of the
+ * members of consecutive ranges and the 28-byte empty member (pmz_eof_byte) is a BGZF file.  ins_records (may be NULL) receives the
+ * 16-byte records whose insertion count is not 0, ascending, *n_ins their number.  The range is checked and plane 0 folded as by
+ * pemap_dev_fetch_records.  With gz_out == NULL the call returns the three sizes only.  A gz_capacity (bytes) or an ins_capacity
+ * (records) that is too small fails with a message that names what is needed, and nothing is written to either buffer.  The members
+ * are copied straight into gz_out where the caller pinned it (pemap_dev_pin_host), else through page-locked blocks of the object. */
+int pemap_dev_fetch_records_gz (pemap_dev * dev, uint64_t first, uint64_t count, void *gz_out, uint64_t gz_capacity, uint64_t * gz_bytes,
+                                uint64_t * n_records, void *ins_records, uint64_t ins_capacity, uint64_t * n_ins);
+/* kernel milliseconds of the last pemap_dev_fetch_records_gz: the records (count, scan, emit), the insertion list, the deflate, the scan
+ * over the members' lengths and the pack */
+int pemap_dev_fetch_gz_ms (pemap_dev * dev, float *ms4);
 /* Counters, insertion log and summary start over.  Fails, changing nothing, while a submitted batch was not waited for. */
 int pemap_dev_reset_pileup (pemap_dev * dev);
 /* The end of a run on several objects: afterwards dst is what it would be had it mapped src's batches as well, and src is as

@@ -17,6 +17,7 @@
 #include "pemap_kernels.hip.h"
 #include "pemap_aux.hip.h"
 #include "pemap_fastq.hip.h"
+#include "pemap_gz.hip.h"
 #include <rocprim/rocprim.hpp>
 
 static char g_create_err[512] = "";
@@ -458,6 +459,15 @@ static void ring_free (PmRing & g, bool blocks_only)
   g.cap = 0;
 }
 
+// The deflated records' way out (pemap_dev_fetch_records_gz): the kernel times of the last call, and the two page-locked blocks the
+// members pass through where the caller's buffer is not pinned (made at the first such call, released by pemap_dev_destroy).
+#define PM_GZ_BLOCK ((size_t) 8 << 20)
+struct PmGzOut
+{
+  float ms[4] = {};
+  char *h_block[2] = {};
+};
+
 struct pemap_dev
 {
   int device = 0, n_cus = 0;
@@ -480,6 +490,7 @@ struct pemap_dev
   std::mutex submit_mu;
   PmRing rg;
   PmFastq fq;
+  PmGzOut gz;
 };
 
 static inline PmPile pile_of (const pemap_dev * d)
@@ -555,6 +566,7 @@ extern "C" void pemap_dev_destroy (pemap_dev * d)
   run_free (d->run);
   ring_free (d->rg, false);
   fq_free (d->fq);
+  pm_host_free (d->gz.h_block[0], d->gz.h_block[1]);
   for (hipStream_t st : { d->rg.stream_h2d, d->run.stream2, d->stream })
     if (st)
       hipStreamDestroy (st);
@@ -2691,40 +2703,53 @@ extern "C" int pemap_dev_fetch_pileup (pemap_dev * d, uint16_t * counts, pemap_i
   return 0;
 }
 
-extern "C" int pemap_dev_fetch_records (pemap_dev * d, uint64_t first, uint64_t count, void *out, uint64_t out_capacity,
-                                        uint64_t * n_records)
+// What pemap_dev_fetch_records and pemap_dev_fetch_records_gz begin with: the checks of the range, the fold of plane 0, the sites' counts
+// per tile of PR_BLOCK positions and their scan.  `who` names the entry in the messages.  *total = 0 and no arrays for a range of no
+// positions; else d_to holds the tiles' first records.  ev2 (may be NULL): two events, recorded around the two kernels.
+static int pile_count_range (pemap_dev * d, const char *who, uint64_t first, uint64_t count, DevTmp < uint64_t > &d_to, uint64_t * total, hipEvent_t * ev2)
 {
   HIPCHK (d, hipSetDevice (d->device));
+  *total = 0;
   if (!d->pile.d_counts)
-    return fail (d, "fetch_records: no index");
-  if (first + count > d->ix.gsize)
-    return fail (d, "fetch_records: range beyond the genome");
+    return fail (d, "%s: no index", who);
+  if (first + count > d->ix.gsize || first + count < first)
+    return fail (d, "%s: range beyond the genome", who);
   if (count == 0)
-    {
-      *n_records = 0;
-      return 0;
-    }
+    return 0;
   if (count > (1ull << 31))
-    return fail (d, "fetch_records: at most 2^31 sites per call");
+    return fail (d, "%s: at most 2^31 sites per call", who);
   TRY (pile_fold (d));          // (on the ALU stream, behind everything queued, and waited for)
   HIPCHK (d, hipStreamSynchronize (d->stream));
   const uint64_t n_tiles = (count + PR_BLOCK - 1) / PR_BLOCK;
-  DevTmp < uint64_t > d_total, d_to;
+  DevTmp < uint64_t > d_total;
   DevTmp < uint32_t > d_tc;
   TRY (dev_alloc (d, &d_tc.p, n_tiles));
   TRY (dev_alloc (d, &d_to.p, n_tiles));
   TRY (dev_alloc (d, &d_total.p, 1));
+  if (ev2)
+    HIPCHK (d, hipEventRecord (ev2[0], d->stream));
   hipLaunchKernelGGL (pile_count_kernel, dim3 ((unsigned) n_tiles), dim3 (PR_BLOCK), 0, d->stream, pile_of (d), first, count, d_tc);
   hipLaunchKernelGGL (ix_scan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d_tc, d_to, n_tiles, d_total);
-  uint64_t total = 0;
-  HIPCHK (d, hipMemcpyAsync (&total, d_total, 8, hipMemcpyDeviceToHost, d->stream));
+  if (ev2)
+    HIPCHK (d, hipEventRecord (ev2[1], d->stream));
+  HIPCHK (d, hipMemcpyAsync (total, d_total, 8, hipMemcpyDeviceToHost, d->stream));
   HIPCHK (d, hipStreamSynchronize (d->stream));
+  return 0;
+}
+
+extern "C" int pemap_dev_fetch_records (pemap_dev * d, uint64_t first, uint64_t count, void *out, uint64_t out_capacity,
+                                        uint64_t * n_records)
+{
+  DevTmp < uint64_t > d_to;
+  uint64_t total = 0;
+  TRY (pile_count_range (d, "fetch_records", first, count, d_to, &total, nullptr));
   *n_records = total;
   if (!out || !total)
     return 0;
   if (total > out_capacity)
     return fail (d, "fetch_records: %llu records do not fit the caller's %llu", (unsigned long long) total,
                  (unsigned long long) out_capacity);
+  const uint64_t n_tiles = (count + PR_BLOCK - 1) / PR_BLOCK;
   DevTmp < PileRec > d_out;
   TRY (dev_alloc (d, &d_out.p, (size_t) total));
   hipLaunchKernelGGL (pile_emit_kernel, dim3 ((unsigned) n_tiles), dim3 (PR_BLOCK), 0, d->stream, pile_of (d), first, count, d_to,
@@ -2732,6 +2757,150 @@ extern "C" int pemap_dev_fetch_records (pemap_dev * d, uint64_t first, uint64_t 
   if (hipStreamSynchronize (d->stream) != hipSuccess
       || hipMemcpy (out, d_out, total * sizeof (PileRec), hipMemcpyDeviceToHost) != hipSuccess)
     return fail (d, "fetch_records: copy failed");
+  return 0;
+}
+
+// the timing events of one pemap_dev_fetch_records_gz, destroyed on every return
+struct PmGzEvents
+{
+  hipEvent_t e[12] = {};
+  ~PmGzEvents ()
+  {
+    for (hipEvent_t & x : e)
+      pm_event_free (x);
+  }
+};
+
+// device bytes to the caller's buffer: directly where the caller pinned it, else through the object's two page-locked blocks, the
+// copy of block k + 1 under the host's memcpy of block k
+static int gz_to_host (pemap_dev * d, char *out, const char *d_src, size_t bytes)
+{
+  if (pm_host_pin_lookup (out, bytes))
+    {
+      HIPCHK (d, hipMemcpyAsync (out, d_src, bytes, hipMemcpyDeviceToHost, d->stream));
+      HIPCHK (d, hipStreamSynchronize (d->stream));
+      return 0;
+    }
+  for (char *&h : d->gz.h_block)
+    if (!h)
+      HIPCHK (d, hipHostMalloc ((void **) &h, PM_GZ_BLOCK, hipHostMallocDefault));
+  size_t prev_o = 0, prev_m = 0;
+  int k = 0;
+  for (size_t o = 0; o < bytes; o += PM_GZ_BLOCK, k++)
+    {
+      const size_t m = bytes - o < PM_GZ_BLOCK ? bytes - o : PM_GZ_BLOCK;
+      // (block k & 1 was copied out of in the turn before the last: the stream is waited for in every turn)
+      HIPCHK (d, hipMemcpyAsync (d->gz.h_block[k & 1], d_src + o, m, hipMemcpyDeviceToHost, d->stream));
+      if (prev_m)
+        memcpy (out + prev_o, d->gz.h_block[(k & 1) ^ 1], prev_m);
+      HIPCHK (d, hipStreamSynchronize (d->stream));
+      prev_o = o;
+      prev_m = m;
+    }
+  if (prev_m)
+    memcpy (out + prev_o, d->gz.h_block[(k & 1) ^ 1], prev_m);
+  return 0;
+}
+
+// The records of pemap_dev_fetch_records stay on the device: their insertion sites are compacted, the records deflated piece by
+// piece into BGZF members (pemap_gz.hip.h, the rule: pemap_gz_rule.h), the members packed; the packed bytes and the sites come back.
+extern "C" int pemap_dev_fetch_records_gz (pemap_dev * d, uint64_t first, uint64_t count, void *gz_out, uint64_t gz_capacity, uint64_t * gz_bytes,
+                                           uint64_t * n_records, void *ins_records, uint64_t ins_capacity, uint64_t * n_ins)
+{
+  if (!d)
+    return 1;
+  if (!gz_bytes || !n_records || !n_ins)
+    return fail (d, "fetch_records_gz: gz_bytes, n_records and n_ins must not be NULL");
+  HIPCHK (d, hipSetDevice (d->device));         // (before the events are made)
+  *gz_bytes = *n_records = *n_ins = 0;
+  memset (d->gz.ms, 0, sizeof d->gz.ms);
+  PmGzEvents E;
+  for (hipEvent_t & x : E.e)
+    if (hipEventCreate (&x) != hipSuccess)
+      return fail (d, "fetch_records_gz: hipEventCreate failed");
+  int n_ev = 2;                 // (0 and 1: around the count and its scan, pile_count_range)
+  auto stamp = [&] () { return hipEventRecord (E.e[n_ev++], d->stream); };
+  auto between = [&] (int a, int b, float *ms) -> int
+  {
+    float v = 0.f;
+    HIPCHK (d, hipEventElapsedTime (&v, E.e[a], E.e[b]));
+    *ms += v;
+    return 0;
+  };
+  // ---- the records (the kernels of pemap_dev_fetch_records)
+  DevTmp < uint64_t > d_to, d_total;
+  uint64_t total = 0;
+  TRY (pile_count_range (d, "fetch_records_gz", first, count, d_to, &total, E.e));
+  *n_records = total;
+  if (!total)
+    return 0;
+  const uint64_t n_tiles = (count + PR_BLOCK - 1) / PR_BLOCK;
+  TRY (dev_alloc (d, &d_total.p, 3));   // [1] insertion sites, [2] packed bytes
+  const uint64_t n_pieces = pmz_pieces (total), n_itiles = (total + PMZ_BLOCK - 1) / PMZ_BLOCK;
+  const uint64_t slot_bytes = n_pieces * PMZ_SLOT + PMZ_SLOT_SLACK;
+  DevTmp < uint4 > d_rec, d_ins;
+  DevTmp < unsigned char >d_slots, d_gz;
+  DevTmp < uint32_t > d_mlen, d_ic;
+  DevTmp < uint64_t > d_mat, d_io;
+  TRY (dev_alloc (d, &d_rec.p, (size_t) total));
+  TRY (dev_alloc (d, &d_slots.p, (size_t) slot_bytes));
+  TRY (dev_alloc (d, &d_mlen.p, (size_t) n_pieces));
+  TRY (dev_alloc (d, &d_mat.p, (size_t) n_pieces));
+  TRY (dev_alloc (d, &d_ic.p, (size_t) n_itiles));
+  TRY (dev_alloc (d, &d_io.p, (size_t) n_itiles));
+  HIPCHK (d, stamp ());         // 2
+  hipLaunchKernelGGL (pile_emit_kernel, dim3 ((unsigned) n_tiles), dim3 (PR_BLOCK), 0, d->stream, pile_of (d), first, count, d_to, (PileRec *) d_rec.p, total);
+  HIPCHK (d, stamp ());         // 3
+  // ---- the insertion sites' counts, the members, their places
+  hipLaunchKernelGGL (pmz_ins_count_kernel, dim3 ((unsigned) n_itiles), dim3 (PMZ_BLOCK), 0, d->stream, d_rec, total, d_ic);
+  hipLaunchKernelGGL (ix_scan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d_ic, d_io, n_itiles, d_total.p + 1);
+  HIPCHK (d, stamp ());         // 4
+  hipLaunchKernelGGL (pmz_deflate_kernel, dim3 ((unsigned) n_pieces), dim3 (PMZ_BLOCK), 0, d->stream, d_rec, total, d_slots, n_pieces, d_mlen);
+  HIPCHK (d, stamp ());         // 5
+  hipLaunchKernelGGL (ix_scan_tiles_kernel, dim3 (1), dim3 (1024), 0, d->stream, d_mlen, d_mat, n_pieces, d_total.p + 2);
+  HIPCHK (d, stamp ());         // 6
+  uint64_t two[2] = { 0, 0 };
+  HIPCHK (d, hipMemcpyAsync (two, d_total.p + 1, 16, hipMemcpyDeviceToHost, d->stream));
+  HIPCHK (d, hipStreamSynchronize (d->stream));
+  HIPCHK (d, hipGetLastError ());
+  const uint64_t ins = two[0], packed = two[1];
+  if (ins > total || packed < n_pieces * (PMZ_HEAD + PMZ_TAIL) || packed > n_pieces * PMZ_MEMBER_MAX)
+    return fail (d, "internal: fetch_records_gz: %llu insertion sites and %llu bytes for %llu records", (unsigned long long) ins, (unsigned long long) packed,
+                 (unsigned long long) total);
+  *n_ins = ins;
+  *gz_bytes = packed;
+  // (nothing has been written to the caller's buffers so far, and nothing is unless both hold what they have to)
+  if (gz_out && packed > gz_capacity)
+    return fail (d, "fetch_records_gz: %llu bytes of members do not fit the caller's %llu", (unsigned long long) packed, (unsigned long long) gz_capacity);
+  if (gz_out && ins_records && ins > ins_capacity)
+    return fail (d, "fetch_records_gz: %llu insertion records do not fit the caller's %llu", (unsigned long long) ins, (unsigned long long) ins_capacity);
+  TRY (between (0, 1, &d->gz.ms[0]));
+  TRY (between (2, 3, &d->gz.ms[0]));
+  TRY (between (3, 4, &d->gz.ms[1]));
+  TRY (between (4, 5, &d->gz.ms[2]));
+  TRY (between (5, 6, &d->gz.ms[3]));
+  if (!gz_out)
+    return 0;                   // (the sizes only: no insertion list, no packed array)
+  TRY (dev_alloc (d, &d_ins.p, (size_t) ins));
+  TRY (dev_alloc (d, &d_gz.p, (size_t) packed + 16));
+  HIPCHK (d, stamp ());         // 7
+  hipLaunchKernelGGL (pmz_ins_emit_kernel, dim3 ((unsigned) n_itiles), dim3 (PMZ_BLOCK), 0, d->stream, d_rec, total, d_io, d_ins, ins);
+  HIPCHK (d, stamp ());         // 8
+  hipLaunchKernelGGL (pmz_pack_kernel, dim3 ((unsigned) n_pieces), dim3 (PMZ_BLOCK), 0, d->stream, d_slots, n_pieces, slot_bytes, d_mat, d_mlen, d_gz, packed);
+  HIPCHK (d, stamp ());         // 9
+  HIPCHK (d, hipStreamSynchronize (d->stream));
+  HIPCHK (d, hipGetLastError ());
+  TRY (between (7, 8, &d->gz.ms[1]));
+  TRY (between (8, 9, &d->gz.ms[3]));
+  TRY (gz_to_host (d, (char *) gz_out, (const char *) d_gz.p, (size_t) packed));
+  if (ins_records && ins)
+    HIPCHK (d, hipMemcpy (ins_records, d_ins, (size_t) ins * sizeof (uint4), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+extern "C" int pemap_dev_fetch_gz_ms (pemap_dev * d, float *ms4)
+{
+  memcpy (ms4, d->gz.ms, sizeof d->gz.ms);
   return 0;
 }
 

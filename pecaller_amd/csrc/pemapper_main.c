@@ -22,6 +22,10 @@
  * PEMAPPER_DEVICE_PARSE=1 (off by default): the read files' text goes to the device as it is and the read rows are made there
  * (pemap_dev_submit_fastq; map_one_file_parse below) instead of by fill_rows, a line at a time, on the host.  Every output file is
  * the same; the number of "We have read" lines may differ.  PEMAPPER_PARSE_BYTES: the text buffer per mate (default 384 bytes per pair of a batch).
+ * PEMAPPER_DEVICE_GZ=1 (off by default): the records of <out>.pileup.gz are deflated on the device (pemap_dev_fetch_records_gz; the rule is
+ * pemap_gz_rule.h) and written as they come back: BGZF members of 512 records each, whose heads say how long they are, and the 28-byte
+ * empty member at the end.  The file inflates to the same records; the indel rows are made from the insertion sites the same call
+ * returns; every other file is the same.  PEMAPPER_OUTPUT_TIMES=1: one more line per output set, the seconds its files took.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,9 +38,13 @@
 #include <unistd.h>
 #include "../../include/pemap_hip.h"
 #include "host_io.h"
+#include "pemap_gz_rule.h"
 
 /* (weak: the program links against a library without this entry too, and PEMAPPER_DEVICE_PARSE=1 then ends the run with a message) */
 extern __typeof__ (pemap_dev_submit_fastq) pemap_dev_submit_fastq __attribute__ ((weak));
+
+/* (weak as well: PEMAPPER_DEVICE_GZ=1 with a library that lacks the entry ends the run with a message) */
+extern __typeof__ (pemap_dev_fetch_records_gz) pemap_dev_fetch_records_gz __attribute__ ((weak));
 
 #define MAX_FILES 2000
 #define BATCH_PAIRS (1 << 20)
@@ -413,6 +421,8 @@ typedef struct
   int n_contigs;
   int paired;
   int io_threads;
+  int device_gz;                /* PEMAPPER_DEVICE_GZ=1 */
+  int output_times;             /* PEMAPPER_OUTPUT_TIMES=1 */
   char mate_names[9][80];
 } ctx_t;
 
@@ -424,9 +434,60 @@ typedef struct
 } pile_rec;
 #pragma pack(pop)
 
+/* the row of indel.txt.gz of a record with an insertion count; *ip walks the sorted insertion strings */
+static void
+indel_row (ctx_t * c, gzFile indelfile, const pile_rec * rec, size_t *ip)
+{
+  const uint32_t pos = rec->pos;
+  const char ref = c->genome[pos];
+  int tot_c = 0;
+  for (int k = 0; k < 6; k++)
+    tot_c += rec->c[k];
+  int ref_reads = ref == 'A' ? rec->c[0] : ref == 'C' ? rec->c[1] : ref == 'G' ? rec->c[2] : rec->c[3];
+  int which = find_chrom (c->real_starts, c->n_contigs, 0, c->n_contigs - 1, 7, pos);
+  int contig_pos = 1 + (int) (pos - c->real_starts[which]);
+  gzprintf (indelfile, "\n%s\t%d\t%c\t%d\t%d\t%d\t%d", c->contig_names[which], contig_pos, ref, tot_c, ref_reads, rec->c[4], rec->c[5]);
+  while (*ip < g_nins && g_ins[*ip].pos < pos)
+    (*ip)++;
+  /* the counter is a wrapping u16, the strings are all kept: print as many as the counter says */
+  for (int j = 0; j < rec->c[5] && *ip < g_nins && g_ins[*ip].pos == pos; j++, (*ip)++)
+    gzprintf (indelfile, "\t%s", g_inschars + g_ins[*ip].off);
+}
+
+/* <out>.pileup.gz, written by the host's deflate threads (pgz) or, with PEMAPPER_DEVICE_GZ=1, as the device's members come back */
+typedef struct
+{
+  int device_gz;
+  pgz host;
+  FILE *members;
+} pileup_out;
+
+static int
+pileup_open (pileup_out * o, const char *path, int device_gz, int io_threads)
+{
+  o->device_gz = device_gz;
+  if (!device_gz)
+    return pgz_open (&o->host, path, io_threads);
+  o->members = fopen (path, "wb");
+  return o->members == NULL;
+}
+
+/* (the device's file ends with the empty BGZF member, which is the whole file where nothing mapped) */
+static int
+pileup_close (pileup_out * o)
+{
+  if (!o->device_gz)
+    return pgz_close (&o->host);
+  uint8_t eof[PMZ_EOF_BYTES];
+  for (uint32_t k = 0; k < PMZ_EOF_BYTES; k++)
+    eof[k] = pmz_eof_byte (k);
+  const int bad = fwrite (eof, 1, PMZ_EOF_BYTES, o->members) != PMZ_EOF_BYTES;
+  return (fclose (o->members) != 0) | bad;
+}
+
 /* the final genome walk and the three writers, pemapper.c:788-900 / pemapper_tsw.c dump_output 848-965 */
 static void
-dump_output (ctx_t * c, const char *basename, long tot_pairs)
+dump_output_files (ctx_t * c, const char *basename, long tot_pairs)
 {
   char path[4200];
   long S[13];
@@ -438,8 +499,8 @@ dump_output (ctx_t * c, const char *basename, long tot_pairs)
   if (!summaryfile)
     die ("\n Can not open file %s for writing", path);
   snprintf (path, sizeof path, "%s.pileup.gz", basename);
-  pgz pileupfile;
-  if (pgz_open (&pileupfile, path, c->io_threads))
+  pileup_out pileupfile;
+  if (pileup_open (&pileupfile, path, c->device_gz, c->io_threads))
     die ("\n Can not open file %s for writing", path);
   snprintf (path, sizeof path, "%s.indel.txt.gz", basename);
   gzFile indelfile = gzopen (path, "w");
@@ -462,7 +523,7 @@ dump_output (ctx_t * c, const char *basename, long tot_pairs)
           fprintf (summaryfile, "\n%s\t%ld\t%g", c->mate_names[i], mate_counts[i], (double) mate_counts[i] / (double) tot_pairs);
       fprintf (summaryfile, "\n");
       fclose (summaryfile);
-      pgz_close (&pileupfile);
+      pileup_close (&pileupfile);
       gzclose (indelfile);
       return;
     }
@@ -482,36 +543,54 @@ dump_output (ctx_t * c, const char *basename, long tot_pairs)
   gzprintf (indelfile,
             "Fragment\tPositions\tReference Base\tTotal Coverage\tReference Reads\tNo Deletions\tNo Insertions\tInsertion Sequence");
   const uint64_t chunk = 1ull << 26;
-  pile_rec *recs = (pile_rec *) malloc (chunk * sizeof (pile_rec));
   size_t ip = 0;
-  for (uint64_t first = 0; first < c->gsize; first += chunk)
+  if (c->device_gz)
     {
-      uint64_t cnt = c->gsize - first < chunk ? c->gsize - first : chunk, n = 0;
-      ck (c->dev, pemap_dev_fetch_records (c->dev, first, cnt, recs, chunk, &n));
-      if (n && pgz_write (&pileupfile, recs, (size_t) n * sizeof (pile_rec)))
-        die ("\n Can not write %s", "the pileup");
-      for (uint64_t r = 0; r < n; r++)
-        if (recs[r].c[5] > 0)
-          {
-            const uint32_t pos = recs[r].pos;
-            const char ref = c->genome[pos];
-            int tot_c = 0;
-            for (int k = 0; k < 6; k++)
-              tot_c += recs[r].c[k];
-            int ref_reads = ref == 'A' ? recs[r].c[0] : ref == 'C' ? recs[r].c[1] : ref == 'G' ? recs[r].c[2] : recs[r].c[3];
-            int which = find_chrom (c->real_starts, c->n_contigs, 0, c->n_contigs - 1, 7, pos);
-            int contig_pos = 1 + (int) (pos - c->real_starts[which]);
-            gzprintf (indelfile, "\n%s\t%d\t%c\t%d\t%d\t%d\t%d", c->contig_names[which], contig_pos, ref, tot_c, ref_reads,
-                      recs[r].c[4], recs[r].c[5]);
-            while (ip < g_nins && g_ins[ip].pos < pos)
-              ip++;
-            /* the counter is a wrapping u16, the strings are all kept: print as many as the counter says */
-            for (int j = 0; j < recs[r].c[5] && ip < g_nins && g_ins[ip].pos == pos; j++, ip++)
-              gzprintf (indelfile, "\t%s", g_inschars + g_ins[ip].off);
-          }
+      /* a chunk's members and its insertion sites: both buffers hold the worst case of a chunk of this genome (pages that are never
+         written cost nothing), so one call per chunk does */
+      const uint64_t most = c->gsize < chunk ? c->gsize : chunk;
+      const uint64_t gz_cap = pmz_pieces (most) * PMZ_MEMBER_MAX;
+      /* (whole pages of its own: the page lock below then shares no page with another allocation, and a copy into a neighbour
+         never straddles the locked range) */
+      uint8_t *gz = NULL;
+      if (posix_memalign ((void **) &gz, 4096, (gz_cap + 4095) & ~(uint64_t) 4095))
+        gz = NULL;
+      pile_rec *sites = (pile_rec *) malloc (most * sizeof (pile_rec));
+      if (!gz || !sites)
+        die ("\n Can not allocate the buffers of %s", "the pileup");
+      /* page-locked for this output set, so that the members are copied straight into it (where the lock is refused they come
+         through the library's own page-locked blocks) */
+      const int pinned = pemap_dev_pin_host (c->dev, gz, gz_cap) == 0;
+      for (uint64_t first = 0; first < c->gsize; first += chunk)
+        {
+          uint64_t cnt = c->gsize - first < chunk ? c->gsize - first : chunk, n = 0, gz_bytes = 0, n_sites = 0;
+          ck (c->dev, pemap_dev_fetch_records_gz (c->dev, first, cnt, gz, gz_cap, &gz_bytes, &n, sites, most, &n_sites));
+          if (gz_bytes && fwrite (gz, 1, (size_t) gz_bytes, pileupfile.members) != (size_t) gz_bytes)
+            die ("\n Can not write %s", "the pileup");
+          for (uint64_t r = 0; r < n_sites; r++)
+            indel_row (c, indelfile, &sites[r], &ip);
+        }
+      if (pinned)
+        ck (c->dev, pemap_dev_unpin_host (c->dev, gz));
+      free (sites);
+      free (gz);
     }
-  free (recs);
-  if (pgz_close (&pileupfile))
+  else
+    {
+      pile_rec *recs = (pile_rec *) malloc (chunk * sizeof (pile_rec));
+      for (uint64_t first = 0; first < c->gsize; first += chunk)
+        {
+          uint64_t cnt = c->gsize - first < chunk ? c->gsize - first : chunk, n = 0;
+          ck (c->dev, pemap_dev_fetch_records (c->dev, first, cnt, recs, chunk, &n));
+          if (n && pgz_write (&pileupfile.host, recs, (size_t) n * sizeof (pile_rec)))
+            die ("\n Can not write %s", "the pileup");
+          for (uint64_t r = 0; r < n; r++)
+            if (recs[r].c[5] > 0)
+              indel_row (c, indelfile, &recs[r], &ip);
+        }
+      free (recs);
+    }
+  if (pileup_close (&pileupfile))
     die ("\n Can not write %s", "the pileup");
   gzclose (indelfile);
   double avg_reads = (double) total_bases / (double) c->gsize;
@@ -530,6 +609,17 @@ dump_output (ctx_t * c, const char *basename, long tot_pairs)
   fprintf (summaryfile, "\n");
   fclose (summaryfile);
   ck (c->dev, pemap_dev_reset_pileup (c->dev));  /* counters and totals start over for the next output name (tsw 917, 948-954) */
+}
+
+static void
+dump_output (ctx_t * c, const char *basename, long tot_pairs)
+{
+  struct timespec t0, t1;
+  clock_gettime (CLOCK_MONOTONIC, &t0);
+  dump_output_files (c, basename, tot_pairs);
+  clock_gettime (CLOCK_MONOTONIC, &t1);
+  if (c->output_times)
+    printf ("\n pemapper_hip: outputs of %s written in %.3f s \n", basename, (double) (t1.tv_sec - t0.tv_sec) + 1e-9 * (double) (t1.tv_nsec - t0.tv_nsec));
 }
 
 static int
@@ -1217,6 +1307,15 @@ main (int argc, char *argv[])
   memset (&c, 0, sizeof c);
   c.n_contigs = n_contigs;
   c.paired = paired;
+  {
+    /* (before any device work: a library without the entry is refused at once) */
+    const char *e = getenv ("PEMAPPER_DEVICE_GZ");
+    c.device_gz = e && atoi (e) == 1;
+    if (c.device_gz && !pemap_dev_fetch_records_gz)
+      die ("\n pemapper_hip: PEMAPPER_DEVICE_GZ=1 needs %s, which this library lacks", "pemap_dev_fetch_records_gz");
+    e = getenv ("PEMAPPER_OUTPUT_TIMES");
+    c.output_times = e && atoi (e) == 1;
+  }
   c.contig_names = (char **) calloc ((size_t) n_contigs + 1, sizeof (char *));
   uint32_t *contig_len = (uint32_t *) calloc ((size_t) n_contigs + 1, sizeof (uint32_t));
   uint32_t *contig_starts = (uint32_t *) calloc ((size_t) n_contigs + 2, sizeof (uint32_t));

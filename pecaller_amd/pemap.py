@@ -31,7 +31,11 @@ SYMBOLS = [
     "pecall_dev_sites_base_text",
     "pecall_dev_sites_base_gz",
     "pemap_dev_stage_fastq", "pemap_dev_submit_fastq", "pemap_dev_seed_launch", "pemap_dev_pipeline_stats",
+    "pemap_dev_fetch_records_gz", "pemap_dev_fetch_gz_ms",
 ]
+
+# pemap_gz_rule.h: records of a piece, that is of one BGZF member of pemap_dev_fetch_records_gz
+PILEUP_GZ_PIECE_RECORDS = 512
 
 # pemap_fastq.hip.h: bytes of text a block of the line-end scan takes, lines a block of the role and record scans takes, and how
 # many tile counts the one top-level block takes at a time (tests place their inputs at these edges)
@@ -103,6 +107,9 @@ def load_library():
         L.pemap_dev_free.argtypes = [vp, vp]
         L.pemap_dev_fetch_pileup.argtypes = [vp, vp, vp, vp]
         L.pemap_dev_fetch_records.argtypes = [vp, u64, u64, vp, u64, C.POINTER(u64)]
+        if hasattr(L, "pemap_dev_fetch_records_gz"):    # (an older library under PEMAP_LIB lacks them)
+            L.pemap_dev_fetch_records_gz.argtypes = [vp, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, u64, C.POINTER(u64)]
+            L.pemap_dev_fetch_gz_ms.argtypes = [vp, vp]
         L.pemap_dev_reset_pileup.argtypes = [vp]
         L.pemap_dev_summary.argtypes = [vp, vp]
         L.pemap_dev_run_stats.argtypes = [vp, vp, vp]
@@ -366,6 +373,27 @@ class PemapDev:
         if n.value:
             self._ck(self.L.pemap_dev_fetch_records(self.h, first, count, _p(out), n.value, C.byref(n)))
         return out
+
+    def fetch_records_gz(self, first=0, count=None):
+        """the records of fetch_records deflated on the device -> (the BGZF members as bytes, the number of records, the records with
+        an insertion count)"""
+        count = self.gsize - first if count is None else count
+        nb, nr, ni = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        # one call: buffers for the worst case of `count` positions (every position a record, every piece stored; pages that are
+        # never written cost nothing)
+        pieces = (count + PILEUP_GZ_PIECE_RECORDS - 1) // PILEUP_GZ_PIECE_RECORDS
+        gz = np.empty(pieces * (16 * PILEUP_GZ_PIECE_RECORDS + 31), np.uint8)
+        ins = np.empty(count, PILE_DT)
+        self._ck(self.L.pemap_dev_fetch_records_gz(self.h, first, count, _p(gz) if count else None, gz.nbytes, C.byref(nb), C.byref(nr),
+                                                   _p(ins), len(ins), C.byref(ni)))
+        gz, ins = gz[:nb.value], ins[:ni.value].copy()
+        return gz.tobytes(), nr.value, ins
+
+    def fetch_gz_ms(self):
+        """kernel milliseconds of the last fetch_records_gz: records, insertion list, deflate, scan and pack"""
+        t = np.zeros(4, np.float32)
+        self._ck(self.L.pemap_dev_fetch_gz_ms(self.h, _p(t)))
+        return dict(zip(("records", "insertions", "deflate", "pack"), (float(x) for x in t)))
 
     def reset_pileup(self):
         self._ck(self.L.pemap_dev_reset_pileup(self.h))

@@ -97,6 +97,7 @@ struct PmChunkCtr
   unsigned next_end;            // work counter of the persistent look-up waves
   unsigned n_big2;              // read-ends the second tier of the fused seed kernel leaves to pm_seed_kernel
   unsigned next_end2;           // the second tier's work counter
+  unsigned long long t_lookup_begin, t_lookup_end;      // the fused first tier's own stamps (wall_clock64; 0: the launch took none)
 };
 
 #define PM_MAX_CHUNKS 256
@@ -402,7 +403,13 @@ struct PmRun
   // two-stream pipeline: the look-up kernel of chunk k+1 (memory stream) runs beside vote/SW/walk of chunk k
   hipStream_t stream2 = nullptr;
   PmChunkCtr *d_chunk_ctr = nullptr;    // PM_MAX_CHUNKS
+  // where absorb_run copies them, and the insertion cursor behind them: pinned memory of the object's own.  (A copy into heap memory must
+  // lie outside every host registration of the process, PmPinned above -- and a heap block may lie where a caller's buffer, registered
+  // and since freed, lay: the copy of a run's counters into a std::vector was refused that way, `invalid argument`, in one run of
+  // pemapper_hip in some, whatever the library's other sources)
+  struct Absorbed { PmChunkCtr ctr[PM_MAX_CHUNKS]; PmInsCursor cur; } *h_absorbed = nullptr;
   std::vector < hipEvent_t > evs;       // PM_NEV per chunk
+  int wall_khz = 0;             // ticks of wall_clock64 per millisecond (hipDeviceAttributeWallClockRate): the first tier's own stamps
   uint64_t last_big = 0, last_big2 = 0; // read-ends the fused seed kernel's first tier passed over; of them, left to pm_seed_kernel
   PmCounters last_ctr = {};     // summed over the chunks of the last run
   PmInsCursor last_cur = {};
@@ -419,6 +426,7 @@ struct PmRun
 static void run_free (PmRun & r)
 {
   pm_free (r.d_chunk_ctr);
+  pm_host_free (r.h_absorbed);
   for (hipEvent_t & e : r.evs)
     pm_event_free (e);
   r.evs.clear ();
@@ -1396,6 +1404,17 @@ struct PmSchedule
   bool emit_on_alu;             // the fused layout's emit kernel goes to the ALU stream in front of the chunk's DP
 };
 
+// does the look-up launch of a chunk stamp its own interval (PmChunkCtr::t_lookup_begin / t_lookup_end)?  The fused kernel's first
+// tier does; the reference layout, PEMAP_FIRST_TIER=0 and a build with the phase probes keep the empty kernel and the two events
+static bool pm_stamped (const pemap_dev * d)
+{
+#ifdef PEMAP_TIMING_PROBES
+  return false;
+#else
+  return pm_fused (d) && d->kn.first_tier && d->run.wall_khz > 0;  // (a device without a wall clock rate keeps the events)
+#endif
+}
+
 // ---- the look-ups of one chunk: the fused seed kernel's two tiers, or the reference layout's look-ups into the set's lists
 static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
 {
@@ -1404,9 +1423,19 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
   L.positions = &cc->positions;
   L.next_end = &cc->next_end;
   // (an event recorded straight after a stream wait is stamped when the wait is queued, not when it is satisfied: the empty
-  // kernel makes the stamp the moment the look-up kernel can start, so that LOOKUP_BEGIN..LOOKUP_END is the kernel's own duration)
-  hipLaunchKernelGGL (pm_nop_kernel, dim3 (1), dim3 (1), 0, st);
-  hipEventRecord (ev[PM_EV_LOOKUP_BEGIN], st);
+  // kernel makes the stamp the moment the look-up kernel can start, so that LOOKUP_BEGIN..LOOKUP_END is the kernel's own duration.
+  // The fused first tier stamps its interval itself, pm_stamped: no empty kernel and neither event in front of it)
+  const bool stamped = pm_stamped (d);
+  if (stamped)
+    {
+      L.t_begin = &cc->t_lookup_begin;
+      L.t_end = &cc->t_lookup_end;
+    }
+  else
+    {
+      hipLaunchKernelGGL (pm_nop_kernel, dim3 (1), dim3 (1), 0, st);
+      hipEventRecord (ev[PM_EV_LOOKUP_BEGIN], st);
+    }
   // PEMAP_LOOKUP_WAVES=n: n persistent one-wave workgroups per CU (pm_seed4_kernel: 12,784 bytes of LDS and 128 VGPRs a wave).  The
   // kernel itself keeps gaining with n (5.06 / 4.53 / 4.05 / 3.84 ms per launch with 7 / 8 / 9 / 10, profiles/r04_ab_sweeps.txt) while the
   // other stream's DP kernels lose the SIMDs' registers to it.  Ten was the most 14,976 bytes admitted; twelve is what
@@ -1460,6 +1489,7 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
   // the list (twice, for reads over 160 bases), a few waves per CU -- most launches find a few thousand ends; what THAT leaves goes
   // to pm_seed_kernel (launch_rest)
   PmLists L2 = L;
+  L2.t_begin = L2.t_end = nullptr;
   L2.big_list = L.big_list + d->wk.lists_cap;
   L2.n_big = &cc->n_big2;
   L2.next_end = &cc->next_end2;
@@ -1471,7 +1501,8 @@ static void launch_lookup (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmCh
                           c.prm, H, L, (const uint32_t *) nullptr, (const unsigned *) nullptr, lprio);
     else if (c.b.n_ends > 0)    // (a chunk's ends fit the list: run_slice sizes it by the chunk)
       hipLaunchKernelGGL (pm_all_big_kernel, dim3 ((unsigned) (c.b.n_ends + 255) / 256), dim3 (256), 0, st, L.big_list, L.n_big, c.b.n_ends);
-    hipEventRecord (ev[PM_EV_LOOKUP_END], st);
+    if (!stamped)
+      hipEventRecord (ev[PM_EV_LOOKUP_END], st);
     hipLaunchKernelGGL (HIP_KERNEL_NAME (pm_seed4_kernel < sm.value, 1 >), dim3 (grid2), dim3 (64), sizeof (PmSeed4Shared < sm.value, 1 >), st, c.ix, c.b,
                         c.prm, H, L2, (const uint32_t *) L.big_list, (const unsigned *) L.n_big, lprio);
   });
@@ -1507,8 +1538,10 @@ static void launch_vote (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChun
 //      over; then the set's lists are consumed
 static void launch_rest (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChunkCtr * cc, hipStream_t st)
 {
-  // The remainder appends to the chunk's task lists and uses the one spill scratch: a second launch for the same chunk doubles the
-  // appended tasks past the lists' ends (the fault PEMAP_REST_STREAM3=1 produced in round 3).  Refused here, reported by run_slice.
+  // The remainder writes the raw hit lists of its ends and uses the one spill scratch: a second launch for the same chunk would share
+  // that scratch with the first (the fault PEMAP_REST_STREAM3=1 produced in round 3, when it still appended to the task lists).
+  // Refused here, reported by run_slice.  (It touches neither n_tasks_s nor n_slots: pm_emit_kernel, which numbers the slabs by
+  // the single-hit task numbers, is their only writer before pm_select_kernel.)
   const uint64_t id = (d->run.serial << 24) | (uint64_t) (cc - d->run.d_chunk_ctr);
   if (S.rest_id == id)
     {
@@ -1534,7 +1567,8 @@ static void launch_rest (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChun
 // ---- the emit kernel (windows, slab numbers, SW task lists); the seed stage ends here
 static void launch_emit (pemap_dev * d, const RunCtx & c, PmChunkSet & S, PmChunkCtr * cc, hipEvent_t * ev, hipStream_t st)
 {
-  hipLaunchKernelGGL (pm_emit_kernel, dim3 ((c.b.n_ends + 63) / 64), dim3 (64), 0, st, c.ix, c.b, S.hits, S.tasks_s, S.tasks_m, &cc->c);
+  const int per_wave = 64 * PM_EMIT_ROUNDS;
+  hipLaunchKernelGGL (pm_emit_kernel, dim3 ((c.b.n_ends + per_wave - 1) / per_wave), dim3 (64), 0, st, c.ix, c.b, S.hits, S.tasks_s, S.tasks_m, &cc->c);
   hipEventRecord (ev[PM_EV_SEED_END], st);
 }
 
@@ -1713,9 +1747,10 @@ static int absorb_run (pemap_dev * d)
       }
   }
 #endif
-  std::vector < PmChunkCtr > hc (nch);
-  HIPCHK (d, hipMemcpy (hc.data (), d->run.d_chunk_ctr, sizeof (PmChunkCtr) * nch, hipMemcpyDeviceToHost));
-  HIPCHK (d, hipMemcpy (&d->run.last_cur, d->pile.d_cur, sizeof (PmInsCursor), hipMemcpyDeviceToHost));
+  const PmChunkCtr *const hc = d->run.h_absorbed->ctr;
+  HIPCHK (d, hipMemcpy (d->run.h_absorbed->ctr, d->run.d_chunk_ctr, sizeof (PmChunkCtr) * nch, hipMemcpyDeviceToHost));
+  HIPCHK (d, hipMemcpy (&d->run.h_absorbed->cur, d->pile.d_cur, sizeof (PmInsCursor), hipMemcpyDeviceToHost));
+  d->run.last_cur = d->run.h_absorbed->cur;
   PmCounters & t = d->run.last_ctr;
   for (int k = 0; k < nch; k++)
     {
@@ -1742,8 +1777,20 @@ static int absorb_run (pemap_dev * d)
       d->run.last_big2 += hc[k].n_big2;
       hipEvent_t *ev = &d->run.evs[(size_t) k * PM_NEV];
       float ms = 0.f;
+      // (a first tier that stamped its own interval -- its stamps are zeroed with the chunk's counters -- recorded no look-up events.
+      // Workgroup 0 is not bound to start first: the interval may miss the few microseconds by which another workgroup was earlier, and
+      // a chunk whose end stamp is not behind its begin -- a launch in which workgroup 0 came up last -- adds nothing to `lookup`)
+      const bool stamped = hc[k].t_lookup_end != 0ull;
+      if (stamped && hc[k].t_lookup_end > hc[k].t_lookup_begin)
+        {
+          ms = (float) ((double) (hc[k].t_lookup_end - hc[k].t_lookup_begin) / (double) d->run.wall_khz);
+          d->run.last_ms[PM_T_LOOKUP] += ms;
+          d->run.last_ms[PM_T_SEED] += ms;
+        }
       for (const auto & iv : pm_intervals)
-        if (hipEventElapsedTime (&ms, ev[iv.from], ev[iv.to]) == hipSuccess)
+        if (stamped && iv.from == PM_EV_LOOKUP_BEGIN)
+          continue;
+        else if (hipEventElapsedTime (&ms, ev[iv.from], ev[iv.to]) == hipSuccess)
           {
             d->run.last_ms[iv.slot] += ms;
             d->run.last_ms[PM_T_SEED] += iv.seed_too ? ms : 0.f;
@@ -1771,10 +1818,15 @@ static int ensure_pipeline (pemap_dev * d, int chunk_ends)
   // (a CU mask and stream priorities for the look-up stream were tried in rounds 1 and 2 and gave nothing)
   if (!d->run.stream2)
     HIPCHK (d, hipStreamCreateWithFlags (&d->run.stream2, hipStreamNonBlocking));
+  // (asked once; -1: the device reports none, and the look-ups are timed by events as before)
+  if (d->run.wall_khz == 0 && (hipDeviceGetAttribute (&d->run.wall_khz, hipDeviceAttributeWallClockRate, d->device) != hipSuccess || d->run.wall_khz <= 0))
+    d->run.wall_khz = -1;
   if (d->run.evs.empty ())
     {
       // (the counters and the events are there together or not at all: the next call tries again)
       int rc = dev_alloc (d, &d->run.d_chunk_ctr, (size_t) PM_MAX_CHUNKS);
+      if (!rc && hipHostMalloc ((void **) &d->run.h_absorbed, sizeof (*d->run.h_absorbed), hipHostMallocDefault) != hipSuccess)
+        rc = fail (d, "hipHostMalloc of the absorbed counters failed");
       d->run.evs.resize ((size_t) PM_MAX_CHUNKS * PM_NEV, nullptr);
       for (size_t i = 0; !rc && i < d->run.evs.size (); i++)
         if (hipEventCreate (&d->run.evs[i]) != hipSuccess)

@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
 #include "pemap_pile_diff.h"
 
 #define PM_MAX_HITS 200            // max_hits, pemapper.c:162
@@ -113,7 +114,8 @@ __device__ __forceinline__ uint16_t pm_pile_get (const PmPile & p, size_t pos, i
   return (uint16_t) (p.w[(size_t) q * p.plane_words + (pos >> 1)] >> (16 * (pos & 1)));
 }
 
-// counters shared by the kernels of one run (zeroed at the start of every run)
+// counters shared by the kernels of one run (zeroed at the start of every run).  {n_tasks_s, n_tasks_m} and {n_wins, n_walks} are
+// each one aligned 64-bit word: pm_emit_kernel and pm_select_kernel reserve both ranges of a wave with one 64-bit atomic
 struct PmCounters
 {
   unsigned int n_tasks_s;          // SW problems of read-ends with exactly one hit (scored WITH direction nibbles)
@@ -121,7 +123,7 @@ struct PmCounters
   unsigned int n_slots;            // direction slabs handed out
   unsigned int n_redo;             // winners of multi-hit ends: scored again with direction nibbles
   unsigned int n_wins;             // alignments to walk back
-  unsigned int n_tasks_dp;         // single-hit problems the gapless rule (pm_gapless_kernel) leaves to the DP
+  unsigned int n_walks;            // of n_wins, the alignments pm_walk_kernel follows (the others are known to be plain diagonals)
   unsigned long long positions;    // P: entries copied out of .mdx
   unsigned long long cells_score;  // DP cells computed without / with direction nibbles
   unsigned long long cells_dirs;
@@ -133,9 +135,13 @@ struct PmCounters
   unsigned int band_next[2];       // their work counters
   unsigned int n_c3[2];            // problems the gapless rule's first launch leaves to its second (case (3)): single-hit ends, multi-hit ends
   unsigned long long cells_band;   // band cells computed
-  unsigned int n_walks;            // of n_wins, the alignments pm_walk_kernel follows (the others are known to be plain diagonals)
+  unsigned int n_tasks_dp;         // single-hit problems the gapless rule (pm_gapless_kernel) leaves to the DP
   unsigned int n_gate[2];          // of n_band, the problems admitted by the two-diagonal bound (PEMAP_BAND_GATE): single-hit ends, multi-hit ends
 };
+static_assert (offsetof (PmCounters, n_tasks_s) % 8 == 0 && offsetof (PmCounters, n_tasks_m) == offsetof (PmCounters, n_tasks_s) + 4,
+               "pm_emit_kernel's packed atomic: n_tasks_s and n_tasks_m are the halves of one aligned 64-bit word");
+static_assert (offsetof (PmCounters, n_wins) % 8 == 0 && offsetof (PmCounters, n_walks) == offsetof (PmCounters, n_wins) + 4,
+               "pm_select_kernel's packed atomic: n_wins and n_walks are the halves of one aligned 64-bit word");
 
 // insertion log cursor: survives runs until the host drains the log
 struct PmInsCursor

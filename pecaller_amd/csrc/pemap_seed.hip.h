@@ -1,6 +1,7 @@
 // pemap_seed.hip.h -- K1/K2: seed gather and diagonal vote (initial_map / find_matches) on gfx950.
 // Included from pemap_kernels.hip.h.
 #pragma once
+#include "pemap_wave.hip.h"
 
 // pm_seed_kernel is the seed stage's big-end remainder: it takes only the read-ends on a big-end list, the ones the look-up /
 // vote kernels of pemap_seed2.hip.h or the fused kernel of pemap_seed4.hip.h passed over (a strand with more positions than
@@ -310,19 +311,84 @@ template < class SH > __device__ __forceinline__ void pm_seed_emit (SH & sh, con
     }
 }
 
-// hit -> spot and SW window (pemapper.c:1664-1669, 1047-1081), in place
-__device__ __forceinline__ void pm_emit_hit (const PmIndex & ix, const PmHits & h, size_t o, int len)
+// pm_find_chrom for the N values of a lane at once: every value takes the probes pm_find_chrom takes for it, in the same order, and the
+// loads of the N chains are in flight together (a value that is off, or done, reads entry 0).  -> chrom[], 0 where off
+template < int N > __device__ __forceinline__ void pm_find_chrom_n (const uint32_t * pos, int n, const uint32_t (&x)[N], const bool (&on)[N], int (&chrom)[N])
+{
+  int first[N], last[N], tr[N];
+  bool open[N];
+#pragma unroll
+  for (int r = 0; r < N; r++)
+    {
+      first[r] = 0;
+      last[r] = n - 1;
+      tr[r] = 7;
+      open[r] = on[r];
+      chrom[r] = 0;
+    }
+  for (int it = 0; it < 64; it++)
+    {
+      bool any_open = false;
+      uint32_t a[N], b[N];
+#pragma unroll
+      for (int r = 0; r < N; r++)
+        {
+          if (open[r] && first[r] == last[r])
+            {
+              chrom[r] = first[r];
+              open[r] = false;
+            }
+          any_open |= open[r];
+          const bool in_a = open[r] && tr[r] >= 0 && tr[r] <= n, in_b = open[r] && tr[r] + 1 >= 0 && tr[r] + 1 <= n;
+          a[r] = pos[in_a ? tr[r] : 0];
+          b[r] = pos[in_b ? tr[r] + 1 : 0];
+          a[r] = in_a ? a[r] : 0xFFFFFFFFu;
+          b[r] = in_b ? b[r] : 0xFFFFFFFFu;
+        }
+      if (!any_open)
+        return;
+#pragma unroll
+      for (int r = 0; r < N; r++)
+        if (open[r])
+          {
+            if (a[r] <= x[r] && b[r] >= x[r])
+              {
+                chrom[r] = tr[r];
+                open[r] = false;
+              }
+            else
+              {
+                if (a[r] > x[r])
+                  last[r] = tr[r] - 1;
+                else
+                  first[r] = tr[r] + 1;
+                tr[r] = (last[r] + first[r]) / 2;
+              }
+          }
+    }
+#pragma unroll
+  for (int r = 0; r < N; r++)
+    if (open[r])
+      chrom[r] = first[r] < 0 ? 0 : (first[r] > n - 1 ? n - 1 : first[r]);
+}
+
+// hit -> spot (pemapper.c:1664-1669): the matched position less the segment offset it was found with
+__device__ __forceinline__ uint32_t pm_emit_spot (const PmHits & h, size_t o)
 {
   long temp = (long) h.spot[o] - (long) h.nn[o];
-  uint32_t spot = (uint32_t) (temp > 0 ? temp : 0);
-  int chrom = pm_find_chrom (ix.contig_starts, ix.n_contigs, spot);
+  return (uint32_t) (temp > 0 ? temp : 0);
+}
+
+// spot -> SW window (pemapper.c:1047-1081), in place; cs / cs_next: contig_starts[chrom] and [chrom + 1]
+__device__ __forceinline__ void pm_emit_hit (const PmHits & h, size_t o, int len, uint32_t spot, int chrom, uint32_t cs, uint32_t cs_next)
+{
   unsigned extra = 15u * (unsigned) chrom;
   long tt = (long) extra + (long) spot - (long) PM_SLOP;
   if (tt < 0)
     tt = 0;
-  unsigned cs0 = ix.contig_starts[chrom] + extra;
+  unsigned cs0 = cs + extra;
   unsigned start_match = ((long) cs0 > tt) ? cs0 : (unsigned) tt;
-  unsigned e1 = ix.contig_starts[chrom + 1] + extra;
+  unsigned e1 = cs_next + extra;
   unsigned e2w = extra + spot + (unsigned) len + PM_SLOP;
   unsigned end_match = e1 < e2w ? e1 : e2w;
   int blen = (int) (1u + end_match - start_match);
@@ -331,68 +397,98 @@ __device__ __forceinline__ void pm_emit_hit (const PmIndex & ix, const PmHits & 
   h.nn[o] = (int16_t) blen;
 }
 
-// One thread per read-end.  An end with one hit is scored once, with direction nibbles, into its own slab; ends with
-// several hits are scored without, and only the winner is scored again (pm_select_kernel).  Slab numbers and task-list
-// ranges are handed out with one atomic per wave.
+// A wave takes PM_EMIT_ROUNDS rounds of 64 consecutive read-ends, one lane per end and round.  An end with one hit is scored once,
+// with direction nibbles, into its own slab; ends with several hits are scored without, and only the winner is scored again
+// (pm_select_kernel).  The wave reserves its ranges of both task lists with ONE returning atomic on the pair {n_tasks_s, n_tasks_m}
+// (PmCounters: one aligned 64-bit word; a chunk has fewer than 2^32 problems, so the low half never carries): a single address
+// returns some 85 M atomics a second however many waves ask, and with three atomics per 64 ends the kernel ran at that rate.
+// Slab numbers are the single-hit task numbers: this kernel is the only writer of n_slots and n_tasks_s before pm_select_kernel,
+// which continues from the n_slots left here.  The hits of the wave's ends are worked through by hit number, the rounds side by
+// side: the dependent loads of the contig look-up (pm_find_chrom_n) are PM_EMIT_ROUNDS chains in flight, not one.
 // (one-wave workgroups, like every kernel that runs beside the seed kernel: a wave starts wherever a SIMD has room, a workgroup of
 // four waited until a CU had room for all four)
+#define PM_EMIT_ROUNDS 8
 __global__ __launch_bounds__ (64) void pm_emit_kernel (PmIndex ix, PmBatch b, PmHits h, uint32_t * tasks_s, uint32_t * tasks_m, PmCounters * ctr)
 {
-  const int e = blockIdx.x * 64 + threadIdx.x;
+  constexpr int R = PM_EMIT_ROUNDS;
   const int lane = threadIdx.x & 63;
-  const int tot = e < b.n_ends ? h.n_hits[e] : 0;
   const unsigned long long below = (1ull << lane) - 1ull;
-  // ---- single hits
-  const unsigned long long ms = __ballot (tot == 1);
-  unsigned slot0 = 0, task0 = 0;
-  if (ms)
+  // (an end past the chunk's last reads the last end's count and length, and counts as an end without hits)
+  int e[R], tot[R];
+#pragma unroll
+  for (int r = 0; r < R; r++)
     {
+      const int er = (int) blockIdx.x * (64 * R) + 64 * r + lane;
+      e[r] = er < b.n_ends ? er : b.n_ends - 1;
+      tot[r] = h.n_hits[e[r]];
+      tot[r] = er < b.n_ends ? tot[r] : 0;
+    }
+  // ---- places inside the wave's ranges: a single hit's rank among the wave's single hits; of an end with several hits, the
+  //      exclusive prefix of the counts
+  unsigned at[R], ns = 0, nm = 0;
+#pragma unroll
+  for (int r = 0; r < R; r++)
+    {
+      const unsigned long long ms = __ballot (tot[r] == 1);
+      const unsigned mine = tot[r] > 1 ? (unsigned) tot[r] : 0u;
+      const unsigned inc = pm_wave_incl_sum (mine);
+      at[r] = tot[r] == 1 ? ns + (unsigned) __popcll (ms & below) : nm + inc - mine;
+      ns += (unsigned) __popcll (ms);
+      nm += (unsigned) __builtin_amdgcn_readlane ((int) inc, 63);
+    }
+  unsigned task0 = 0, mbase = 0;
+  if (ns | nm)
+    {
+      unsigned long long old = 0;
       if (lane == 0)
         {
-          slot0 = atomicAdd (&ctr->n_slots, (unsigned) __popcll (ms));
-          task0 = atomicAdd (&ctr->n_tasks_s, (unsigned) __popcll (ms));
+          old = atomicAdd ((unsigned long long *) &ctr->n_tasks_s, (unsigned long long) ns | ((unsigned long long) nm << 32));
+          if (ns)
+            atomicAdd (&ctr->n_slots, ns);      // (nothing waits for it)
         }
-      slot0 = __shfl (slot0, 0);
-      task0 = __shfl (task0, 0);
+      task0 = (unsigned) __builtin_amdgcn_readfirstlane ((int) (unsigned) old);
+      mbase = (unsigned) __builtin_amdgcn_readfirstlane ((int) (unsigned) (old >> 32));
     }
-  // ---- several hits: exclusive prefix of the counts inside the wave
-  const unsigned mine = tot > 1 ? (unsigned) tot : 0u;
-  unsigned inc = mine;
-  for (int o = 1; o < 64; o <<= 1)
+  int len[R], tmax = 0;
+#pragma unroll
+  for (int r = 0; r < R; r++)
     {
-      const unsigned t = __shfl_up (inc, o);
-      if (lane >= o)
-        inc += t;
+      (void) pm_read_ptr (b, e[r], &len[r]);
+      if ((int) blockIdx.x * (64 * R) + 64 * r + lane < b.n_ends)
+        h.slot[e[r]] = tot[r] == 1 ? (int) (task0 + at[r]) : -1;
+      tmax = tot[r] > tmax ? tot[r] : tmax;
     }
-  const unsigned wave_total = __shfl (inc, 63);
-  unsigned mbase = 0;
-  if (wave_total)
+  // ---- hit t of every end that has one (t < PM_MAX_HITS: a hit's place lies inside the arrays whether the end has it or not)
+  for (int t = 0; t < tmax; t++)
     {
-      if (lane == 0)
-        mbase = atomicAdd (&ctr->n_tasks_m, wave_total);
-      mbase = __shfl (mbase, 0);
-    }
-  if (e >= b.n_ends)
-    return;
-  int len;
-  (void) pm_read_ptr (b, e, &len);
-  const size_t o0 = (size_t) e * PM_MAX_HITS;
-  if (tot == 1)
-    {
-      const unsigned r = (unsigned) __popcll (ms & below);
-      h.slot[e] = (int) (slot0 + r);
-      pm_emit_hit (ix, h, o0, len);
-      tasks_s[task0 + r] = (uint32_t) o0;
-    }
-  else
-    {
-      h.slot[e] = -1;
-      const unsigned tb = mbase + inc - mine;
-      for (int t = 0; t < tot; t++)
+      bool on[R];
+      uint32_t spot[R], cs[R], cs_next[R];
+      int chrom[R];
+#pragma unroll
+      for (int r = 0; r < R; r++)
         {
-          pm_emit_hit (ix, h, o0 + t, len);
-          tasks_m[tb + t] = (uint32_t) (o0 + t);
+          on[r] = t < tot[r];
+          spot[r] = pm_emit_spot (h, (uint32_t) e[r] * (uint32_t) PM_MAX_HITS + (uint32_t) t);
         }
+      pm_find_chrom_n < R > (ix.contig_starts, ix.n_contigs, spot, on, chrom);
+#pragma unroll
+      for (int r = 0; r < R; r++)
+        {
+          cs[r] = ix.contig_starts[chrom[r]];
+          cs_next[r] = ix.contig_starts[chrom[r] + 1];
+        }
+#pragma unroll
+      for (int r = 0; r < R; r++)
+        if (on[r])
+          {
+            // (a 32-bit index: task ids are end * PM_MAX_HITS + hit in 32 bits everywhere)
+            const uint32_t o = (uint32_t) e[r] * (uint32_t) PM_MAX_HITS + (uint32_t) t;
+            pm_emit_hit (h, o, len[r], spot[r], chrom[r], cs[r], cs_next[r]);
+            if (tot[r] == 1)
+              tasks_s[task0 + at[r]] = o;
+            else
+              tasks_m[mbase + at[r] + (unsigned) t] = o;
+          }
     }
 }
 

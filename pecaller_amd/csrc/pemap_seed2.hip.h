@@ -31,6 +31,7 @@ struct PmLists
   unsigned *n_big;
   unsigned long long *positions;       // P counter
   unsigned *next_end;                  // work counter of the persistent look-up waves (ends beyond the first grid-ful)
+  unsigned long long *t_begin, *t_end; // pm_seed4_kernel's first tier stamps its own interval here (wall_clock64; null: it does not)
 };
 
 // ---- the look-ups with ONE WAVE per read-end, persistent.  Random 64-byte lines are a DRAM-side limit (about 47 G/s on

@@ -67,7 +67,9 @@
 #endif
 #ifndef PM_S4_AHEAD_T2
 #define PM_S4_AHEAD_T2 2        // ... ends reserved ahead of the one in work (1: the next end's bytes are requested where its entries are, and waited for:
-                                // 518 us a launch against 580 in one kernel trace each, profiles/r16_ab_sweeps.txt; the step's A/B is not taken, 2 stays)
+                                // 513 us a launch against 565 -- but with 1 the counters per step are NOT the ones 2 gives (walks, positions, pile_incs
+                                // lower by 0.1-0.3 %) and change from run to run: profiles/r20_ab_sweeps.txt.  The form loses work, most likely to a load
+                                // it does not wait for; it must not be enabled until the cause is found.  2 stays)
 #endif
 #ifndef PM_S4_HDR_AHEAD_T2
 #define PM_S4_HDR_AHEAD_T2 1    // ... the record headers of round r + 1 are requested before round r's tails are walked
@@ -182,6 +184,12 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
   typedef PmSeed4Shared < SMAX, TIER > SH;
   SH & sh = *reinterpret_cast < SH * >(pm_seed4_lds);
   const int lane = threadIdx.x;
+  // the first tier stamps its own interval (the host's `lookup` time): workgroup 0 the launch's begin here, every wave its end below.
+  // (An event in front of the launch is stamped when the stream's wait is queued, and the empty kernel that made the stamp late
+  // cost the seed stream 0.1 ms per chunk)
+  if constexpr (TIER == 0)
+    if (out.t_begin && blockIdx.x == 0 && lane == 0)
+      *out.t_begin = wall_clock64 ();
   const int idepth = ix.idepth;
   const int max_off = max (2, idepth - 4);
   const uint32_t span = (uint32_t) (2 * (max_off - 1));
@@ -1025,4 +1033,7 @@ void pm_seed4_kernel (PmIndex ix, PmBatch b, PmParams prm, PmHits h, PmLists out
 #endif
   if (lane == 0 && n_pos)
     atomicAdd (out.positions, n_pos);
+  if constexpr (TIER == 0)
+    if (out.t_end && lane == 0)
+      atomicMax (out.t_end, (unsigned long long) wall_clock64 ());    // (nothing waits for it)
 }

@@ -1350,9 +1350,13 @@ __global__ __launch_bounds__ (64) void pm_select_kernel (PmBatch b, PmParams prm
   else
     code = 8;
   uint32_t r1 = 0, r2 = 0;
+  size_t o_win[2] = { 0, 0 };
+  bool win[2], walk[2];
   for (int which = 0; which < 2; which++)
     {
       const int use = which ? use2 : use1;
+      win[which] = use >= 0;
+      walk[which] = false;
       if (use < 0)
         continue;
       const int e = e1 + which;
@@ -1366,16 +1370,37 @@ __global__ __launch_bounds__ (64) void pm_select_kernel (PmBatch b, PmParams prm
       if (h.slot[e] < 0 && !gapless)
         {
           // winner of a multi-hit end (not decided by the gapless rule, whose traceback needs no nibbles): give it a slab
-          // and have it scored again with direction nibbles
+          // and have it scored again with direction nibbles (rare: an atomic per lane)
           h.slot[e] = (int) atomicAdd (&ctr->n_slots, 1u);
           redo[atomicAdd (&ctr->n_redo, 1u)] = (uint32_t) o;
         }
-      const unsigned w = atomicAdd (&ctr->n_wins, 1u);
-      wins[w] = (uint32_t) o;
+      o_win[which] = o;
       // the winners pm_walk_kernel has to follow cell by cell (the ones sent to redo among them): the rest are mm diagonal steps
-      if (!gapless)
-        walks[atomicAdd (&ctr->n_walks, 1u)] = w;
+      walk[which] = !gapless;
     }
+  // the wave's winners, first ends then second ends, and the walkers among them, counted by ballot: ONE returning atomic on the pair
+  // {n_wins, n_walks} (PmCounters: one aligned 64-bit word, neither half can carry) reserves both ranges, a lane writes at its rank.
+  // (the lanes past the chunk's last pair have left: lane 0 is there whenever any lane is)
+  {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const unsigned long long bw0 = __ballot (win[0]), bw1 = __ballot (win[1]), bk0 = __ballot (walk[0]), bk1 = __ballot (walk[1]);
+    const unsigned nw0 = (unsigned) __popcll (bw0), nw = nw0 + (unsigned) __popcll (bw1);
+    const unsigned nk0 = (unsigned) __popcll (bk0), nk = nk0 + (unsigned) __popcll (bk1);
+    unsigned long long old = 0;
+    if (lane == 0 && nw)
+      old = atomicAdd ((unsigned long long *) &ctr->n_wins, (unsigned long long) nw | ((unsigned long long) nk << 32));
+    const unsigned w0 = (unsigned) __builtin_amdgcn_readfirstlane ((int) (unsigned) old);
+    const unsigned k0 = (unsigned) __builtin_amdgcn_readfirstlane ((int) (unsigned) (old >> 32));
+    for (int which = 0; which < 2; which++)
+      if (win[which])
+        {
+          const unsigned w = w0 + (which ? nw0 + (unsigned) __popcll (bw1 & below) : (unsigned) __popcll (bw0 & below));
+          wins[w] = (uint32_t) o_win[which];
+          if (walk[which])
+            walks[k0 + (which ? nk0 + (unsigned) __popcll (bk1 & below) : (unsigned) __popcll (bk0 & below))] = w;
+        }
+  }
   m1[it] = r1;
   if (m2)
     m2[it] = r2;
